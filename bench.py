@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Benchmark of the hot path: U-Net training step (forward + dice_bce_mc + backward + SGD), images/sec.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 Workload = BASELINE.json configs[1]: UNet(1, 2, 64), 512x512, batch 16 per GPU, fp16 storage with fp32
@@ -150,6 +150,28 @@ def cpu_baseline(cin, ncls, f, H, W, budget_s=25.0):
             "cpu": model}
 
 
+DUMP_BUDGET_BYTES = 60 << 20
+
+
+def dump_outputs(out_dir, loss, model):
+    """Writes what the caller of the timed step holds after its last step as out_dir/<name>.npy (float32): the loss,
+    every floating-point tensor of the model's state_dict (updated parameters, BatchNorm running statistics) as
+    `state.<key>`, and the step's gradients as `grad.<param>`.  A tensor larger than its share of DUMP_BUDGET_BYTES is
+    written as a fixed sample (the same seeded element indices in every run), so two builds compare output for output."""
+    import numpy as np
+    arrays = {"loss": loss.detach().reshape(1)}
+    arrays.update(("state." + k, v) for k, v in model.state_dict().items() if v.is_floating_point())
+    arrays.update(("grad." + k, p.grad) for k, p in model.named_parameters() if p.grad is not None)
+    cap = max(1, min(1 << 18, DUMP_BUDGET_BYTES // 4 // len(arrays)))
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in arrays.items():
+        flat = t.detach().float().reshape(-1).cpu()
+        if flat.numel() > cap:
+            idx = torch.randperm(flat.numel(), generator=torch.Generator().manual_seed(0))[:cap].sort().values
+            flat = flat[idx]
+        np.save(os.path.join(out_dir, name + ".npy"), flat.numpy())
+
+
 def self_launch(n, argv):
     """Parent of a multi-GPU run started from a plain shell: one child rank per GPU via torch.distributed.run."""
     import socket
@@ -181,7 +203,11 @@ def main():
     ap.add_argument("--graph", action="store_true", help="(default on one GPU) replay the step from a captured HIP graph")
     ap.add_argument("--eager", action="store_true",
                     help="issue every step's ~350 launches from Python instead of replaying a captured HIP graph of the step")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write the last step's loss, updated state and gradients to DIR/<name>.npy")
     a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -378,6 +404,8 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = t.item()
     final_loss = float(loss.detach())
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, loss, model)
 
     if rank == 0:
         ms = dt / a.steps * 1e3
