@@ -351,6 +351,19 @@ int umi_dice_ce_fwd(const float* logits, const void* target, int target_dtype, i
 int umi_dice_ce_bwd(const float* logits, const void* target, int target_dtype, const float* stats, const float* gout, int N,
                     int C, long HW, float* dlogits, umi_stream_t stream);
 
+/* HausdorffDTLoss (reference loss.py:146-212) on fp32 logits `pred` and targets [B,C,H,W], C == 1, 1 <= H, W <= 4096,
+ * B <= 65535:
+ * s = sigmoid(pred); field(x)[b] = exact Euclidean distance of each pixel to the nearest pixel of the other class of
+ * x[b] > 0.5 (0 if x[b] has no foreground, sqrt(1 + h^2 + w^2) if it has no background, as scipy's edt of the (1,H,W) slice);
+ * D = field(s)^alpha + field(target)^alpha; loss = mean((s - target)^2 * D), summed in a fixed order (deterministic).
+ * fwd writes D[B*H*W], loss[1] and, if `fields` is not NULL, fields[2*B*H*W] = {field(s) | field(target)};
+ * bwd writes dpred = gout[0] * 2 (s - t) s (1 - s) D / (B*H*W) (gout: device pointer, or NULL for 1). */
+size_t umi_hdt_ws_bytes(int B, int H, int W);
+int umi_hdt_fwd(const float* pred, const float* target, int B, int C, int H, int W, float alpha, float* D, float* fields,
+                float* loss, void* ws, size_t ws_bytes, umi_stream_t stream);
+int umi_hdt_bwd(const float* pred, const float* target, const float* D, const float* gout, int B, int C, int H, int W,
+                float* dpred, umi_stream_t stream);
+
 /* Multi-tensor optimizer step: torch.optim.SGD / torch.optim.Adam arithmetic (reference train.py:341-347) on every parameter
  * tensor of a model in ONE launch.  `descs` is a DEVICE array of n_desc umi_optim_desc sorted by blk0; a tensor of n elements
  * occupies ceil(n / umi_optim_block_elems()) consecutive blocks starting at blk0; total_blocks = the sum.

@@ -7,9 +7,15 @@ the softmax (DiceLoss, loss.py:215-251: per-class `1 - (2*sum(p*t)+1e-5)/(sum(p*
 over the whole batch, mean over classes).  It runs as fp32 device ops on the logits the HIP
 network returns; unlike the reference it does not `.item()`-sync once per class.
 
-The dataset-specific research losses of the reference (Hausdorff, ActiveContour, Focal/Tversky,
-TopK, ...) are out of the hot-path scope and raise.
+'HausdorffDTLoss' (loss.py:146-212, dispatched at :508) runs on the device as HIP kernels
+(csrc/hausdorff_dt.hip): the exact distance fields, D and the loss without a host round trip, so
+it stays inside a captured graph.  CPU tensors use a NumPy restatement of the same separable exact
+transform, bit-identical to the reference's scipy fields.
+
+The other dataset-specific research losses of the reference (HausdorffER, ActiveContour,
+Focal/Tversky, TopK, ...) are out of the hot-path scope and raise.
 """
+import numpy as np
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
@@ -42,7 +48,7 @@ class DiceLoss(nn.Module):
 
 
 _OUT_OF_SCOPE = {"TopK", "BCE_HEM", "FL", "dice", "dice_bce", "dice_score", "log_cosh_dice_loss", "dice_score_mc",
-                 "HausdorffDTLoss", "HausdorffERLoss", "ActiveContourLoss", "Tversky"}
+                 "HausdorffERLoss", "ActiveContourLoss", "Tversky"}
 
 
 _TARGET_DTYPES = {torch.int64: 0, torch.float32: 1, torch.uint8: 2, torch.int32: 3}
@@ -83,6 +89,134 @@ def _fused_ok(pred, target):
             and target.shape[0] == pred.shape[0] and tuple(target.shape[1:]) == tuple(pred.shape[2:]))
 
 
+# ---------------------------------------------------------------------------------------------------------------------
+# HausdorffDTLoss (reference loss.py:146-212)
+
+_BIG = 1 << 20         # row-index sentinel of "no pixel of that class in this column" (H <= 4096 << _BIG)
+_INF = 1 << 40         # squared-distance infinity
+
+
+def _col_sq(mask):
+    """Squared distance of every pixel of `mask` (H, W) to the nearest True pixel of its own column, _INF if none."""
+    H = mask.shape[0]
+    r = np.arange(H, dtype=np.int64)[:, None]
+    above = np.maximum.accumulate(np.where(mask, r, -_BIG), axis=0)
+    below = np.minimum.accumulate(np.where(mask, r, _BIG)[::-1], axis=0)[::-1]
+    d = np.minimum(r - above, below - r)
+    return np.where(d > H, _INF, d * d)
+
+
+def _row_min(g2):
+    """Exact min over w' of g2[h, w'] + (w - w')^2 per row, searched outward: a column k away adds k^2, so the search
+    stops once k^2 reaches the largest current minimum (the kernel's hdt_row_d2, vectorised over the image)."""
+    best = g2.copy()
+    W = g2.shape[1]
+    for k in range(1, W):
+        kk = k * k
+        if kk >= best.max():
+            break
+        np.minimum(best[:, k:], g2[:, :-k] + kk, out=best[:, k:])
+        np.minimum(best[:, :-k], g2[:, k:] + kk, out=best[:, :-k])
+    return best
+
+
+def _distance_field(img):
+    """The reference's `HausdorffDTLoss.distance_field` on (B, 1, H, W) float32: per image, the Euclidean distance of
+    every pixel to the nearest pixel of the other class of img > 0.5 -- edt(fg) + edt(~fg) -- zero if the image has no
+    foreground, sqrt(1 + h^2 + w^2) if it has no background (scipy's edt of an all-ones (1, H, W) slice).  Squared
+    distances are exact integers; the float64 root cast to float32 is scipy's value bit for bit."""
+    field = np.zeros(img.shape, dtype=np.float32)
+    for b in range(len(img)):
+        fg = img[b, 0] > 0.5
+        if not fg.any():
+            continue
+        if fg.all():
+            h, w = np.mgrid[0:fg.shape[0], 0:fg.shape[1]]
+            d2 = 1 + h.astype(np.int64) ** 2 + w.astype(np.int64) ** 2
+        else:
+            d2 = np.where(fg, _row_min(_col_sq(~fg)), _row_min(_col_sq(fg)))
+        field[b, 0] = np.sqrt(d2.astype(np.float64)).astype(np.float32)
+    return field
+
+
+def _hdt_check(pred, target):
+    if pred.dim() != 4 or tuple(pred.shape) != tuple(target.shape) or pred.shape[1] != 1:
+        raise NotImplementedError(f"HausdorffDTLoss supports pred and target of one shape (B, 1, H, W); got pred "
+                                  f"{tuple(pred.shape)} and target {tuple(target.shape)}")
+
+
+class _HausdorffDT(torch.autograd.Function):
+    """HausdorffDTLoss on device tensors: csrc/hausdorff_dt.hip computes the fields, D and the loss (forward) and
+    d loss / d pred (backward); D is kept for the backward, the fields only when asked for (debug)."""
+
+    @staticmethod
+    def forward(ctx, pred, target, alpha, fields):
+        from umi import lib as L, ops
+        B, C, H, W = pred.shape
+        D = torch.empty_like(pred)
+        loss = torch.empty((), dtype=torch.float32, device=pred.device)
+        ws = ops.workspace(L.fn("umi_hdt_ws_bytes")(B, H, W), pred.device)
+        L.check(L.fn("umi_hdt_fwd")(pred.data_ptr(), target.data_ptr(), B, C, H, W, alpha, D.data_ptr(),
+                                    None if fields is None else fields.data_ptr(), loss.data_ptr(), ws.data_ptr(),
+                                    ws.numel(), ops._stream()), "umi_hdt_fwd")
+        ctx.save_for_backward(pred, target, D)
+        ctx.mark_non_differentiable(D)
+        return loss, D
+
+    @staticmethod
+    def backward(ctx, gout, _gD):
+        from umi import lib as L, ops
+        pred, target, D = ctx.saved_tensors
+        B, C, H, W = pred.shape
+        g = gout.detach().to(torch.float32).contiguous()
+        dpred = torch.empty_like(pred)
+        L.check(L.fn("umi_hdt_bwd")(pred.data_ptr(), target.data_ptr(), D.data_ptr(), g.data_ptr(), B, C, H, W,
+                                    dpred.data_ptr(), ops._stream()), "umi_hdt_bwd")
+        return dpred, None, None, None
+
+
+class HausdorffDTLoss(nn.Module):
+    """Binary Hausdorff loss based on distance transform (reference loss.py:146-212): loss = mean((s - t)^2 * D),
+    s = sigmoid(pred), D = field(s)^alpha + field(target)^alpha.  pred, target: (B, 1, H, W).  The target is a label and
+    gets no gradient."""
+
+    def __init__(self, alpha=0.2, **kwargs):
+        super().__init__()
+        self.alpha = alpha
+
+    @torch.no_grad()
+    def distance_field(self, img: np.ndarray) -> np.ndarray:
+        return _distance_field(img)
+
+    def forward(self, pred, target, debug=False):
+        _hdt_check(pred, target)
+        if pred.is_cuda:
+            if pred.dtype != torch.float32:
+                raise NotImplementedError(f"HausdorffDTLoss on the device takes fp32 logits, got {pred.dtype}")
+            pred = pred.contiguous()
+            target = target.to(device=pred.device, dtype=torch.float32).contiguous()
+            fields = torch.empty((2,) + tuple(pred.shape), dtype=torch.float32, device=pred.device) if debug else None
+            loss, distance = _HausdorffDT.apply(pred, target, float(self.alpha), fields)
+            if not debug:
+                return loss
+            s = torch.sigmoid(pred)
+            pred_error = (s - target) ** 2
+            pred_dt, target_dt = fields[0], fields[1]
+        else:
+            s = torch.sigmoid(pred)
+            pred_dt = torch.from_numpy(self.distance_field(s.detach().cpu().numpy())).float()
+            target_dt = torch.from_numpy(self.distance_field(target.detach().cpu().float().numpy())).float()
+            pred_error = (s - target) ** 2
+            distance = pred_dt ** self.alpha + target_dt ** self.alpha
+            loss = (pred_error * distance).mean()
+            if not debug:
+                return loss
+        dt_field = pred_error * distance
+        return (loss.detach().cpu().numpy(),
+                (dt_field.detach().cpu().numpy()[0, 0], pred_error.detach().cpu().numpy()[0, 0],
+                 distance.cpu().numpy()[0, 0], pred_dt.cpu().numpy()[0, 0], target_dt.cpu().numpy()[0, 0]))
+
+
 def calc_loss(pred, target, bce_weight=0.5, loss_type='mse'):
     if loss_type == 'dice_bce_mc':
         if _fused_ok(pred, target):
@@ -102,6 +236,8 @@ def calc_loss(pred, target, bce_weight=0.5, loss_type='mse'):
         return torch.sqrt(F.mse_loss(pred, target))
     if loss_type == 'l1loss':
         return F.l1_loss(pred, target)
+    if loss_type == 'HausdorffDTLoss':
+        return HausdorffDTLoss()(pred, target, debug=False)
     if loss_type in _OUT_OF_SCOPE:
         raise NotImplementedError(f"loss_type {loss_type!r} is outside the MI355X hot-path scope")
     raise ValueError(f"unknown loss_type {loss_type!r}")
