@@ -10,8 +10,15 @@ against SciPy itself (tests/test_oracle_resize.py, fixtures tests/golden/zoom_cu
   2. B-spline prefilter in float64 along every zoomed axis: gain (1 - z)(1 - 1/z) = 6, pole z = sqrt(3) - 2, MIRROR boundary
      initialisation of the causal / anticausal recursions (mode 'constant' filters as 'mirror');
   3. output[i] = sum of 4 x 4 coefficients around floor(x) - 1 with the cubic B-spline weights, support indices mirrored;
+     except that mode 'constant' writes cval = 0 wherever the coordinate x = i * ((in - 1) / (out - 1)), evaluated in float64,
+     is < 0 or > in - 1 on either axis (ni_interpolation.c map_coordinate).  The last x rounds just above in - 1 for some
+     sizes (e.g. 32, 512, 1000, 2048 -> 224), and SciPy's whole last output row / column is then 0;
   4. integer inputs: the float64 value is rounded to nearest (floor(v + 0.5)) and clipped to the input type's range
-     (cv2.imread gives uint8); float inputs keep their type."""
+     (cv2.imread gives uint8); float inputs keep their type.
+
+SciPy's float64 spline coefficients differ from the ones of this restatement in the last bits (a few to ~1000 ulp, measured
+against SciPy 1.15), so an output whose exact value is a half-way point k + 0.5 may round either way.  `halfway` marks those;
+they turn up at 2- and 3-pixel axes, where the sampling coordinates are short binary fractions."""
 import numpy as np
 
 _POLE = np.sqrt(3.0) - 2.0
@@ -60,10 +67,11 @@ def _mirror(idx, n):
 
 
 def _axis_plan(n_in, n_out):
+    """Support indices [n_out, 4], weights [n_out, 4] and the out-of-range mask [n_out] (constant mode: output 0) of one axis."""
     x = np.arange(n_out, dtype=np.float64) * ((n_in - 1) / (n_out - 1) if n_out > 1 else 0.0)
     f = np.floor(x)
     idx = _mirror(f.astype(np.int64)[:, None] - 1 + np.arange(4)[None, :], n_in)
-    return idx, _weights(x - f)
+    return idx, _weights(x - f), (x < 0.0) | (x > float(n_in - 1))
 
 
 def zoom_cubic(img, out_hw):
@@ -74,8 +82,8 @@ def zoom_cubic(img, out_hw):
     c = img.astype(np.float64, copy=True)
     _prefilter_axis(c, 0)
     _prefilter_axis(c, 1)
-    iy, wy = _axis_plan(H, oh)
-    ix, wx = _axis_plan(W, ow)
+    iy, wy, zy = _axis_plan(H, oh)
+    ix, wx, zx = _axis_plan(W, ow)
     # rows first, in SciPy's accumulation order: sum over ky of wy * (sum over kx of wx * c)
     out = np.zeros((oh, ow) + img.shape[2:], dtype=np.float64)
     for ky in range(4):
@@ -85,7 +93,15 @@ def zoom_cubic(img, out_hw):
             wgt = wx[:, kx].reshape((1, ow) + (1,) * (img.ndim - 2))
             acc += wgt * rows[:, ix[:, kx]]
         out += wy[:, ky].reshape((oh, 1) + (1,) * (img.ndim - 2)) * acc
+    out[zy] = 0.0                                                 # cval of mode 'constant'
+    out[:, zx] = 0.0
     if np.issubdtype(img.dtype, np.integer):
         info = np.iinfo(img.dtype)
         out = np.clip(np.floor(out + 0.5), info.min, info.max)
     return out.astype(img.dtype)
+
+
+def halfway(img, out_hw, tol=1e-9):
+    """Mask of the outputs of integer image `img` whose float64 value lies within `tol` of a rounding half-way point k + 0.5."""
+    v = zoom_cubic(np.asarray(img).astype(np.float64), out_hw)
+    return np.abs(v - np.floor(v) - 0.5) < tol

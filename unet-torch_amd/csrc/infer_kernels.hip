@@ -108,10 +108,14 @@ __global__ __launch_bounds__(256) void argmax_mask_kernel(const float* __restric
 // oracle/ref_resize.py and pinned against SciPy itself there:
 //   1. cubic B-spline prefilter in float64 along H, then W: gain 6, pole sqrt(3) - 2, MIRROR initialisation (mode 'constant'
 //      filters as 'mirror');
-//   2. corner-aligned sampling x = i * (in - 1) / (out - 1), 4 x 4 coefficients around floor(x) - 1, mirrored indices;
-//   3. uint8 images: floor(v + 0.5) clipped to [0, 255] (the output has the input's type).
-// All arithmetic in float64 without contraction (SciPy's generic x86-64 build has no FMA): uint8 results are identical to SciPy's,
-// float32 ones to the last bit of the float64 -> float32 rounding except where summation order differs by an ulp of float64.
+//   2. corner-aligned sampling x = i * ((in - 1) / (out - 1)), 4 x 4 coefficients around floor(x) - 1, mirrored indices;
+//   3. mode 'constant' (cval 0): an output whose x is < 0 or > in - 1 on either axis is 0 (ni_interpolation.c map_coordinate).
+//      x is the same float64 product as SciPy's, and the last one rounds just above in - 1 for some sizes (e.g. 32, 512, 1000,
+//      2048 -> 224): SciPy's whole last output row / column is then 0, and so is ours;
+//   4. uint8 images: floor(v + 0.5) clipped to [0, 255] (the output has the input's type).
+// All arithmetic in float64 without contraction, the oracle's sequence of operations.  SciPy's spline coefficients differ from
+// those in the last float64 bits, so uint8 results are SciPy's except at exact half-way values k + 0.5 (2- and 3-pixel axes), and
+// float32 ones are within one float32 ulp of SciPy's.
 #pragma clang fp contract(off)
 constexpr double ZC_POLE = -0.26794919243112270647;       // sqrt(3) - 2
 
@@ -151,14 +155,17 @@ __device__ inline int zc_mirror(int idx, int n) {
     idx = (idx < 0 ? -idx : idx) % s2;
     return idx >= n ? s2 - idx : idx;
 }
-__device__ inline void zc_plan(int i, int n_in, int n_out, int idx[4], double w[4]) {
+// returns false when x lies outside [0, n_in - 1] (step 3: the output is cval = 0)
+__device__ inline bool zc_plan(int i, int n_in, int n_out, int idx[4], double w[4]) {
     const double x = (double)i * (n_out > 1 ? (double)(n_in - 1) / (double)(n_out - 1) : 0.0);
+    if (x < 0.0 || x > (double)(n_in - 1)) return false;
     const double f = floor(x), t = x - f, z = 1.0 - t;
     w[1] = (t * t * (t - 2.0) * 3.0 + 4.0) / 6.0;
     w[2] = (z * z * (z - 2.0) * 3.0 + 4.0) / 6.0;
     w[0] = z * z * z / 6.0;
     w[3] = 1.0 - w[0] - w[1] - w[2];
     for (int k = 0; k < 4; ++k) idx[k] = zc_mirror((int)f - 1 + k, n_in);
+    return true;
 }
 
 template <typename T>
@@ -169,8 +176,12 @@ __global__ __launch_bounds__(256) void zoom_sample_kernel(const double* __restri
     const int ch = (int)(t % C), ox = (int)((t / C) % ow), oy = (int)(t / ((long)C * ow));
     int iy[4], ix[4];
     double wy[4], wx[4];
-    zc_plan(oy, H, oh, iy, wy);
-    zc_plan(ox, W, ow, ix, wx);
+    const bool inside_y = zc_plan(oy, H, oh, iy, wy);
+    const bool inside_x = zc_plan(ox, W, ow, ix, wx);
+    if (!inside_y || !inside_x) {
+        out[t] = (T)0;
+        return;
+    }
     double v = 0.0;
     for (int ky = 0; ky < 4; ++ky) {
         double acc = 0.0;

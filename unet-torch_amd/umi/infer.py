@@ -17,7 +17,11 @@ from . import ops
 
 def zoom_cubic(img, input_size):
     """scipy.ndimage.zoom(img, (input_size[0] / H, input_size[1] / W[, 1]), order=3) of one HWC / HW image on the device
-    (reference test_mc3serousv5.py:100-113); uint8 or float32 in, same type out.  `img`: numpy array or tensor."""
+    (reference test_mc3serousv5.py:100-113); uint8 or float32 in, same type out.  `img`: numpy array or tensor.
+    Like SciPy's default mode='constant', an output whose sample coordinate i * ((in - 1) / (out - 1)) (float64) lies above
+    in - 1 on either axis is 0: the whole last row / column for some sizes, e.g. 32, 512, 1000, 2048 -> 224.  uint8 outputs are
+    SciPy's except at exact half-way values k + 0.5 (2- and 3-pixel axes), which may round the other way; float32 outputs are
+    within one float32 ulp of SciPy's (oracle/ref_resize.py, tests/test_oracle_resize.py)."""
     if isinstance(img, np.ndarray):
         img = torch.from_numpy(np.ascontiguousarray(img))
     hw = img.dim() == 2
@@ -44,7 +48,8 @@ def preprocess(img, reverse_channels=None, input_size=None):
     test_mc3serousv5.py:124: BGR -> RGB for cv2 images, but 2- and 4-channel inputs are reversed as well) and leaves 2-D
     (HW) inputs alone; `reverse_channels=None` follows that rule, True / False override it.
     `input_size` = (H, W) of the network input: an image of another size is first resized like the reference does, with the
-    cubic `scipy.ndimage.zoom` (zoom_cubic above: on the device, same values)."""
+    cubic `scipy.ndimage.zoom` (zoom_cubic above, on the device: SciPy's values, zeroed last row / column included, up to the
+    half-way and ulp caveats there)."""
     if input_size is not None:
         shp = img.shape
         if shp[0] != input_size[0] or shp[1] != input_size[1]:
