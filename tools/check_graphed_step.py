@@ -1,5 +1,7 @@
-"""Child-process body of tests/test_gpu_unet.py::test_graphed_step_matches_eager_trajectory."""
-import copy, os, sys
+"""Child-process body of tests/test_gpu_unet.py::test_graphed_step_matches_eager_trajectory (the defaults) and of
+tests/test_gpu_exact_fullsize.py::test_graphed_step_matches_eager_at_bench_scale (--features 64 --size 512 --batch 16).
+usage: python tools/check_graphed_step.py [torch] [--features 8] [--size 64] [--batch 2]"""
+import argparse, copy, os, sys
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [REPO, os.path.join(REPO, "unet-torch_amd")]
 import torch
@@ -7,19 +9,25 @@ import Model
 import loss as L
 from umi.graphs import GraphedStep
 
+ap = argparse.ArgumentParser()
+ap.add_argument("opt", nargs="?", choices=["umi", "torch"], default="umi")
+ap.add_argument("--features", type=int, default=8)
+ap.add_argument("--size", type=int, default=64)
+ap.add_argument("--batch", type=int, default=2)
+a = ap.parse_args()
 DEV = "cuda"
 L.CLASS_NUMBER = 2
 torch.manual_seed(21)
-base = Model.UNet(1, 2, 8, compute_dtype="fp16").to(DEV).train()
-x = torch.randn(2, 1, 64, 64, device=DEV)
-lab = torch.randint(0, 2, (2, 64, 64), device=DEV).float()
+base = Model.UNet(1, 2, a.features, compute_dtype="fp16").to(DEV).train()
+x = torch.randn(a.batch, 1, a.size, a.size, device=DEV)
+lab = torch.randint(0, 2, (a.batch, a.size, a.size), device=DEV).float()
 
 
 def make(model):
     # the fused optimizer (one launch per step; its descriptor table is uploaded from pinned memory, also under capture)
     # unless "torch" is passed on the command line
     from umi import optim as umi_optim
-    cls = torch.optim.SGD if "torch" in sys.argv[1:] else umi_optim.SGD
+    cls = torch.optim.SGD if a.opt == "torch" else umi_optim.SGD
     opt = cls(model.parameters(), lr=0.05, momentum=0.9, weight_decay=1e-4)
 
     def step(xx, yy):
@@ -42,4 +50,6 @@ for i in range(4):
     assert torch.equal(lg, le.detach()), (i, float(lg), float(le))
 for pg, pe in zip(m_g.parameters(), m_e.parameters()):
     assert torch.equal(pg, pe)
+    assert torch.isfinite(pg).all()
+assert torch.isfinite(lg).all()
 print("GRAPHED_STEP_OK", float(lg))
