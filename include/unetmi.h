@@ -364,6 +364,45 @@ int umi_hdt_fwd(const float* pred, const float* target, int B, int C, int H, int
 int umi_hdt_bwd(const float* pred, const float* target, const float* D, const float* gout, int B, int C, int H, int W,
                 float* dpred, umi_stream_t stream);
 
+/* Binary-segmentation losses of the reference calc_loss (loss.py:442-516) on NCHW fp32 logits `pred`, s = sigmoid(pred),
+ * bce = (1 - t) * pred - log_sigmoid(pred) per pixel.  Every sum is fixed-order with fp64 across threads (deterministic); the
+ * workspace holds only per-call scratch, what the backward needs is in the caller's `stats` / `mask`.  gout: device pointer
+ * to the upstream scalar gradient, or NULL for 1.  Limits: B <= 65535, B*C*HW < 2^31, C <= 8 (else UMI_ERR_UNSUPPORTED).
+ *
+ * 'dice_bce' (loss.py:484-487, BinaryDiceLoss :254-307): pred [B,1,HW], target fp32 [B,HW];
+ *   loss = 0.5 * mean(bce) + 0.5 * mean_b(1 - (2*sum_b s*t + 1) / (sum_b |s| + sum_b |t| + 1)).
+ *   fwd writes stats[5*B] (fp64, per image {sum s*t, sum s, sum |t|, sum t, sum bce}) and loss[1];
+ *   bwd writes dpred = gout[0] * d loss / d pred from those stats.
+ * 'Tversky' (loss.py:514-515, FocalTverskyLoss :380-420 with gamma 1): tv(TP, P, T) = (TP + 1) / (TP + alpha*(P - TP) +
+ *   beta*(T - TP) + 1).  C == 1: target fp32 [B,HW] (target_dtype 1 only), TP = sum s*t, P = sum s, T = sum t over the batch,
+ *   loss = 1 - tv, stats[5*B] as for dice_bce.  2 <= C <= 8: p = softmax(pred) over C, target [B,HW] labels (target_dtype
+ *   0 = int64, 1 = float32, 2 = uint8, 3 = int32; a value that is not an integer in [0, C) matches no class),
+ *   TP_c = sum p_c*[t==c], P_c = sum p_c, T_c = sum [t==c], loss = mean_c(1 - tv_c), stats[3*C] = {TP | P | T}.
+ * umi_binloss_ws_bytes(B, C, HW) sizes the workspace of both forwards. */
+size_t umi_binloss_ws_bytes(int B, int C, long HW);
+int umi_dice_bce_fwd(const float* pred, const float* target, int B, long HW, double* stats, float* loss, void* ws,
+                     size_t ws_bytes, umi_stream_t stream);
+int umi_dice_bce_bwd(const float* pred, const float* target, const double* stats, const float* gout, int B, long HW,
+                     float* dpred, umi_stream_t stream);
+int umi_tversky_fwd(const float* pred, const void* target, int target_dtype, int B, int C, long HW, float alpha, float beta,
+                    double* stats, float* loss, void* ws, size_t ws_bytes, umi_stream_t stream);
+int umi_tversky_bwd(const float* pred, const void* target, int target_dtype, const double* stats, const float* gout, int B,
+                    int C, long HW, float alpha, float beta, float* dpred, umi_stream_t stream);
+
+/* Hard-pixel losses on fp32 logits `pred` and fp32 targets of N = B*H*W elements (C == 1, flat NCHW order), 1 <= k <= N < 2^31:
+ * loss = sum of bce over the selected set / k.  mode 0 'TopK' (loss.py:445-446, TopKLoss :354-378): the k pixels of LOWEST
+ * true-class probability sigmoid(pred) where trunc(t) == 1, 1 - sigmoid(pred) otherwise (the reference's gather index
+ * t.long(); other values are an error there and count as 0 here), k = N // 2.  mode 1 'BCE_HEM' (loss.py:447-467): the k
+ * pixels of LARGEST bce, k = 500.  The set is exact: a radix select on the fp32 key finds the threshold T and how many keys
+ * equal to T are taken; among those, the lowest flat indices are.  Nothing is read back to the host.
+ * fwd writes mask[N] (1 = selected, else 0) and loss[1]; bwd writes dpred = mask * gout[0] * (s - t) / k.
+ * mask: 4-byte aligned for the vector path (any alignment works). */
+size_t umi_topk_loss_ws_bytes(long N);
+int umi_topk_loss_fwd(const float* pred, const float* target, long N, long k, int mode, unsigned char* mask, float* loss,
+                      void* ws, size_t ws_bytes, umi_stream_t stream);
+int umi_topk_loss_bwd(const float* pred, const float* target, const unsigned char* mask, const float* gout, long N, long k,
+                      float* dpred, umi_stream_t stream);
+
 /* Multi-tensor optimizer step: torch.optim.SGD / torch.optim.Adam arithmetic (reference train.py:341-347) on every parameter
  * tensor of a model in ONE launch.  `descs` is a DEVICE array of n_desc umi_optim_desc sorted by blk0; a tensor of n elements
  * occupies ceil(n / umi_optim_block_elems()) consecutive blocks starting at blk0; total_blocks = the sum.

@@ -12,8 +12,16 @@ network returns; unlike the reference it does not `.item()`-sync once per class.
 it stays inside a captured graph.  CPU tensors use a NumPy restatement of the same separable exact
 transform, bit-identical to the reference's scipy fields.
 
-The other dataset-specific research losses of the reference (HausdorffER, ActiveContour,
-Focal/Tversky, TopK, ...) are out of the hot-path scope and raise.
+The binary-segmentation losses 'dice_bce' (loss.py:484-487), 'Tversky' (:514-515), 'TopK' (:445-446) and 'BCE_HEM'
+(:447-467) run on the device as HIP kernels (csrc/binary_losses.hip) for contiguous fp32 logits of the shapes the kernels
+cover: streaming statistics with fp64 fixed-order sums for dice_bce and Tversky, and an exact device radix select of the
+k-th key for TopK and BCE_HEM (ties go to the lowest flat index), so no value travels to the host and a step with any of
+them can be captured in a graph.  Every other input (CPU tensors, other dtypes or shapes) runs a torch composite that
+restates the reference branch and raises where it raises.
+
+The remaining names raise NotImplementedError: 'dice', 'dice_score', 'dice_score_mc' and 'log_cosh_dice_loss' call
+DiceLoss() without n_classes, 'FL' names an undefined BinaryFocalLoss, HausdorffERLoss has no gradient and
+ActiveContourLoss hard-codes 512x512 tensors on cuda:0 in the reference itself.
 """
 import numpy as np
 import torch
@@ -47,8 +55,7 @@ class DiceLoss(nn.Module):
         return total / self.n_classes
 
 
-_OUT_OF_SCOPE = {"TopK", "BCE_HEM", "FL", "dice", "dice_bce", "dice_score", "log_cosh_dice_loss", "dice_score_mc",
-                 "HausdorffERLoss", "ActiveContourLoss", "Tversky"}
+_OUT_OF_SCOPE = {"FL", "dice", "dice_score", "log_cosh_dice_loss", "dice_score_mc", "HausdorffERLoss", "ActiveContourLoss"}
 
 
 _TARGET_DTYPES = {torch.int64: 0, torch.float32: 1, torch.uint8: 2, torch.int32: 3}
@@ -217,6 +224,202 @@ class HausdorffDTLoss(nn.Module):
                  distance.cpu().numpy()[0, 0], pred_dt.cpu().numpy()[0, 0], target_dt.cpu().numpy()[0, 0]))
 
 
+# ---------------------------------------------------------------------------------------------------------------------
+# dice_bce, Tversky, TopK, BCE_HEM (reference loss.py:254-307, 344-420, 442-516)
+
+TVERSKY_ALPHA, TVERSKY_BETA = 0.4, 0.6     # calc_loss's FocalTverskyLoss(alpha=0.4, beta=0.6), gamma 1, smooth 1
+BCE_HEM_K = 500
+_TOPK, _BCE_HEM = 0, 1
+
+
+def _flatten(pred, target):
+    """The reference's `flatten` (loss.py:344-352): (B, C, H, W) -> (B*H*W, C), target -> (B*H*W,)."""
+    return pred.permute(0, 2, 3, 1).contiguous().view(-1, pred.size(1)), target.view(-1)
+
+
+def _binary_dice(pred, target):
+    """BinaryDiceLoss() (loss.py:254-307) on logits: per-image 1 - (2 sum(s t) + 1) / (sum(|s| + |t|) + 1), mean."""
+    s = torch.sigmoid(pred)
+    s = s.contiguous().view(s.shape[0], -1)
+    t = target.contiguous().view(target.shape[0], -1).float()
+    num = 2 * torch.sum(torch.mul(s, t), dim=1) + 1
+    den = torch.sum(s.abs() + t.abs(), dim=1) + 1
+    return (1 - num / den).mean()
+
+
+def dice_bce_composite(pred, target):
+    p = pred.squeeze(1)
+    return 0.5 * F.binary_cross_entropy_with_logits(p, target) + 0.5 * _binary_dice(p, target)
+
+
+def tversky_composite(pred, target, alpha=TVERSKY_ALPHA, beta=TVERSKY_BETA, smooth=1.0):
+    pred, target = _flatten(pred, target)
+    if pred.size(1) == 1:
+        p = torch.sigmoid(pred[:, 0])
+        t_p = (p * target).sum()
+        f_p = ((1 - target) * p).sum()
+        f_n = (target * (1 - p)).sum()
+        return 1 - (t_p + smooth) / (t_p + alpha * f_p + beta * f_n + smooth)
+    p = F.softmax(pred, dim=1)
+    losses = []
+    for c in range(pred.size(1)):
+        t_c = (target == c).float()
+        p_c = p[:, c]
+        t_p = (p_c * t_c).sum()
+        f_p = ((1 - t_c) * p_c).sum()
+        f_n = (t_c * (1 - p_c)).sum()
+        losses.append(1 - (t_p + smooth) / (t_p + alpha * f_p + beta * f_n + smooth))
+    return torch.stack(losses).mean()
+
+
+def topk_composite(pred, target):
+    pred, target = _flatten(pred, target)
+    p = pred[:, 0]
+    fg = torch.sigmoid(p)
+    prob = torch.gather(torch.stack((1 - fg, fg), dim=1), 1, target.unsqueeze(1).long())[:, 0]
+    _, idx = torch.topk(prob, len(target) // 2, largest=False)
+    ce = F.binary_cross_entropy_with_logits(p, target, reduction='none')
+    mask = torch.zeros_like(ce)
+    mask[idx] = 1
+    return ce[mask > 0].mean()
+
+
+def bce_hem_composite(pred, target):
+    loss_f = F.binary_cross_entropy_with_logits(pred.squeeze(1), target, reduction='none').flatten()
+    _, idx = torch.topk(loss_f, BCE_HEM_K)
+    mask = torch.zeros_like(loss_f)
+    mask[idx] = 1
+    return (loss_f * mask).sum() / mask.sum()
+
+
+class _DiceBCE(torch.autograd.Function):
+    """'dice_bce' on (B, 1, H, W) fp32 device logits: umi_dice_bce_fwd / _bwd; the fp64 per-image stats are saved."""
+
+    @staticmethod
+    def forward(ctx, pred, target):
+        from umi import lib as L, ops
+        B, HW = pred.shape[0], pred[0, 0].numel()
+        stats = torch.empty(5 * B, dtype=torch.float64, device=pred.device)
+        loss = torch.empty((), dtype=torch.float32, device=pred.device)
+        ws = ops.workspace(L.fn("umi_binloss_ws_bytes")(B, 1, HW), pred.device)
+        L.check(L.fn("umi_dice_bce_fwd")(pred.data_ptr(), target.data_ptr(), B, HW, stats.data_ptr(), loss.data_ptr(),
+                                         ws.data_ptr(), ws.numel(), ops._stream()), "umi_dice_bce_fwd")
+        ctx.save_for_backward(pred, target, stats)
+        return loss
+
+    @staticmethod
+    def backward(ctx, gout):
+        from umi import lib as L, ops
+        pred, target, stats = ctx.saved_tensors
+        g = gout.detach().to(torch.float32).contiguous()
+        dpred = torch.empty_like(pred)
+        L.check(L.fn("umi_dice_bce_bwd")(pred.data_ptr(), target.data_ptr(), stats.data_ptr(), g.data_ptr(), pred.shape[0],
+                                         pred[0, 0].numel(), dpred.data_ptr(), ops._stream()), "umi_dice_bce_bwd")
+        return dpred, None
+
+
+class _Tversky(torch.autograd.Function):
+    """'Tversky' on (B, C, H, W) fp32 device logits, C <= 8: umi_tversky_fwd / _bwd; the fp64 stats are saved."""
+
+    @staticmethod
+    def forward(ctx, pred, target, alpha, beta):
+        from umi import lib as L, ops
+        B, C, HW = pred.shape[0], pred.shape[1], pred[0, 0].numel()
+        stats = torch.empty(5 * B if C == 1 else 3 * C, dtype=torch.float64, device=pred.device)
+        loss = torch.empty((), dtype=torch.float32, device=pred.device)
+        ws = ops.workspace(L.fn("umi_binloss_ws_bytes")(B, C, HW), pred.device)
+        L.check(L.fn("umi_tversky_fwd")(pred.data_ptr(), target.data_ptr(), _TARGET_DTYPES[target.dtype], B, C, HW, alpha,
+                                        beta, stats.data_ptr(), loss.data_ptr(), ws.data_ptr(), ws.numel(), ops._stream()),
+                "umi_tversky_fwd")
+        ctx.save_for_backward(pred, target, stats)
+        ctx.ab = (alpha, beta)
+        return loss
+
+    @staticmethod
+    def backward(ctx, gout):
+        from umi import lib as L, ops
+        pred, target, stats = ctx.saved_tensors
+        B, C, HW = pred.shape[0], pred.shape[1], pred[0, 0].numel()
+        g = gout.detach().to(torch.float32).contiguous()
+        dpred = torch.empty_like(pred)
+        L.check(L.fn("umi_tversky_bwd")(pred.data_ptr(), target.data_ptr(), _TARGET_DTYPES[target.dtype], stats.data_ptr(),
+                                        g.data_ptr(), B, C, HW, ctx.ab[0], ctx.ab[1], dpred.data_ptr(), ops._stream()),
+                "umi_tversky_bwd")
+        return dpred, None, None, None
+
+
+class _TopKBCE(torch.autograd.Function):
+    """'TopK' (mode 0) and 'BCE_HEM' (mode 1) on (B, 1, H, W) fp32 device logits: umi_topk_loss_fwd selects the k pixels
+    on the device and writes their mask, which is saved for umi_topk_loss_bwd."""
+
+    @staticmethod
+    def forward(ctx, pred, target, k, mode):
+        from umi import lib as L, ops
+        N = pred.numel()
+        mask = torch.empty(N, dtype=torch.uint8, device=pred.device)
+        loss = torch.empty((), dtype=torch.float32, device=pred.device)
+        ws = ops.workspace(L.fn("umi_topk_loss_ws_bytes")(N), pred.device)
+        L.check(L.fn("umi_topk_loss_fwd")(pred.data_ptr(), target.data_ptr(), N, k, mode, mask.data_ptr(), loss.data_ptr(),
+                                          ws.data_ptr(), ws.numel(), ops._stream()), "umi_topk_loss_fwd")
+        ctx.save_for_backward(pred, target, mask)
+        ctx.k = k
+        return loss
+
+    @staticmethod
+    def backward(ctx, gout):
+        from umi import lib as L, ops
+        pred, target, mask = ctx.saved_tensors
+        g = gout.detach().to(torch.float32).contiguous()
+        dpred = torch.empty_like(pred)
+        L.check(L.fn("umi_topk_loss_bwd")(pred.data_ptr(), target.data_ptr(), mask.data_ptr(), g.data_ptr(), pred.numel(),
+                                          ctx.k, dpred.data_ptr(), ops._stream()), "umi_topk_loss_bwd")
+        return dpred, None, None, None
+
+
+def _device_logits(pred, max_c):
+    return (pred.is_cuda and pred.dtype == torch.float32 and pred.dim() == 4 and pred.is_contiguous()
+            and 1 <= pred.shape[1] <= max_c and 0 < pred.numel() < (1 << 31))
+
+
+def _binary_target_ok(pred, target, exact_shape):
+    """fp32 contiguous device target of B*H*W elements; `exact_shape`: (B, H, W), as BCEWithLogits(pred.squeeze(1), t) needs."""
+    if not (_device_logits(pred, 1) and target.is_cuda and target.dtype == torch.float32 and target.is_contiguous()):
+        return False
+    B, _, H, W = pred.shape
+    return tuple(target.shape) == (B, H, W) if exact_shape else target.numel() == B * H * W
+
+
+def _mc_target_ok(pred, target):
+    B, C, H, W = pred.shape
+    return (C >= 2 and target.is_cuda and target.dtype in _TARGET_DTYPES and target.is_contiguous()
+            and tuple(target.shape) == (B, H, W))
+
+
+def dice_bce_loss(pred, target):
+    if _binary_target_ok(pred, target, exact_shape=True):
+        return _DiceBCE.apply(pred, target)
+    return dice_bce_composite(pred, target)
+
+
+def tversky_loss(pred, target):
+    if _device_logits(pred, 8) and (_binary_target_ok(pred, target, exact_shape=False) if pred.shape[1] == 1
+                                    else _mc_target_ok(pred, target)):
+        return _Tversky.apply(pred, target, TVERSKY_ALPHA, TVERSKY_BETA)
+    return tversky_composite(pred, target)
+
+
+def topk_loss(pred, target):
+    if _binary_target_ok(pred, target, exact_shape=False) and pred.numel() >= 2:
+        return _TopKBCE.apply(pred, target, pred.numel() // 2, _TOPK)
+    return topk_composite(pred, target)
+
+
+def bce_hem_loss(pred, target):
+    if _binary_target_ok(pred, target, exact_shape=True) and pred.numel() >= BCE_HEM_K:
+        return _TopKBCE.apply(pred, target, BCE_HEM_K, _BCE_HEM)
+    return bce_hem_composite(pred, target)
+
+
 def calc_loss(pred, target, bce_weight=0.5, loss_type='mse'):
     if loss_type == 'dice_bce_mc':
         if _fused_ok(pred, target):
@@ -238,6 +441,14 @@ def calc_loss(pred, target, bce_weight=0.5, loss_type='mse'):
         return F.l1_loss(pred, target)
     if loss_type == 'HausdorffDTLoss':
         return HausdorffDTLoss()(pred, target, debug=False)
+    if loss_type == 'dice_bce':
+        return dice_bce_loss(pred, target)
+    if loss_type == 'Tversky':
+        return tversky_loss(pred, target)
+    if loss_type == 'TopK':
+        return topk_loss(pred, target)
+    if loss_type == 'BCE_HEM':
+        return bce_hem_loss(pred, target)
     if loss_type in _OUT_OF_SCOPE:
         raise NotImplementedError(f"loss_type {loss_type!r} is outside the MI355X hot-path scope")
     raise ValueError(f"unknown loss_type {loss_type!r}")

@@ -139,6 +139,17 @@ SIGNATURES = {
     "umi_hdt_fwd": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_float, c_void_p, c_void_p, c_void_p, c_void_p,
                             c_size_t, c_void_p]),
     "umi_hdt_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "umi_binloss_ws_bytes": (c_size_t, [c_int, c_int, c_long]),
+    "umi_dice_bce_fwd": (c_int, [c_void_p, c_void_p, c_int, c_long, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "umi_dice_bce_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_long, c_void_p, c_void_p]),
+    "umi_tversky_fwd": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_long, c_float, c_float, c_void_p, c_void_p,
+                                c_void_p, c_size_t, c_void_p]),
+    "umi_tversky_bwd": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_long, c_float, c_float,
+                                c_void_p, c_void_p]),
+    "umi_topk_loss_ws_bytes": (c_size_t, [c_long]),
+    "umi_topk_loss_fwd": (c_int, [c_void_p, c_void_p, c_long, c_long, c_int, c_void_p, c_void_p, c_void_p, c_size_t,
+                                  c_void_p]),
+    "umi_topk_loss_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_long, c_long, c_void_p, c_void_p]),
     "umi_optim_block_elems": (c_int, []),
     "umi_table_upload": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p]),
     "umi_optim_sgd_multi": (c_int, [c_void_p, c_int, c_int, c_double, c_double, c_double, c_double, c_int, c_int, c_void_p]),
