@@ -403,6 +403,26 @@ int umi_topk_loss_fwd(const float* pred, const float* target, long N, long k, in
 int umi_topk_loss_bwd(const float* pred, const float* target, const unsigned char* mask, const float* gout, long N, long k,
                       float* dpred, umi_stream_t stream);
 
+/* Count-ratio-weighted two-task loss of the reference's multi_task_trainRatio (Trainer.py:1225-1249) on fp32 head outputs
+ * o1, o2 [B,1,HW] and label maps l1, l2 [B,HW] (B <= 65535, B*HW < 2^31, else UMI_ERR_UNSUPPORTED):
+ *   R_k = relu(o_k), L_k = mean((R_k - l_k)^2), rG_b = G1_b / (G2_b + G1_b), rP_b = P1_b / (P2_b + P1_b) with G_k,b = sum of
+ *   l_k over image b and P_k,b = sum of R_k; r = mean_b |rG_b - rP_b|; loss = (L1 + L2) * (1 + 10 r) if `gate`, else L1 + L2.
+ * gate_dev (device, nullable): if given, gate = (gate_dev[0] != 0), read by the kernel, so a captured graph follows it.
+ * A zero denominator makes r NaN, as in torch.  Sums are fp32 per thread, then fp64 in a fixed order (deterministic).
+ * fwd writes loss, loss1, loss2, ratio (fp32 scalars) and stats[umi_mt_ratio_stats_len(B)] (fp64: per image the six sums
+ * {S1, S2, P1, P2, G1, G2} at [6b..6b+5], s_b = sgn(rG_b - rP_b) at [6B + b] with sgn(NaN) = 0, {L1, L2, r, gate} at [7B..]).
+ * bwd writes, with {gL, g1, g2, gr} = gout[0..3] (device; NULL for {1, 0, 0, 0}) the upstream gradients of the four scalars,
+ * N = B*HW, wL = gL (1 + 10 r gate), cr = gL 10 gate (L1 + L2) + gr:
+ *   d1 = [o1 > 0] ((wL + g1) 2 (R1 - l1) / N - cr s_b P2_b / (B (P1_b + P2_b)^2)),
+ *   d2 = [o2 > 0] ((wL + g2) 2 (R2 - l2) / N + cr s_b P1_b / (B (P1_b + P2_b)^2)). */
+size_t umi_mt_ratio_ws_bytes(int B, long HW);
+size_t umi_mt_ratio_stats_len(int B);
+int umi_mt_ratio_fwd(const float* o1, const float* o2, const float* l1, const float* l2, int B, long HW, int gate,
+                     const float* gate_dev, double* stats, float* loss, float* loss1, float* loss2, float* ratio, void* ws, size_t ws_bytes,
+                     umi_stream_t stream);
+int umi_mt_ratio_bwd(const float* o1, const float* o2, const float* l1, const float* l2, const double* stats,
+                     const float* gout, int B, long HW, float* d1, float* d2, umi_stream_t stream);
+
 /* Multi-tensor optimizer step: torch.optim.SGD / torch.optim.Adam arithmetic (reference train.py:341-347) on every parameter
  * tensor of a model in ONE launch.  `descs` is a DEVICE array of n_desc umi_optim_desc sorted by blk0; a tensor of n elements
  * occupies ceil(n / umi_optim_block_elems()) consecutive blocks starting at blk0; total_blocks = the sum.

@@ -19,18 +19,28 @@ kernel argument would freeze it; `param_groups[i]['lr']` is refreshed from the d
 `multi_task_train` (Trainer.py:831-992; model types 'multi_task*' with a plain loss name): two-headed models
 (`Model.UNet_multitask`, `VisionTransformerMultitask`), batches `(inputs, (label1, label2))`, both outputs through
 `F.relu` (:883-884), loss = loss1 + loss2 (:885-890), model selection on the validation LOSS (:926).
-The remaining epoch loops of the reference (uncertainty / ratio weighted multi-task, CLTR, Topo losses) are out of scope
-and raise.
+`multi_task_trainRatio` (Trainer.py:1174-1366; loss_function 'multi_task_loss_ratio' on the 'multi_task*' model types): the
+same two-headed step with `loss.multi_task_ratio_loss` (per-task MSE of the ReLU'd heads, error r of the per-image count
+ratio, loss = (L1 + L2) * (1 + 10 r) from epoch 6 on), and the reference's bookkeeping: alpha = part1 / part2 per epoch, the
+per-task epoch losses divided by the step count twice, no validation record, checkpoint or early stop before epoch 6, then
+`lr_scheduler.step(0.0)` when a scheduler is given.  The sums are kept on the device and read back once per phase.  In graph
+mode the epoch gate is a device flag the loss kernel reads (rewritten in place at the start of each epoch, so the graphs of
+the full and the ragged batch serve both gate values), and an LR change made by a scheduler object is written into the device
+LR block in place (umi.optim push_lr), so the captured step sees it.
+`lr_scheduler=True` (what the reference's train.py passes) crashes the reference in its first validation after epoch 5
+(`True.step`); here train() raises NotImplementedError before the first step whenever the run would reach that point.
+The remaining epoch loops of the reference (uncertainty-weighted multi-task, CLTR, Topo losses) are out of scope and raise.
 """
 import copy
 import os
 import time
 
+import numpy as np
 import torch
 import torch.nn.functional as F
 from tqdm import tqdm
 
-from loss import calc_loss
+from loss import calc_loss, multi_task_ratio_loss
 
 _SINGLE = ('single', 'TransUnet', 'regression', 'regression_t', 'attention')
 _TOPO = ('TopoCount', 'TopoCount2', 'TopoLoss', 'TopoLoss2', 'MyTopoLoss1', 'MyTopoLoss2', 'MyTopoLossGraph',
@@ -70,6 +80,9 @@ class Trainer():
         self.grad_sync = None         # optional callable run between backward and optimizer.step (DDP)
         self.graph = (os.environ.get("UMI_TRAINER_GRAPH") == "1") if graph is None else bool(graph)
         self._graphs, self._seen_shapes, self._dev_sched, self._side = {}, set(), False, None
+        # multi_task_trainRatio: epoch > 5 (host, and in graph mode a device flag), ratioAccuracy of the last step
+        self._ratio_gate, self._gate_dev, self._ratio = False, None, None
+        self.alpha, self.alpha_list = None, []
 
         self.save_dir_model = os.path.join(self.output_save_dir, 'models/')
         os.makedirs(self.save_dir_model, exist_ok=True)
@@ -81,9 +94,10 @@ class Trainer():
                 raise NotImplementedError("Topo-loss warm-up loop (reference singe_train_wup) is out of scope")
             return self.singe_train()
         if self.model_type in _MULTI:
-            if self.loss_function in ('multi_task_loss', 'multi_task_loss_ratio'):
-                raise NotImplementedError("uncertainty- / ratio-weighted multi-task loops (reference multi_task_uc_train, "
-                                          "multi_task_trainRatio) are out of scope")
+            if self.loss_function == 'multi_task_loss':
+                raise NotImplementedError("uncertainty-weighted multi-task loop (reference multi_task_uc_train) is out of scope")
+            if self.loss_function == 'multi_task_loss_ratio':
+                return self.multi_task_trainRatio()
             return self.multi_task_train()
         if self.model_type in _OTHER:
             raise NotImplementedError(f'model_type "{self.model_type}" (CLTR loop) is out of scope')
@@ -95,7 +109,16 @@ class Trainer():
             return inputs.to(self.device).type(self.dtype), tuple(l.to(self.device).type(self.dtype) for l in labels)
         return inputs.to(self.device).type(self.dtype), labels.to(self.device).type(self.dtype)
 
+    def _ratio_loop(self):
+        return self.model_type in _MULTI and self.loss_function == 'multi_task_loss_ratio'
+
     def _forward_loss(self, inputs, labels):
+        if self._ratio_loop():                                   # reference Trainer.py:1226-1249
+            o1, o2 = self.model(inputs)
+            gate = self._ratio_gate if self._gate_dev is None else self._gate_dev
+            loss, loss1, loss2, self._ratio = multi_task_ratio_loss(o1, o2, labels[0], labels[1], gate)
+            self._task_losses = [loss1, loss2]
+            return (o1, o2), loss
         if self.model_type in _MULTI:                            # reference Trainer.py:882-890
             outs = tuple(F.relu(o) for o in self.model(inputs))
             self._task_losses = [calc_loss(o, l, loss_type=self.loss_function) for o, l in zip(outs, labels)]
@@ -139,11 +162,15 @@ class Trainer():
             self._dev_sched, self._side = True, torch.cuda.Stream()
         flat = [inputs] + (list(labels) if isinstance(labels, (list, tuple)) else [labels])
         multi = isinstance(labels, (list, tuple))
+        ratio = self._ratio_loop()
         key = tuple(tuple(t.shape) for t in flat)
+        if ratio and self._gate_dev is None:       # the gate as a device flag: a captured kernel argument would freeze it
+            self._gate_dev = torch.full((), float(self._ratio_gate), dtype=torch.float32, device=inputs.device)
 
         def body(x, *ys):
             loss = self._step_body(x, tuple(ys) if multi else ys[0])
-            return (loss.detach(),) + tuple(l.detach() for l in (self._task_losses if multi else ()))
+            extra = (self._task_losses if multi else []) + ([self._ratio] if ratio else [])
+            return (loss.detach(),) + tuple(t.detach() for t in extra)
 
         gs = self._graphs.get(key)
         if gs is None and key in self._seen_shapes:
@@ -159,7 +186,9 @@ class Trainer():
                 outs = body(*flat)
             torch.cuda.current_stream().wait_stream(self._side)
         if multi:
-            self._task_losses = [o.clone() for o in outs[1:]]
+            self._task_losses = [o.clone() for o in outs[1:3]]
+        if ratio:
+            self._ratio = outs[3].clone()
         self.iter_num += 1
         return outs[0].clone()            # the static output buffer is overwritten by the next replay
 
@@ -173,6 +202,114 @@ class Trainer():
         return loss.detach(), score.detach()
 
     # ------------------------------------------------------------------------------------
+    def _check_ratio_scheduler(self):
+        """The reference calls `self.lr_scheduler.step(val_score)` in the first validation after epoch 5 (Trainer.py:1282-1284);
+        a truthy lr_scheduler without .step (train.py passes True) dies there with AttributeError."""
+        if self.lr_scheduler and not callable(getattr(self.lr_scheduler, "step", None)) \
+                and max(self.start_epoch, 6) <= self.num_epochs:
+            raise NotImplementedError(
+                f"multi_task_loss_ratio with lr_scheduler={self.lr_scheduler!r}: the reference loop calls lr_scheduler.step() "
+                "in the first validation after epoch 5 and crashes there (AttributeError); pass a scheduler object, or None "
+                "/ False, or stop at epoch 5")
+
+    def _scheduler_step(self):
+        """lr_scheduler.step(0.0) (the reference's val_score, Trainer.py:1284).  With the LR on the device (graph mode) the
+        host copy is refreshed first and the scheduler's result is written back into the device block in place."""
+        if self._dev_sched:
+            self.optimizer.sync_host()
+        self.lr_scheduler.step(0.0)
+        if self._dev_sched:
+            self.optimizer.push_lr()
+
+    def multi_task_trainRatio(self):
+        """Reference Trainer.multi_task_trainRatio (Trainer.py:1174-1366), see the module docstring."""
+        self._check_ratio_scheduler()
+        os.makedirs(self.output_save_dir, exist_ok=True)
+        log = open(os.path.join(self.output_save_dir, "logs.txt"), 'a')
+
+        def say(msg, echo=True):
+            if echo:
+                print(msg)
+            log.write(msg + "\n")
+
+        total_time = 0.0
+        for epoch in range(self.start_epoch, self.num_epochs + 1):
+            log.write('Epoch {}/{}\n'.format(epoch, self.num_epochs) + '-' * 10 + "\n")
+            since = time.time()
+            self._ratio_gate = epoch > 5
+            if self._gate_dev is not None:
+                self._gate_dev.fill_(float(self._ratio_gate))
+            for phase in self.phases:
+                train = phase == 'train'
+                if train:
+                    if self._dev_sched:
+                        self.optimizer.sync_host()
+                    for group in self.optimizer.param_groups:
+                        print("LR", group['lr'])
+                        log.write(f"LR {group['lr']}\n")
+                    since = time.time()
+                self.model.train(train)
+
+                # device sums: loss, loss1, loss2 (fp64, as the reference's float += .item()), part1 = sum of loss1 + loss2
+                # (fp64) and part2 = sum of fp32(loss1 + loss2) * ratioAccuracy (fp32, a tensor in the reference too)
+                sums, steps = None, 0
+                with tqdm(self.dataloader[phase], unit="batch") as bar:
+                    for inputs, labels in bar:
+                        bar.set_description(f"Epoch {epoch}")
+                        steps += 1
+                        loss = self.train_step(inputs, labels) if train else self.eval_step(inputs, labels)[0]
+                        l1, l2 = (t.detach().double() for t in self._task_losses)
+                        s12 = l1 + l2
+                        acc = [loss.double(), l1, l2, s12, s12.float() * self._ratio.detach()]
+                        sums = acc if sums is None else [a + b for a, b in zip(sums, acc)]
+                loss_sum, sum1, sum2, part1, part2 = torch.stack([v.double() for v in sums]).tolist()
+                epoch_loss = loss_sum / steps
+                loss1_epoch = sum1 / steps / steps                  # divided by batch_step twice (Trainer.py:1275-1278)
+                loss2_epoch = sum2 / steps / steps
+
+                if not train:
+                    if epoch <= 5:                                  # Trainer.py:1280-1281: nothing recorded yet
+                        continue
+                    if self.lr_scheduler:
+                        self._scheduler_step()
+                    self.val_loss_list.append(epoch_loss)
+                    self.val_loss_list_1.append(loss1_epoch)
+                    self.val_loss_list_2.append(loss2_epoch)
+                    say("Val loss on epoch %i: %f" % (epoch, epoch_loss))
+                    say("Val score on epoch %i: %f" % (epoch, 0.0))
+                    if epoch_loss < self.best_val_score:
+                        self.early_stop_counter = 0
+                        self.best_val_score = epoch_loss
+                        self.best_loss = epoch_loss
+                        say("saving best model")
+                        self.best_model = copy.deepcopy(self.model.state_dict())
+                        torch.save(self.best_model, os.path.join(self.save_dir_model, 'epoch{}.pt'.format(epoch)))
+                        torch.save(self.best_model, os.path.join(self.save_dir_model, 'best.pt'))
+                    else:
+                        self.early_stop_counter += 1
+                    if self.early_stop_counter > self.patience:
+                        say("Early stopping")
+                        return self._finish(log, say)
+                    continue
+
+                elapsed = time.time() - since
+                self.train_loss_list.append(epoch_loss)
+                self.train_loss_list_1.append(loss1_epoch)
+                self.train_loss_list_2.append(loss2_epoch)
+                # alpha = (part1 / n) / (part2 / n) with the reference's roundings: part2 and the quotient are fp32 tensors
+                with np.errstate(divide='ignore', invalid='ignore'):
+                    self.alpha = float(np.float32(part1 / steps) / (np.float32(part2) / np.float32(steps)))
+                self.alpha_list.append(self.alpha)
+                say("Alpha on epoch %i: %f" % (epoch, self.alpha))
+                say("Train loss on epoch %i: %f" % (epoch, epoch_loss))
+                total_time += elapsed
+                self.meanTimePerEpoch = total_time / epoch
+                torch.save(self.model.state_dict(), os.path.join(self.save_dir_model, 'last_epoch.pt'))
+
+            elapsed = time.time() - since
+            say('{:.0f}m {:.0f}s\n'.format(elapsed // 60, elapsed % 60))
+        return self._finish(log, say)
+
     def multi_task_train(self):
         return self.singe_train()                                # same epoch loop; the differences are flagged `multi` below
 

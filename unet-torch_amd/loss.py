@@ -19,6 +19,13 @@ k-th key for TopK and BCE_HEM (ties go to the lowest flat index), so no value tr
 them can be captured in a graph.  Every other input (CPU tensors, other dtypes or shapes) runs a torch composite that
 restates the reference branch and raises where it raises.
 
+`multi_task_ratio_loss(o1, o2, l1, l2, ratio_weighted)` is the step loss of the reference's count-ratio-weighted multi-task
+loop (Trainer.py:1225-1249, used by Trainer.multi_task_trainRatio): per-task MSE of the ReLU'd heads, the mean absolute
+error r of the per-image immune : (immune + other) count ratio, and (L1 + L2) * (1 + 10 r) when `ratio_weighted` (epoch > 5).
+Contiguous fp32 device heads (B, 1, H, W) with labels (B, H, W) run two HIP kernels forward and one backward
+(csrc/multitask_ratio.hip, fp64 fixed-order sums, nothing read back, so the step can be captured); every other input runs a
+torch composite that restates the reference lines.
+
 The remaining names raise NotImplementedError: 'dice', 'dice_score', 'dice_score_mc' and 'log_cosh_dice_loss' call
 DiceLoss() without n_classes, 'FL' names an undefined BinaryFocalLoss, HausdorffERLoss has no gradient and
 ActiveContourLoss hard-codes 512x512 tensors on cuda:0 in the reference itself.
@@ -452,3 +459,86 @@ def calc_loss(pred, target, bce_weight=0.5, loss_type='mse'):
     if loss_type in _OUT_OF_SCOPE:
         raise NotImplementedError(f"loss_type {loss_type!r} is outside the MI355X hot-path scope")
     raise ValueError(f"unknown loss_type {loss_type!r}")
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# count-ratio-weighted multi-task loss (reference Trainer.py:1225-1249)
+
+def multi_task_ratio_composite(output1, output2, label1, label2, ratio_weighted):
+    """The reference lines, restated: returns (loss, loss1, loss2, ratioAccuracy)."""
+    output1 = F.relu(output1)
+    output2 = F.relu(output2)
+    loss1 = calc_loss(output1, label1, loss_type='mse')
+    loss2 = calc_loss(output2, label2, loss_type='mse')
+    cellCountGt_immune = torch.sum(label1, axis=(1, 2))
+    cellCountPred_immune = torch.sum(output1.squeeze(1), axis=(1, 2))
+    cellCountGt_other = torch.sum(label2, axis=(1, 2))
+    cellCountPred_other = torch.sum(output2.squeeze(1), axis=(1, 2))
+    ratioGT = cellCountGt_immune / (cellCountGt_other + cellCountGt_immune)
+    ratioPred = cellCountPred_immune / (cellCountPred_other + cellCountPred_immune)
+    ratioAccuracy = torch.mean(abs(ratioGT - ratioPred))
+    if ratio_weighted:
+        loss = (loss1 + loss2) * (1 + (10 * ratioAccuracy))
+    else:
+        loss = loss1 + loss2
+    return loss, loss1, loss2, ratioAccuracy
+
+
+class _MultiTaskRatio(torch.autograd.Function):
+    """multi_task_ratio_loss on (B, 1, H, W) fp32 device heads: umi_mt_ratio_fwd / _bwd; the fp64 stats are saved.  The gate
+    (a bool, or a device tensor the kernel reads, so that a captured graph follows it) is kept in the stats for the backward."""
+
+    @staticmethod
+    def forward(ctx, o1, o2, l1, l2, gate):
+        from umi import lib as L, ops
+        B, HW = o1.shape[0], o1[0, 0].numel()
+        dev = o1.device
+        stats = torch.empty(L.fn("umi_mt_ratio_stats_len")(B), dtype=torch.float64, device=dev)
+        outs = [torch.empty((), dtype=torch.float32, device=dev) for _ in range(4)]
+        ws = ops.workspace(L.fn("umi_mt_ratio_ws_bytes")(B, HW), dev)
+        flag = torch.is_tensor(gate)
+        L.check(L.fn("umi_mt_ratio_fwd")(o1.data_ptr(), o2.data_ptr(), l1.data_ptr(), l2.data_ptr(), B, HW,
+                                         0 if flag else int(bool(gate)), gate.data_ptr() if flag else None, stats.data_ptr(), *[t.data_ptr() for t in outs], ws.data_ptr(), ws.numel(),
+                                         ops._stream()), "umi_mt_ratio_fwd")
+        ctx.save_for_backward(o1, o2, l1, l2, stats)
+        return tuple(outs)
+
+    @staticmethod
+    def backward(ctx, gL, g1, g2, gr):
+        from umi import lib as L, ops
+        o1, o2, l1, l2, stats = ctx.saved_tensors
+        zero = torch.zeros((), dtype=torch.float32, device=o1.device)
+        g = torch.stack([zero if v is None else v.detach().to(torch.float32) for v in (gL, g1, g2, gr)])
+        d1, d2 = torch.empty_like(o1), torch.empty_like(o2)
+        L.check(L.fn("umi_mt_ratio_bwd")(o1.data_ptr(), o2.data_ptr(), l1.data_ptr(), l2.data_ptr(), stats.data_ptr(),
+                                         g.data_ptr(), o1.shape[0], o1[0, 0].numel(), d1.data_ptr(), d2.data_ptr(),
+                                         ops._stream()), "umi_mt_ratio_bwd")
+        return d1, d2, None, None, None
+
+
+def _mt_ratio_device_ok(o1, o2, l1, l2):
+    if not all(t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() for t in (o1, o2, l1, l2)):
+        return False
+    if l1.requires_grad or l2.requires_grad:            # the kernels give the labels no gradient
+        return False
+    if o1.dim() != 4 or o1.shape[1] != 1 or tuple(o2.shape) != tuple(o1.shape):
+        return False
+    B, _, H, W = o1.shape
+    return (tuple(l1.shape) == (B, H, W) and tuple(l2.shape) == (B, H, W) and 0 < o1.numel() < (1 << 31)
+            and B <= 65535 and len({o1.device, o2.device, l1.device, l2.device}) == 1)
+
+
+def multi_task_ratio_loss(o1, o2, l1, l2, ratio_weighted):
+    """Step loss of the reference's multi_task_trainRatio (Trainer.py:1225-1249) on the RAW head outputs o1, o2 (the ReLU is
+    part of it) and the label maps l1, l2: returns (loss, loss1, loss2, ratioAccuracy), all differentiable.  ratio_weighted:
+    the reference's `epoch > 5` gate, loss = (loss1 + loss2) * (1 + 10 * ratioAccuracy); else loss = loss1 + loss2.  It may
+    be a one-element fp32 device tensor (nonzero = on), which the device kernels read at run time (graph replay); with the
+    composite it is read on the host."""
+    if torch.is_tensor(ratio_weighted):
+        if _mt_ratio_device_ok(o1, o2, l1, l2) and ratio_weighted.is_cuda and ratio_weighted.dtype == torch.float32 \
+                and ratio_weighted.numel() == 1 and ratio_weighted.device == o1.device:
+            return _MultiTaskRatio.apply(o1, o2, l1, l2, ratio_weighted.detach())
+        ratio_weighted = bool(ratio_weighted)
+    if _mt_ratio_device_ok(o1, o2, l1, l2):
+        return _MultiTaskRatio.apply(o1, o2, l1, l2, bool(ratio_weighted))
+    return multi_task_ratio_composite(o1, o2, l1, l2, ratio_weighted)

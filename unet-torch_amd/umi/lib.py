@@ -150,6 +150,12 @@ SIGNATURES = {
     "umi_topk_loss_fwd": (c_int, [c_void_p, c_void_p, c_long, c_long, c_int, c_void_p, c_void_p, c_void_p, c_size_t,
                                   c_void_p]),
     "umi_topk_loss_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_long, c_long, c_void_p, c_void_p]),
+    "umi_mt_ratio_ws_bytes": (c_size_t, [c_int, c_long]),
+    "umi_mt_ratio_stats_len": (c_size_t, [c_int]),
+    "umi_mt_ratio_fwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_long, c_int, c_void_p, c_void_p, c_void_p,
+                                 c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "umi_mt_ratio_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_long, c_void_p,
+                                 c_void_p, c_void_p]),
     "umi_optim_block_elems": (c_int, []),
     "umi_table_upload": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p]),
     "umi_optim_sgd_multi": (c_int, [c_void_p, c_int, c_int, c_double, c_double, c_double, c_double, c_int, c_int, c_void_p]),

@@ -155,6 +155,17 @@ class _DeviceHyper:
             out.append(h)
         return out
 
+    def push_lr(self):
+        """param_groups[i]['lr'] -> the device block's learning rate, written in place (a captured graph holds the block's
+        address), so an LR set on the host between steps -- e.g. by a torch lr_scheduler after sync_host() -- is what the next
+        eager or replayed step uses."""
+        if self.device_hyper is None:
+            return
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("umi.optim: push_lr() cannot run inside a HIP-graph capture")
+        for group, (dev, _) in zip(self.param_groups, self._umi_hyper):
+            dev[:8].copy_(torch.tensor([float(group["lr"])], dtype=torch.float64).view(torch.uint8))   # Hyper.lr, offset 0
+
     def state_dict(self):
         self.sync_host()
         return super().state_dict()
