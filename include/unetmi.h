@@ -517,6 +517,39 @@ size_t umi_zoom_cubic_ws_bytes(int H, int W, int C);
 int umi_zoom_cubic_hwc(const void* img, int src_dtype, void* out, int H, int W, int C, int out_h, int out_w, void* ws,
                        size_t ws_bytes, umi_stream_t stream);
 
+/* Binary-model (one-logit) post-processing, the reference's test.py:393-404 and loss.py:422-440 (MRAccuracy).
+ * umi_binary_mask: mask[i] = 1 where fp32 sigmoid(logits[i]) >= 0.5 as torch evaluates it, i.e. logits[i] >= -0x1.7ffffcp-23
+ *   (bit pattern 0xB43FFFFE; 1 / (1 + exp(-x)) rounds to exactly 0.5 from there on), else 0; NaN gives 0.  n elements; logits
+ *   4-byte aligned (16-byte accesses when it is 16-byte aligned), mask 16-byte aligned.
+ * umi_zoom_nearest: scipy.ndimage.zoom(img, (out_h / H, out_w / W), order=0) of N [H][W] images, dtype 0 = uint8, 1 = float32, same
+ *   type out: sample coordinate i * ((in - 1) / (out - 1)) in float64, source index floor(x + 0.5), 0 where the coordinate exceeds
+ *   in - 1 on either axis (mode 'constant', as umi_zoom_cubic_hwc).
+ * umi_sum_trunc: out[n] = (int)(float64 sum of the HW floats of image n), fixed summation order, truncated toward zero, clamped to
+ *   int32, NaN -> 0: int(np.sum(dot_map)), exact for 0/1 maps.  ws: umi_sum_trunc_ws_bytes(N) bytes of partial sums. */
+int umi_binary_mask(const float* logits, unsigned char* mask, long n, umi_stream_t stream);
+int umi_zoom_nearest(const void* in, int dtype, void* out, int N, int H, int W, int out_h, int out_w, umi_stream_t stream);
+size_t umi_sum_trunc_ws_bytes(int N);
+int umi_sum_trunc(const float* x, int* out, int N, long HW, void* ws, size_t ws_bytes, umi_stream_t stream);
+
+/* 8-connected component labelling of N uint8 [H][W] masks (foreground = non-zero), cv2.connectedComponents(connectivity=8) /
+ * scipy.ndimage.label(structure=ones((3,3))): labels 1..counts[n] in the raster order of each component's first pixel, 0 =
+ * background.  A union-find by minimum flat index in separate launches (csrc/components.hip); integer atomics and fixed-order
+ * scans only, so two runs give identical bits.
+ *   umi_components_cap(H, W) = ceil(H/2) * ceil(W/2): a 2x2 block is mutually 8-adjacent, so it meets at most one component;
+ *     the row length of area / sum_y / sum_x.  Entries beyond counts[n] are 0.
+ *   umi_count_components: counts only.   umi_label_components: labels[N][H][W], counts[N], area[N][cap] (pixels),
+ *     sum_y / sum_x[N][cap] (integer coordinate sums; centroid = sum / area).
+ *   ws: umi_components_ws_bytes(N, H, W) bytes (0 for unsupported sizes), re-initialised by every call.  Its first int32 is a
+ *     fault word: 0, or a non-zero code when a find / union loop hit its iteration cap or met a corrupted chain (the results
+ *     are then invalid; the loops are bounded by the pixel count, so the kernels always terminate).
+ *   N * H * W < 2^31 and N <= 65535, else UMI_ERR_UNSUPPORTED. */
+size_t umi_components_ws_bytes(int N, int H, int W);
+int umi_components_cap(int H, int W);
+int umi_count_components(const unsigned char* mask, int* counts, int N, int H, int W, void* ws, size_t ws_bytes,
+                         umi_stream_t stream);
+int umi_label_components(const unsigned char* mask, int* labels, int* counts, int* area, long long* sum_y, long long* sum_x,
+                         int N, int H, int W, void* ws, size_t ws_bytes, umi_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

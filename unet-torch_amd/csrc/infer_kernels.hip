@@ -261,3 +261,137 @@ extern "C" int umi_zoom_cubic_hwc(const void* img, int src_dtype, void* out, int
     UMI_LAUNCH_CHECK();
     return UMI_OK;
 }
+
+// ---- binary-model post-processing (reference test.py:393-404 sigmoid -> >= 0.5 -> 0/1 mask -> scipy.ndimage.zoom(order=0);
+// loss.py:425-431 the same threshold and the dot count of MRAccuracy)
+//   umi_binary_mask    fp32 logits -> uint8, 1 where fp32 sigmoid(x) >= 0.5.  torch's 1 / (1 + exp(-x)) rounds to exactly 0.5 for
+//                      every x >= -0x1.7ffffcp-23 (bits 0xB43FFFFE), found by bisection over bit patterns against torch.sigmoid
+//                      (tests/test_binary_infer.py repeats it), so the kernel compares with that constant and evaluates no exp.
+//                      NaN compares false: 0.
+//   umi_zoom_nearest   SciPy's order-0 zoom of N uint8 / float32 images: sample coordinate x = i * ((in - 1) / (out - 1)) in
+//                      float64 (0 for out == 1), source index floor(x + 0.5), and 0 where x exceeds in - 1 on either axis
+//                      (mode 'constant', step 3 of the cubic resize above).
+//   umi_sum_trunc      out[n] = (int) sum of image n in float64, fixed order (64 slice sums per image, then those in index order),
+//                      truncated toward zero and clamped to int32 (int(np.sum(dot_map)); exact for 0/1 maps).
+namespace {
+
+constexpr unsigned BM_CUTOFF_BITS = 0xB43FFFFEu;          // -0x1.7ffffcp-23 = -1.7881390590446244e-07
+
+__device__ inline unsigned bm_bit(float x, float cut) { return x >= cut ? 1u : 0u; }
+
+// one thread = 16 consecutive logits -> one 16-byte store; `in_al` says the logits are 16-byte aligned as well (a view that
+// starts inside its storage is not: scalar loads then)
+__global__ __launch_bounds__(256) void binary_mask_kernel(const float* __restrict__ x, unsigned char* __restrict__ m, long n, int in_al) {
+    const float cut = __builtin_bit_cast(float, BM_CUTOFF_BITS);
+    const long i0 = ((long)blockIdx.x * 256 + threadIdx.x) * 16;
+    if (i0 >= n) return;
+    if (i0 + 16 <= n) {
+        unsigned w[4];
+        for (int j = 0; j < 4; ++j) {
+            float4 v;
+            if (in_al) v = *reinterpret_cast<const float4*>(x + i0 + 4 * j);
+            else v = make_float4(x[i0 + 4 * j], x[i0 + 4 * j + 1], x[i0 + 4 * j + 2], x[i0 + 4 * j + 3]);
+            w[j] = bm_bit(v.x, cut) | bm_bit(v.y, cut) << 8 | bm_bit(v.z, cut) << 16 | bm_bit(v.w, cut) << 24;
+        }
+        *reinterpret_cast<uint4*>(m + i0) = make_uint4(w[0], w[1], w[2], w[3]);
+    } else {
+        for (long i = i0; i < n; ++i) m[i] = (unsigned char)bm_bit(x[i], cut);
+    }
+}
+
+// source index of output i, or -1 where SciPy's mode 'constant' gives 0
+__device__ inline int zn_src(int i, int n_in, int n_out) {
+    const double x = (double)i * (n_out > 1 ? (double)(n_in - 1) / (double)(n_out - 1) : 0.0);
+    if (x < 0.0 || x > (double)(n_in - 1)) return -1;
+    const int s = (int)floor(x + 0.5);
+    return s > n_in - 1 ? n_in - 1 : s;
+}
+
+// one thread = 16 bytes of one output row (blockIdx.y = row, blockIdx.z = image); `al`: every row of `out` starts 16-byte aligned
+template <typename T>
+__global__ __launch_bounds__(256) void zoom_nearest_kernel(const T* __restrict__ in, T* __restrict__ out, int H, int W, int oh, int ow,
+                                                           int al) {
+    constexpr int V = 16 / sizeof(T);
+    const int j0 = (blockIdx.x * 256 + threadIdx.x) * V;
+    if (j0 >= ow) return;
+    const int oy = blockIdx.y;
+    const int sy = zn_src(oy, H, oh);
+    const T* src = in + ((long)blockIdx.z * H + (sy < 0 ? 0 : sy)) * W;
+    T* dst = out + ((long)blockIdx.z * oh + oy) * ow;
+    alignas(16) T v[V];
+    for (int k = 0; k < V; ++k) {
+        const int sx = j0 + k < ow ? zn_src(j0 + k, W, ow) : -1;
+        v[k] = (sy < 0 || sx < 0) ? (T)0 : src[sx];
+    }
+    if (al && j0 + V <= ow) *reinterpret_cast<uint4*>(dst + j0) = *reinterpret_cast<const uint4*>(v);
+    else
+        for (int k = 0; k < V && j0 + k < ow; ++k) dst[j0 + k] = v[k];
+}
+
+constexpr int ST_BLOCKS = 64;                             // partial sums per image
+
+// blockIdx.x = slice of image blockIdx.y: part[n][b] = float64 sum of the slice, threads striding it, fixed-order tree
+__global__ __launch_bounds__(256) void sum_trunc_partial_kernel(const float* __restrict__ x, double* __restrict__ part, long HW) {
+    __shared__ double sh[256];
+    const float* p = x + (long)blockIdx.y * HW;
+    const long per = (HW + ST_BLOCKS - 1) / ST_BLOCKS, lo = (long)blockIdx.x * per, hi = lo + per < HW ? lo + per : HW;
+    double acc = 0.0;
+    for (long i = lo + threadIdx.x; i < hi; i += 256) acc += (double)p[i];
+    sh[threadIdx.x] = acc;
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+        if ((int)threadIdx.x < o) sh[threadIdx.x] += sh[threadIdx.x + o];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) part[(long)blockIdx.y * ST_BLOCKS + blockIdx.x] = sh[0];
+}
+
+// one thread per image: the partials in index order, then the truncation
+__global__ __launch_bounds__(64) void sum_trunc_finish_kernel(const double* __restrict__ part, int* __restrict__ out, int N) {
+    const int n = blockIdx.x * 64 + threadIdx.x;
+    if (n >= N) return;
+    double s = 0.0;
+    for (int b = 0; b < ST_BLOCKS; ++b) s += part[(long)n * ST_BLOCKS + b];
+    out[n] = s != s ? 0 : (s >= 2147483647.0 ? 2147483647 : (s <= -2147483648.0 ? -2147483647 - 1 : (int)s));
+}
+}  // namespace
+
+extern "C" int umi_binary_mask(const float* logits, unsigned char* mask, long n, umi_stream_t stream) {
+    if (!logits || !mask || n <= 0) return UMI_ERR_BADARG;
+    if (((unsigned long)logits & 3) || ((unsigned long)mask & 15)) return UMI_ERR_BADARG;
+    if ((n + 4095) / 4096 >= (1L << 31)) return UMI_ERR_UNSUPPORTED;
+    hipLaunchKernelGGL(binary_mask_kernel, dim3((unsigned)((n + 4095) / 4096)), dim3(256), 0, (hipStream_t)stream, logits, mask, n,
+                       ((unsigned long)logits & 15) == 0 ? 1 : 0);
+    UMI_LAUNCH_CHECK();
+    return UMI_OK;
+}
+
+extern "C" int umi_zoom_nearest(const void* in, int dtype, void* out, int N, int H, int W, int out_h, int out_w, umi_stream_t stream) {
+    if (!in || !out || N <= 0 || H <= 0 || W <= 0 || out_h <= 0 || out_w <= 0) return UMI_ERR_BADARG;
+    if (dtype != 0 && dtype != 1) return UMI_ERR_BADARG;
+    if (N > 65535 || out_h > 65535 || (long)N * H * W >= (1L << 31) || (long)N * out_h * out_w >= (1L << 31)) return UMI_ERR_UNSUPPORTED;
+    hipStream_t s = (hipStream_t)stream;
+    const int esz = dtype == 0 ? 1 : 4, V = 16 / esz;
+    const int al = (((unsigned long)out & 15) == 0 && ((long)out_w * esz) % 16 == 0) ? 1 : 0;
+    const dim3 grid((unsigned)((out_w + 256 * V - 1) / (256 * V)), out_h, N);
+    if (dtype == 0)
+        hipLaunchKernelGGL((zoom_nearest_kernel<unsigned char>), grid, dim3(256), 0, s, (const unsigned char*)in, (unsigned char*)out, H, W,
+                           out_h, out_w, al);
+    else
+        hipLaunchKernelGGL((zoom_nearest_kernel<float>), grid, dim3(256), 0, s, (const float*)in, (float*)out, H, W, out_h, out_w, al);
+    UMI_LAUNCH_CHECK();
+    return UMI_OK;
+}
+
+extern "C" size_t umi_sum_trunc_ws_bytes(int N) { return N > 0 ? (size_t)N * ST_BLOCKS * sizeof(double) : 0; }
+
+extern "C" int umi_sum_trunc(const float* x, int* out, int N, long HW, void* ws, size_t ws_bytes, umi_stream_t stream) {
+    if (!x || !out || N <= 0 || HW <= 0) return UMI_ERR_BADARG;
+    if (N > 65535) return UMI_ERR_UNSUPPORTED;
+    if (!ws || ws_bytes < umi_sum_trunc_ws_bytes(N)) return UMI_ERR_WORKSPACE;
+    hipStream_t s = (hipStream_t)stream;
+    hipLaunchKernelGGL(sum_trunc_partial_kernel, dim3(ST_BLOCKS, N), dim3(256), 0, s, x, (double*)ws, HW);
+    hipLaunchKernelGGL(sum_trunc_finish_kernel, dim3((N + 63) / 64), dim3(64), 0, s, (const double*)ws, out, N);
+    UMI_LAUNCH_CHECK();
+    return UMI_OK;
+}

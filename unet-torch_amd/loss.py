@@ -26,6 +26,13 @@ Contiguous fp32 device heads (B, 1, H, W) with labels (B, H, W) run two HIP kern
 (csrc/multitask_ratio.hip, fp64 fixed-order sums, nothing read back, so the step can be captured); every other input runs a
 torch composite that restates the reference lines.
 
+`MRAccuracy(pred, target)` is the reference's cell-count error of a batch (loss.py:422-440): threshold the one-logit map at
+fp32 sigmoid >= 0.5, count the 8-connected components of every image and compare with the number of ground-truth dots.  Device
+tensors run the threshold, the labelling (csrc/components.hip, a union-find in separate launches) and the dot sums as HIP kernels
+and read 2 B integers (and the labelling's fault word) back once; CPU tensors run a NumPy restatement (umi/components.py).  The
+component count is cv2.connectedComponents' / scipy.ndimage.label's with a full 3x3 structure; the same Python expression on the
+same integers gives the reference's float.
+
 The remaining names raise NotImplementedError: 'dice', 'dice_score', 'dice_score_mc' and 'log_cosh_dice_loss' call
 DiceLoss() without n_classes, 'FL' names an undefined BinaryFocalLoss, HausdorffERLoss has no gradient and
 ActiveContourLoss hard-codes 512x512 tensors on cuda:0 in the reference itself.
@@ -425,6 +432,57 @@ def bce_hem_loss(pred, target):
     if _binary_target_ok(pred, target, exact_shape=True) and pred.numel() >= BCE_HEM_K:
         return _TopKBCE.apply(pred, target, BCE_HEM_K, _BCE_HEM)
     return bce_hem_composite(pred, target)
+
+
+def MRAccuracy(pred, target):
+    """Mean relative cell-count error of a batch (reference loss.py:422-440), a Python float: per image the number n of
+    8-connected components of `sigmoid(pred.squeeze(1)) >= 0.5` against count_gt = int(sum(target[b])):
+    |count_gt - n| / count_gt, or 1 where count_gt == 0 and n != 0, averaged over target.shape[0].
+    pred (B, 1, H, W) logits, target (B, H, W) dot maps.  Device logits: HIP kernels, one read-back of 2 B + 1 integers
+    (count_gt is the fixed-order float64 sum of the fp32 map truncated toward zero: exact for 0/1 dot maps).  CPU logits: NumPy."""
+    batch_size = target.shape[0]
+    pred = pred.detach().squeeze(1)
+    if pred.dim() != 3:
+        raise ValueError(f"MRAccuracy: pred.squeeze(1) must be (B, H, W) (connectedComponents takes one 2-D image), got "
+                         f"{tuple(pred.shape)}")
+    if pred.shape[0] < batch_size:
+        raise IndexError(f"MRAccuracy: target has {batch_size} images, pred {pred.shape[0]}")
+    if batch_size == 0:
+        raise ZeroDivisionError("MRAccuracy of an empty batch")
+    if pred.is_cuda:
+        from umi import infer
+        pred = pred[:batch_size]
+        if pred.dtype == torch.float32:
+            mask = infer.binary_mask(pred.unsqueeze(1))
+        else:
+            mask = (torch.sigmoid(pred) >= 0.5).to(torch.uint8).contiguous()
+        # the dot sums first: both calls use the shared workspace, and the labelling's fault word has to survive until the copy
+        gts = infer.sum_trunc(target.detach().reshape(batch_size, -1).float()) if target.is_cuda else None
+        counts, fault = infer.count_objects(mask, _fault=True)
+        if gts is not None:
+            host = torch.cat([counts, gts, fault]).cpu().tolist()
+            n_pred, n_gt, code = host[:batch_size], host[batch_size:2 * batch_size], host[-1]
+        else:
+            host = torch.cat([counts, fault]).cpu().tolist()
+            tnp = target.detach().numpy()
+            n_pred, n_gt, code = host[:batch_size], [int(np.sum(tnp[b])) for b in range(batch_size)], host[-1]
+        if code:
+            raise RuntimeError(f"MRAccuracy: the component labelling reported fault {code}; the counts are invalid")
+    else:
+        from umi import components
+        tnp = target.detach().cpu().numpy()
+        pred_bin = torch.sigmoid(pred).numpy()
+        pred_bin = (pred_bin >= 0.5).astype(np.uint8)             # NaN compares false: 0
+        n_pred = [components.count_components_numpy(pred_bin[b]) for b in range(batch_size)]
+        n_gt = [int(np.sum(tnp[b])) for b in range(batch_size)]
+    mre = 0
+    for count_pred, count_gt in zip(n_pred, n_gt):
+        if count_gt != 0:
+            mre += abs(count_gt - count_pred) / (count_gt)
+        elif count_pred != 0:
+            mre += 1
+    mre /= batch_size
+    return mre
 
 
 def calc_loss(pred, target, bce_weight=0.5, loss_type='mse'):

@@ -6,8 +6,17 @@
 
     x = infer.preprocess(img, input_size=(512, 512))   # + the reference's cubic scipy.ndimage.zoom resize, on the device
 
+Binary (one-logit) models, the reference's test.py:391-455 and loss.py:422-440:
+
+    mask = infer.predict_binary_mask(model, x, out_hw=(h, w))      # sigmoid >= 0.5, nearest resize to the image's own size
+    mask = infer.predict_binary_mask_tiled(model, x, crop_size)    # the same over crop_size tiles of a padded image
+    labels, counts, area, sum_y, sum_x = infer.label_components(mask)   # 8-connected components, all on the device
+    counts = infer.count_objects(mask)
+
 No CPU path: the arithmetic is libunetmi kernels (the resize restates SciPy's spline algorithm, oracle/ref_resize.py).
 """
+import struct
+
 import numpy as np
 import torch
 
@@ -101,5 +110,177 @@ def predict_mask(model, x):
         if isinstance(out, tuple):
             return tuple(argmax_mask(o) for o in out)
         return argmax_mask(out)
+    finally:
+        model.train(was_training)
+
+
+# fp32 sigmoid(x) >= 0.5 as torch evaluates it (1 / (1 + exp(-x))) holds exactly for x >= this value, not for x >= 0: 1 + exp(-x)
+# rounds to 2 for every x down to -0x1.7ffffcp-23.  Found by bisection over fp32 bit patterns against torch.sigmoid on the CPU;
+# tests/test_binary_infer.py repeats the bisection on the torch build it runs on.
+SIGMOID_HALF_CUTOFF_BITS = 0xB43FFFFE
+SIGMOID_HALF_CUTOFF = struct.unpack("<f", struct.pack("<I", SIGMOID_HALF_CUTOFF_BITS))[0]      # -1.7881390590446244e-07
+
+
+def binary_mask(logits):
+    """[N,1,H,W] fp32 device logits -> uint8 [N,H,W], 1 where fp32 sigmoid(x) >= 0.5 (reference test.py:395-399,
+    loss.py:425-428).  The kernel compares x with SIGMOID_HALF_CUTOFF, which is where torch's sigmoid reaches exactly 0.5; it
+    evaluates no exp.  A NaN logit gives 0 (the reference's np.uint8(nan) is undefined)."""
+    ops._need_cuda(logits)
+    if logits.dim() != 4 or logits.shape[1] != 1 or logits.dtype != torch.float32:
+        raise ValueError(f"binary_mask expects fp32 logits [N,1,H,W], got {tuple(logits.shape)} {logits.dtype}")
+    logits = logits.contiguous()
+    N, _, H, W = logits.shape
+    mask = torch.empty((N, H, W), dtype=torch.uint8, device=logits.device)
+    if mask.numel():
+        L.check(L.fn("umi_binary_mask")(logits.data_ptr(), mask.data_ptr(), mask.numel(), ops._stream()), "umi_binary_mask")
+    return mask
+
+
+def zoom_nearest(mask, out_hw):
+    """scipy.ndimage.zoom(mask, (out_hw[0] / H, out_hw[1] / W), order=0) of an (H,W) or (N,H,W) uint8 / float32 device mask
+    (reference test.py:400-401), same dtype out.  SciPy's rule: output size round(in * zoom); sample coordinate
+    i * ((in - 1) / (out - 1)) in float64 (0 when out == 1); source index floor(x + 0.5); like the cubic resize, an output
+    whose coordinate exceeds in - 1 on either axis is 0 (the whole last row and column for 512 -> 224)."""
+    ops._need_cuda(mask)
+    if mask.dim() not in (2, 3) or mask.dtype not in (torch.uint8, torch.float32):
+        raise ValueError(f"zoom_nearest expects an (H,W) or (N,H,W) uint8 / float32 mask, got {tuple(mask.shape)} {mask.dtype}")
+    single = mask.dim() == 2
+    m = (mask.unsqueeze(0) if single else mask).contiguous()
+    N, H, W = m.shape
+    if N < 1 or H < 1 or W < 1:
+        raise ValueError(f"empty mask {tuple(mask.shape)}")
+    oh, ow = int(round(H * (out_hw[0] / H))), int(round(W * (out_hw[1] / W)))
+    if oh < 1 or ow < 1:
+        raise ValueError(f"output size {(oh, ow)}")
+    out = torch.empty((N, oh, ow), dtype=m.dtype, device=m.device)
+    st = L.fn("umi_zoom_nearest")(m.data_ptr(), 0 if m.dtype == torch.uint8 else 1, out.data_ptr(), N, H, W, oh, ow, ops._stream())
+    if st == -2:
+        raise ValueError(f"zoom_nearest: unsupported size {tuple(m.shape)} -> {(oh, ow)}")
+    L.check(st, "umi_zoom_nearest")
+    return out[0] if single else out
+
+
+def _component_mask(mask):
+    ops._need_cuda(mask)
+    if mask.dim() not in (2, 3) or mask.dtype != torch.uint8:
+        raise ValueError(f"expected a uint8 (N,H,W) or (H,W) mask, got {tuple(mask.shape)} {mask.dtype}")
+    if not mask.is_contiguous():
+        raise ValueError("the mask must be contiguous")
+    m = mask.unsqueeze(0) if mask.dim() == 2 else mask
+    N, H, W = m.shape
+    nbytes = L.fn("umi_components_ws_bytes")(N, H, W) if min(N, H, W) >= 1 and max(N, H, W) < 2 ** 31 else 0
+    if nbytes == 0:
+        raise ValueError(f"label_components: unsupported mask shape {tuple(mask.shape)} (N, H, W >= 1, N * H * W < 2**31)")
+    return m, N, H, W, nbytes
+
+
+def _raise_on_fault(ws, what):
+    code = int(ws[:4].view(torch.int32).item())
+    if code:
+        raise RuntimeError(f"{what}: the union-find reported fault {code} (iteration cap reached or parent chain corrupted); "
+                           "the results are invalid")
+
+
+def label_components(mask, check=False):
+    """8-connected components (cv2.connectedComponents(connectivity=8), reference loss.py:432) of a uint8 (N,H,W) or (H,W)
+    device mask, foreground = non-zero.  Returns, all on the device and without a host synchronisation:
+      labels int32, the mask's shape: 0 = background, 1..n numbered in the raster order of each component's first pixel
+             (scipy.ndimage.label's numbering with a full 3x3 structure);
+      counts int32 (N,);  area int32 (N,cap);  sum_y, sum_x int64 (N,cap): pixel count and integer coordinate sums per label
+             (pixel centroid = sum / area), cap = ceil(H/2) * ceil(W/2), rows beyond counts[n] are 0.
+    check=True reads the kernels' fault word back (one synchronisation) and raises if a find / union loop gave up."""
+    m, N, H, W, nbytes = _component_mask(mask)
+    cap = L.fn("umi_components_cap")(H, W)
+    dev = m.device
+    labels = torch.empty((N, H, W), dtype=torch.int32, device=dev)
+    counts = torch.empty(N, dtype=torch.int32, device=dev)
+    area = torch.empty((N, cap), dtype=torch.int32, device=dev)
+    sum_y = torch.empty((N, cap), dtype=torch.int64, device=dev)
+    sum_x = torch.empty((N, cap), dtype=torch.int64, device=dev)
+    ws = ops.workspace(nbytes, dev)
+    L.check(L.fn("umi_label_components")(m.data_ptr(), labels.data_ptr(), counts.data_ptr(), area.data_ptr(), sum_y.data_ptr(),
+                                         sum_x.data_ptr(), N, H, W, ws.data_ptr(), nbytes, ops._stream()), "umi_label_components")
+    if check:
+        _raise_on_fault(ws, "label_components")
+    return (labels[0] if mask.dim() == 2 else labels), counts, area, sum_y, sum_x
+
+
+def count_objects(mask, check=False, _fault=False):
+    """Number of 8-connected components per image, int32 (N,) on the device: label_components' `counts` without the relabel
+    and statistics passes."""
+    m, N, H, W, nbytes = _component_mask(mask)
+    counts = torch.empty(N, dtype=torch.int32, device=m.device)
+    ws = ops.workspace(nbytes, m.device)
+    L.check(L.fn("umi_count_components")(m.data_ptr(), counts.data_ptr(), N, H, W, ws.data_ptr(), nbytes, ops._stream()),
+            "umi_count_components")
+    if check:
+        _raise_on_fault(ws, "count_objects")
+    return (counts, ws[:4].view(torch.int32)) if _fault else counts
+
+
+def sum_trunc(x):
+    """int32 (N,): per image of a contiguous fp32 device tensor (N, ...) the float64 sum in a fixed order, truncated toward
+    zero: int(np.sum(dot_map[n])), exact for 0/1 maps."""
+    ops._need_cuda(x)
+    if x.dtype != torch.float32 or x.dim() < 2 or x.numel() == 0:
+        raise ValueError(f"sum_trunc expects a non-empty fp32 tensor (N, ...), got {tuple(x.shape)} {x.dtype}")
+    x = x.contiguous()
+    out = torch.empty(x.shape[0], dtype=torch.int32, device=x.device)
+    nbytes = L.fn("umi_sum_trunc_ws_bytes")(x.shape[0])
+    ws = ops.workspace(nbytes, x.device)
+    L.check(L.fn("umi_sum_trunc")(x.data_ptr(), out.data_ptr(), x.shape[0], x[0].numel(), ws.data_ptr(), nbytes, ops._stream()),
+            "umi_sum_trunc")
+    return out
+
+
+def _binary_head(out, out_hw):
+    m = binary_mask(out)
+    if out_hw is not None and (int(out_hw[0]) != m.shape[1] or int(out_hw[1]) != m.shape[2]):
+        m = zoom_nearest(m, out_hw)
+    return m
+
+
+@torch.no_grad()
+def predict_binary_mask(model, x, out_hw=None):
+    """Reference evaluation step of a one-logit model (test.py:391-404): eval-mode forward, sigmoid >= 0.5 -> uint8 [N,H,W]
+    mask, and the nearest (order-0) resize to `out_hw` = the image's own (height, width) when that differs from the network
+    size.  Two-headed models give a tuple of masks, as predict_mask does."""
+    was_training = model.training
+    model.eval()
+    try:
+        out = model(x.to("cuda"))
+        if isinstance(out, tuple):
+            return tuple(_binary_head(o, out_hw) for o in out)
+        return _binary_head(out, out_hw)
+    finally:
+        model.train(was_training)
+
+
+@torch.no_grad()
+def predict_binary_mask_tiled(model, x, crop_size):
+    """Reference test_single_crop (test.py:437-448): x (1,C,Hp,Wp) with Hp and Wp multiples of crop_size (padding the image
+    with 255 before `preprocess`, test.py:91-119, stays with the caller); every crop_size tile goes through the network on its
+    own, one tile per forward as the reference does, and its thresholded mask is placed into a uint8 (Hp,Wp) mask on the
+    device.  Two-headed models give a tuple of masks."""
+    crop_size = int(crop_size)
+    if x.dim() != 4 or x.shape[0] != 1:
+        raise ValueError(f"predict_binary_mask_tiled expects x (1,C,Hp,Wp), got {tuple(x.shape)}")
+    Hp, Wp = x.shape[2], x.shape[3]
+    if crop_size < 1 or Hp % crop_size or Wp % crop_size or Hp == 0 or Wp == 0:
+        raise ValueError(f"the padded image {Hp}x{Wp} is not a whole number of {crop_size}-pixel tiles")
+    x = x.to("cuda")
+    was_training = model.training
+    model.eval()
+    try:
+        pred = None
+        for i in range(0, Hp, crop_size):
+            for j in range(0, Wp, crop_size):
+                out = model(x[:, :, i:i + crop_size, j:j + crop_size].contiguous())
+                outs = out if isinstance(out, tuple) else (out,)
+                if pred is None:
+                    pred = [torch.zeros((Hp, Wp), dtype=torch.uint8, device=x.device) for _ in outs]
+                for p, o in zip(pred, outs):
+                    p[i:i + crop_size, j:j + crop_size] = binary_mask(o)[0]
+        return tuple(pred) if isinstance(out, tuple) else pred[0]
     finally:
         model.train(was_training)

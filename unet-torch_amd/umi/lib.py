@@ -178,6 +178,15 @@ SIGNATURES = {
     "umi_znorm_ws_bytes": (c_size_t, []),
     "umi_znorm_hwc": (c_int, [c_void_p, c_int, c_void_p, c_long, c_int, c_int, c_void_p, c_size_t, c_void_p]),
     "umi_argmax_mask": (c_int, [c_void_p, c_void_p, c_int, c_int, c_long, c_void_p]),
+    "umi_binary_mask": (c_int, [c_void_p, c_void_p, c_long, c_void_p]),
+    "umi_zoom_nearest": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p]),
+    "umi_sum_trunc_ws_bytes": (c_size_t, [c_int]),
+    "umi_sum_trunc": (c_int, [c_void_p, c_void_p, c_int, c_long, c_void_p, c_size_t, c_void_p]),
+    "umi_components_ws_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "umi_components_cap": (c_int, [c_int, c_int]),
+    "umi_count_components": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p]),
+    "umi_label_components": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p,
+                                     c_size_t, c_void_p]),
 }
 
 for _name, (_res, _args) in SIGNATURES.items():
