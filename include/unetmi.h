@@ -550,6 +550,44 @@ int umi_count_components(const unsigned char* mask, int* counts, int N, int H, i
 int umi_label_components(const unsigned char* mask, int* labels, int* counts, int* area, long long* sum_y, long long* sum_x,
                          int N, int H, int W, void* ws, size_t ws_bytes, umi_stream_t stream);
 
+/* Localisation scoring of a predicted mask's components against a ground-truth dot map (csrc/matching.hip): the reference's
+ * CrowdMatchingTest (Gaussian matching), three-argument CrowdMatchingTest2 (distance matching) and GMAE (grid count errors)
+ * restated on coordinate lists.  All results are integers; the float64 tables and the distance limit come from the host, so
+ * the device evaluates no exp and no square root.  Coordinate pairs are (x, y).  Nothing synchronises with the host.
+ *   umi_dot_lists: N [H][W] maps (dtype 0 = uint8, 1 = float32; a dot = a non-zero pixel) -> dots[N][max_dots][2] in raster
+ *     order and g_count[N].  max_dots <= umi_match_max_dots() (8192); H, W <= 65536, N * H * W < 2^31, N <= 65535.  An image
+ *     with more dots sets the fault word (the first int32 of ws, cleared by every call), keeps its first max_dots dots, stores
+ *     g_count = max_dots and writes nothing beyond its row.  ws: umi_dot_lists_ws_bytes(N, H, W) bytes (0: unsupported size).
+ *   umi_component_centers: umi_label_components' counts / area / sum_y / sum_x (rows of cap entries) -> centers[N][cap][2] =
+ *     (round(sum_x / area), round(sum_y / area)), ties to even, in integers; entries beyond counts[n] are (0, 0).
+ *   umi_crowd_match: out[N][S][T][2] = (tp, fp).  Per image the centres 0 .. c_count[n] - 1 (read on the device, clamped to
+ *     [0, cap]) are taken in order; each looks for the largest tables[s][dy + r][dx + r] over the still-unmatched dots with
+ *     |dx|, |dy| <= r = radii[s] (the lowest dot index on ties; 0 without such a dot); a value < thresh[t] is a false positive,
+ *     otherwise a true positive that removes the dot.  tables: the S tables of (2 r + 1)^2 float64 one after the other on
+ *     the device, table_len doubles in all; radii: S ints on the HOST, read before the call returns; S <= 8; thresh: T float64
+ *     on the device.  Dot coordinates must lie in [0, 65535]; centres may be any int32 (no address is formed from them).
+ *   umi_distance_match: out[N][3] = (tp, centres, dots).  Per image the dots in order; each takes the nearest centre not taken
+ *     yet (squared integer distance, the lowest centre index on ties) when its d2 <= d2_max.  |coordinates| < 2^29.
+ *     ws: umi_distance_match_ws_bytes(N, cap) bytes.
+ *   umi_grid_sums: out[N][8][8] = sums over the 8 x 8 grid of (size / 8)-pixel cells, clipped to the image: int64 for uint8 maps,
+ *     float64 in a fixed order for float32 maps.  size % 8 == 0.
+ *   umi_scatter_centers: map[N][H][W] (uint8) = 0, then 1 at every centre c < c_count[n] that lies inside the image. */
+int umi_match_max_dots(void);
+size_t umi_dot_lists_ws_bytes(int N, int H, int W);
+int umi_dot_lists(const void* map, int dtype, int* dots, int* g_count, int N, int H, int W, int max_dots, void* ws, size_t ws_bytes,
+                  umi_stream_t stream);
+int umi_component_centers(const int* counts, const int* area, const long long* sum_y, const long long* sum_x, int* centers, int N,
+                          int cap, umi_stream_t stream);
+int umi_crowd_match(const int* dots, const int* g_count, int max_dots, const int* centers, const int* c_count, int cap,
+                    const double* tables, size_t table_len, const int* radii, int S, const double* thresh, int T, int* out, int N,
+                    umi_stream_t stream);
+size_t umi_distance_match_ws_bytes(int N, int cap);
+int umi_distance_match(const int* dots, const int* g_count, int max_dots, const int* centers, const int* c_count, int cap,
+                       long long d2_max, int* out, int N, void* ws, size_t ws_bytes, umi_stream_t stream);
+int umi_grid_sums(const void* map, int dtype, void* out, int N, int H, int W, int size, umi_stream_t stream);
+int umi_scatter_centers(const int* centers, const int* c_count, int cap, unsigned char* map, int N, int H, int W,
+                        umi_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -13,6 +13,8 @@ Binary (one-logit) models, the reference's test.py:391-455 and loss.py:422-440:
     labels, counts, area, sum_y, sum_x = infer.label_components(mask)   # 8-connected components, all on the device
     counts = infer.count_objects(mask)
 
+    scores = infer.score_binary_masks(mask, gt_dots, [5, 20], np.arange(0.5, 1, 0.05))   # localisation metrics per image
+
 No CPU path: the arithmetic is libunetmi kernels (the resize restates SciPy's spline algorithm, oracle/ref_resize.py).
 """
 import struct
@@ -284,3 +286,59 @@ def predict_binary_mask_tiled(model, x, crop_size):
         return tuple(pred) if isinstance(out, tuple) else pred[0]
     finally:
         model.train(was_training)
+
+
+def score_binary_masks(mask, gt_dots, sigma_list, sigma_thresh_list, dist_thresh=10, size=512):
+    """What the reference's `ResultsCC.compareImages` (test.py:227-271) appends for each image of a batch, computed on the
+    device with ONE device-to-host copy: `mask` uint8 (N,H,W) predicted masks, `gt_dots` uint8 / float32 (N,H,W) 0/1 dot maps.
+    label_components -> centres -> Gaussian matching (CrowdMatchingTest) and distance matching (CrowdMatchingTest2) against the
+    dot lists -> grid sums of the dot map and of the map with a 1 at every centre (GMAE at levels 1-3 over `size` pixels).
+
+    Returns a list of N dicts: 'GT', 'Pred' (dot and component counts), 'AbsDiff', 'RelativeAccuracy', 'G1', 'G2', 'G3',
+    'arr_prec', 'arr_recall', 'arr_f1' ((S, T) float64 arrays), 'precision', 'recall', 'f1'.  An image with components but no
+    dots raises ZeroDivisionError, as the reference's CrowdMatchingTest2 does.
+
+    The centres are PIXEL centroids, round(sum / area) half to even (umi.matching.component_centers).  The reference's
+    `_findObjects` uses cv2.moments of the cv2.findContours outline, a different number that also drops components whose
+    outline encloses no area (while still counting them); OpenCV is not available to this project, so that definition is not
+    reproduced and 'Pred' here is the number of 8-connected components."""
+    import CrowdMatching as CM
+    from . import matching as M
+    if gt_dots.shape != mask.shape or mask.dim() != 3:
+        raise ValueError(f"score_binary_masks expects (N,H,W) masks and dot maps of one shape, got {tuple(mask.shape)} "
+                         f"{tuple(gt_dots.shape)}")
+    ops._need_cuda(mask, gt_dots)
+    N, H, W = mask.shape
+    _, counts, area, sum_y, sum_x = label_components(mask)
+    cc_fault = M._fault_word(ops.workspace(4, mask.device))
+    centers = M.component_centers(counts, area, sum_y, sum_x)
+    dots, g_count, dot_fault = M.dot_lists(gt_dots, _fault=True)
+    crowd = M.crowd_match(dots, g_count, centers, counts, sigma_list, sigma_thresh_list)
+    dist = M.distance_match(dots, g_count, centers, counts, dist_thresh)
+    cells_gt = M.grid_sums(gt_dots, size)
+    cells_pred = M.grid_sums(M.scatter_centers(centers, counts, H, W), size)
+    back = torch.cat([t.reshape(-1).to(torch.int64) for t in (cc_fault, dot_fault, counts, g_count, crowd, dist, cells_gt,
+                                                              cells_pred)]).cpu().numpy()
+    if back[0]:
+        raise RuntimeError(f"score_binary_masks: the union-find reported fault {back[0]}; the results are invalid")
+    M.raise_on_dot_overflow(back[1])
+    parts, at = [], 2
+    for n_el in (N, N, crowd.numel(), dist.numel(), N * 64, N * 64):
+        parts.append(back[at:at + n_el])
+        at += n_el
+    counts_h, g_h = parts[0], parts[1]
+    crowd_h, dist_h = parts[2].reshape(crowd.shape), parts[3].reshape(N, 3)
+    cg, cp = parts[4].reshape(N, 8, 8), parts[5].reshape(N, 8, 8)
+    out = []
+    for n in range(N):
+        gt, pred = int(g_h[n]), int(counts_h[n])
+        abs_diff, rel, _, _ = CM.countAccuracyMetric(gt, pred)
+        arr_prec, arr_recall, arr_f1 = CM.precision_recall_f1(crowd_h[n], gt, pred)
+        tp, nc, ng = (int(v) for v in dist_h[n])
+        prec, recall, f1 = (0, 0, 0) if nc == 0 else CM._prf_distance(tp, nc, ng)
+        out.append({"GT": gt, "Pred": pred, "AbsDiff": abs_diff, "RelativeAccuracy": rel,
+                    "G1": CM.game_from_cells(1, cg[n], cp[n])[0], "G2": CM.game_from_cells(2, cg[n], cp[n])[0],
+                    "G3": CM.game_from_cells(3, cg[n], cp[n])[0],
+                    "arr_prec": arr_prec, "arr_recall": arr_recall, "arr_f1": arr_f1,
+                    "precision": prec, "recall": recall, "f1": f1})
+    return out

@@ -187,6 +187,17 @@ SIGNATURES = {
     "umi_count_components": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p]),
     "umi_label_components": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p,
                                      c_size_t, c_void_p]),
+    "umi_match_max_dots": (c_int, []),
+    "umi_dot_lists_ws_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "umi_dot_lists": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p]),
+    "umi_component_centers": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p]),
+    "umi_crowd_match": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_size_t, c_void_p, c_int,
+                                c_void_p, c_int, c_void_p, c_int, c_void_p]),
+    "umi_distance_match_ws_bytes": (c_size_t, [c_int, c_int]),
+    "umi_distance_match": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, ctypes.c_longlong, c_void_p, c_int,
+                                   c_void_p, c_size_t, c_void_p]),
+    "umi_grid_sums": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
+    "umi_scatter_centers": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_void_p]),
 }
 
 for _name, (_res, _args) in SIGNATURES.items():
