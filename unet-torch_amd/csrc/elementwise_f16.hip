@@ -166,30 +166,77 @@ __global__ __launch_bounds__(256) void colsum_group_reduce(CsGroup grp, const fl
 }
 
 // ---- BN + ReLU backward, stage 3: dy = gamma*rstd * (dz - sum_dz/M - xhat*sum_dzx/M), in place ---------------
+// Streaming form.  A workgroup owns up to BNA_GB = 64 channel groups (blockIdx.y walks wider tensors) and RPW consecutive
+// rows (blockIdx.x).  The per-channel constants are fetched once per workgroup with coalesced loads, transposed through LDS
+// ([j][group]: conflict-free reads) and kept in registers for all its rows -- the first form loaded them per thread (22 load
+// instructions touching 16-64 lines each) for as little as ONE row on the deep levels.  A wave covers contiguous bytes:
+// 64 lanes x 16 B of one row (C >= 512) or 64 / (C/8) whole rows.  Per trip a thread takes BNA_RT rows PL = 256 / groups
+// apart: all 2 * BNA_RT loads are issued (row index clamped to the workgroup's last row, so the loads need no branch)
+// before the first use, the stores are predicated.  A clamped load may read a row another thread is storing: its value
+// is discarded.  The arithmetic is umi_bn_dz8 (common.h), as before.
+#define BNA_GB 64
+#ifndef BNA_RT
+#define BNA_RT 4
+#endif
 __global__ __launch_bounds__(256) void bn_bwd_apply_v8(half_t* __restrict__ da, int ldda, const half_t* __restrict__ y,
                                                        int ldy, const float4* __restrict__ tx,
                                                        const float* __restrict__ rstd,
                                                        const float* __restrict__ sum_dz,
-                                                       const float* __restrict__ sum_dzx, long M, int C) {
-    const int G = C >> 3;
-    const long gt = (long)blockIdx.x * 256 + threadIdx.x;     // gridDim*256 is a multiple of G => cg fixed per thread
-    const int cg = (int)(gt % G);
-    const long stride_rows = ((long)gridDim.x * 256) / G;
+                                                       const float* __restrict__ sum_dzx, long M, int C, int RPW) {
+    __shared__ float4 s_t[8][BNA_GB];
+    __shared__ float s_k[3][8][BNA_GB];
+    const int tid = threadIdx.x;
+    const int G = C >> 3;                                      // a power of two <= 256 (vec_ok)
+    const int Gb = G < BNA_GB ? G : BNA_GB;
+    const int PL = 256 / Gb;
+    const int cgl = tid & (Gb - 1), pl = tid / Gb;
+    const int cb = blockIdx.y * (Gb * 8);                      // first channel of this workgroup
     const float invM = 1.f / (float)M;
+    for (int i = tid; i < Gb * 8; i += 256) {
+        const int c = cb + i;
+        s_t[i & 7][i >> 3] = tx[c];
+        s_k[0][i & 7][i >> 3] = rstd[c];
+        s_k[1][i & 7][i >> 3] = sum_dz[c] * invM;
+        s_k[2][i & 7][i >> 3] = sum_dzx[c] * invM;
+    }
+    __syncthreads();
     float4 t[8];
     float rs[8], c1[8], c2[8];
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
-        int c = cg * 8 + j;
-        t[j] = tx[c];
-        rs[j] = rstd[c];
-        c1[j] = sum_dz[c] * invM;
-        c2[j] = sum_dzx[c] * invM;
+        t[j] = s_t[j][cgl];
+        rs[j] = s_k[0][j][cgl];
+        c1[j] = s_k[1][j][cgl];
+        c2[j] = s_k[2][j][cgl];
     }
-    for (long r = gt / G; r < M; r += stride_rows) {
-        half8 yv = *reinterpret_cast<const half8*>(y + r * ldy + cg * 8);
-        half8 gv = *reinterpret_cast<const half8*>(da + r * ldda + cg * 8);
-        *reinterpret_cast<half8*>(da + r * ldda + cg * 8) = umi_bn_dz8(yv, gv, t, rs, c1, c2);
+    const long r0 = (long)blockIdx.x * RPW;
+    long r1 = r0 + RPW;
+    if (r1 > M) r1 = M;
+    const int nr = (int)(r1 - r0);                             // rows of this workgroup
+    // workgroup-uniform bases + 32-bit lane offsets (the launch keeps RPW * ld below 2^30 elements)
+    half_t* dab = da + r0 * ldda + cb;
+    const half_t* yb = y + r0 * ldy + cb;
+    for (int r = pl; r < nr; r += BNA_RT * PL) {
+        unsigned oy[BNA_RT], og[BNA_RT];
+        half8 yv[BNA_RT], gv[BNA_RT];
+#pragma unroll
+        for (int k = 0; k < BNA_RT; ++k) {
+            const int q = r + k * PL < nr ? r + k * PL : nr - 1;
+            oy[k] = (unsigned)(q * ldy + cgl * 8);
+            og[k] = (unsigned)(q * ldda + cgl * 8);
+        }
+#pragma unroll
+        for (int k = 0; k < BNA_RT; ++k) {
+            yv[k] = *reinterpret_cast<const half8*>(yb + oy[k]);
+            gv[k] = *reinterpret_cast<const half8*>(dab + og[k]);
+        }
+#pragma unroll
+        for (int k = 0; k < BNA_RT; ++k) asm volatile("" : "+v"(yv[k]), "+v"(gv[k]));   // every load issued before the first use
+#pragma unroll
+        for (int k = 0; k < BNA_RT; ++k) {
+            const half8 o = umi_bn_dz8(yv[k], gv[k], t, rs, c1, c2);
+            if (r + k * PL < nr) *reinterpret_cast<half8*>(dab + og[k]) = o;
+        }
     }
 }
 
@@ -330,6 +377,29 @@ int grid_for(long items) {
     return (int)g;
 }
 
+// rows per lane of a bn_bwd_apply_v8 workgroup (a workgroup owns PL times as many rows; gy = workgroups across the channels):
+// about BNA_WGS workgroups per launch, whole trips of BNA_RT rows, at least BNA_MIN_RL and at most BNA_MAX_RL rows.  At the
+// bench shapes (batch 16) a lane owns 64 / 32 / 16 / 8 / 8 rows at 512^2 x 64 ... 32^2 x 1024.  Same-process A/B on one box
+// (profiles/bn_apply_stream_grid_rule_ab.txt, us per launch from 512^2 down to 32^2): first form 321 / 160 / 106 / 74 / 71,
+// this rule 314 / 157 / 70 / 33 / 19; 1,024 or 4,096 workgroups, a floor of 4 or 16 rows, 2 or 8 rows per trip are each within
+// 3 % of it on every level where they win and lose up to 13 % elsewhere (one-trip workgroups at 32^2: 22 us).  The macros are
+// what tools/build_variant.py overrides for that A/B.
+#ifndef BNA_WGS
+#define BNA_WGS 2048
+#endif
+#ifndef BNA_MIN_RL
+#define BNA_MIN_RL 8
+#endif
+#ifndef BNA_MAX_RL
+#define BNA_MAX_RL 64
+#endif
+int bna_rows_per_lane(long M, int PL, int gy) {
+    const long per_wg = (long)PL * (BNA_WGS / gy);
+    long rl = (M + per_wg - 1) / per_wg;
+    rl = (rl + BNA_RT - 1) / BNA_RT * BNA_RT;
+    return (int)(rl < BNA_MIN_RL ? BNA_MIN_RL : (rl > BNA_MAX_RL ? BNA_MAX_RL : rl));
+}
+
 }  // namespace
 
 int umi_bn_bwd_rpb_f16v(long M) { return rpb_for(M); }
@@ -399,8 +469,11 @@ bool umi_bn_bwd_reduce1_f16v(const void* da, int ldda, const void* y, int ldy, c
 bool umi_bn_bwd_apply_f16v(void* da, int ldda, const void* y, int ldy, const void* tx, const float* rstd,
                            const float* sum_dz, const float* sum_dzx, long M, int C, hipStream_t s) {
     if (!vec_ok(C, ldda, ldy, da, y)) return false;
-    hipLaunchKernelGGL(bn_bwd_apply_v8, dim3(grid_for(M * (C / 8))), dim3(256), 0, s, (half_t*)da, ldda, (const half_t*)y, ldy,
-                       (const float4*)tx, rstd, sum_dz, sum_dzx, M, C);
+    const int G = C / 8, Gb = G < BNA_GB ? G : BNA_GB, PL = 256 / Gb, gy = G / Gb;
+    const int rpw = bna_rows_per_lane(M, PL, gy) * PL;
+    if ((long)rpw * (ldda > ldy ? ldda : ldy) >= (1L << 30)) return false;      // 32-bit offsets inside a workgroup
+    hipLaunchKernelGGL(bn_bwd_apply_v8, dim3((unsigned)((M + rpw - 1) / rpw), gy), dim3(256), 0, s, (half_t*)da, ldda,
+                       (const half_t*)y, ldy, (const float4*)tx, rstd, sum_dz, sum_dzx, M, C, rpw);
     return true;
 }
 
