@@ -550,6 +550,25 @@ int umi_count_components(const unsigned char* mask, int* counts, int N, int H, i
 int umi_label_components(const unsigned char* mask, int* labels, int* counts, int* area, long long* sum_y, long long* sum_x,
                          int N, int H, int W, void* ws, size_t ws_bytes, umi_stream_t stream);
 
+/* The same for class-valued masks (values 0 .. n_classes - 1, 2 <= n_classes <= 8): two pixels are in one component iff they
+ * are 8-connected through pixels of the same non-zero value, i.e. the partition of scipy.ndimage.label(mask == c, ones((3,3)))
+ * for every c, all classes in the same launches.  Labels 1..counts[n] run over ALL classes in the raster order of each
+ * component's first pixel.
+ *   umi_count_class_components: class_counts[N][n_classes] only (column 0 is 0).
+ *   umi_label_class_components: labels[N][H][W], counts[N], class_counts[N][n_classes], label_class[N][cap] (uint8, the class
+ *     of label i + 1), area[N][cap], sum_y / sum_x[N][cap]; rows beyond counts[n] are 0.  cap (1 .. H * W) is the caller's:
+ *     with four classes every pixel can be its own component.  An image with more components than cap keeps counts,
+ *     class_counts and labels exact, gets the first cap labels' rows, has nothing written beyond them and sets the fault word
+ *     to UMI_CC_FAULT_CAP (6).
+ *   A mask value >= n_classes is background and sets the fault word to UMI_CC_FAULT_CLASS (5); it is never used as an index.
+ *   ws: umi_class_components_ws_bytes(N, H, W, n_classes) bytes (0: unsupported), first int32 = the fault word as above. */
+size_t umi_class_components_ws_bytes(int N, int H, int W, int n_classes);
+int umi_count_class_components(const unsigned char* mask, int* class_counts, int N, int H, int W, int n_classes, void* ws,
+                               size_t ws_bytes, umi_stream_t stream);
+int umi_label_class_components(const unsigned char* mask, int* labels, int* counts, int* class_counts, unsigned char* label_class,
+                               int* area, long long* sum_y, long long* sum_x, int N, int H, int W, int n_classes, int cap, void* ws,
+                               size_t ws_bytes, umi_stream_t stream);
+
 /* Localisation scoring of a predicted mask's components against a ground-truth dot map (csrc/matching.hip): the reference's
  * CrowdMatchingTest (Gaussian matching), three-argument CrowdMatchingTest2 (distance matching) and GMAE (grid count errors)
  * restated on coordinate lists.  All results are integers; the float64 tables and the distance limit come from the host, so
@@ -571,7 +590,13 @@ int umi_label_components(const unsigned char* mask, int* labels, int* counts, in
  *     ws: umi_distance_match_ws_bytes(N, cap) bytes.
  *   umi_grid_sums: out[N][8][8] = sums over the 8 x 8 grid of (size / 8)-pixel cells, clipped to the image: int64 for uint8 maps,
  *     float64 in a fixed order for float32 maps.  size % 8 == 0.
- *   umi_scatter_centers: map[N][H][W] (uint8) = 0, then 1 at every centre c < c_count[n] that lies inside the image. */
+ *   umi_scatter_centers: map[N][H][W] (uint8) = 0, then 1 at every centre c < c_count[n] that lies inside the image.
+ *   umi_split_classes: a class-valued uint8 map[N][H][W] -> planes[N][n_classes - 1][H][W] (uint8 0/1), plane c - 1 = (map == c);
+ *     the functions above take the planes as N * (n_classes - 1) images.
+ *   umi_class_center_lists: umi_label_class_components' counts / label_class / area / sum_y / sum_x (rows of cap entries) ->
+ *     centers[N * (n_classes - 1)][cap][2] and c_count[N * (n_classes - 1)]: per (image, class 1 .. n_classes - 1) the centres
+ *     (as umi_component_centers forms them) of that class's labels in label order, (0, 0) beyond the count.  Labels beyond
+ *     cap (UMI_CC_FAULT_CAP) are not listed. */
 int umi_match_max_dots(void);
 size_t umi_dot_lists_ws_bytes(int N, int H, int W);
 int umi_dot_lists(const void* map, int dtype, int* dots, int* g_count, int N, int H, int W, int max_dots, void* ws, size_t ws_bytes,
@@ -587,6 +612,9 @@ int umi_distance_match(const int* dots, const int* g_count, int max_dots, const 
 int umi_grid_sums(const void* map, int dtype, void* out, int N, int H, int W, int size, umi_stream_t stream);
 int umi_scatter_centers(const int* centers, const int* c_count, int cap, unsigned char* map, int N, int H, int W,
                         umi_stream_t stream);
+int umi_split_classes(const unsigned char* map, unsigned char* planes, int N, int H, int W, int n_classes, umi_stream_t stream);
+int umi_class_center_lists(const int* counts, const unsigned char* label_class, const int* area, const long long* sum_y,
+                           const long long* sum_x, int* centers, int* c_count, int N, int cap, int n_classes, umi_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -18,7 +18,10 @@
 #define UMI_CC_HD inline
 #endif
 
-enum { UMI_CC_OK = 0, UMI_CC_FAULT_FIND_CAP = 1, UMI_CC_FAULT_UNION_CAP = 2, UMI_CC_FAULT_CHAIN = 3, UMI_CC_FAULT_RANK = 4 };
+// UMI_CC_FAULT_CLASS: a mask value >= n_classes was met (taken as background); UMI_CC_FAULT_CAP: an image has more components
+// than the caller's statistics rows hold (counts and the label map stay exact, the rows hold the first `cap` labels).
+enum { UMI_CC_OK = 0, UMI_CC_FAULT_FIND_CAP = 1, UMI_CC_FAULT_UNION_CAP = 2, UMI_CC_FAULT_CHAIN = 3, UMI_CC_FAULT_RANK = 4,
+       UMI_CC_FAULT_CLASS = 5, UMI_CC_FAULT_CAP = 6 };
 
 template <class M>
 UMI_CC_HD int umi_cc_find(const int* parent, int a, int cap, int* fault) {

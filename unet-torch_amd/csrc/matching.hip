@@ -30,6 +30,11 @@
 //   grid sums    one workgroup per cell of the 8 x 8 grid of size/8-pixel cells: int64 for uint8 maps, float64 in a fixed order
 //                (strided per thread, then a fixed tree) for float32 maps.
 //   scatter      map[n][y][x] = 1 per centre inside the image (a store, not an add: coinciding centres count once).
+//   class split  a class-valued map (N,H,W) -> (N,K-1,H,W) 0/1 planes, plane c - 1 = (map == c); the passes above then run
+//                unchanged on the (N * (K - 1), H, W) view.
+//   class lists  umi_label_class_components' statistics -> per (image, class) the centres of that class's labels in label order
+//                (the raster order of first pixels) and their number: one workgroup per (image, class) walks the labels 256 at a
+//                time, positions by ballot rank plus a running total, so the order is fixed and no atomic is involved.
 #include "common.h"
 
 namespace {
@@ -328,6 +333,52 @@ __global__ __launch_bounds__(256) void mt_scatter_kernel(const int* __restrict__
     map[((long)n * H + y) * W + x] = 1;
 }
 
+// grid (cdiv(HW, 256), K - 1, N)
+__global__ __launch_bounds__(256) void mt_split_classes_kernel(const unsigned char* __restrict__ map, unsigned char* __restrict__ planes,
+                                                               int HW) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= HW) return;
+    const int c = blockIdx.y + 1;
+    planes[((long)blockIdx.z * gridDim.y + blockIdx.y) * HW + i] = map[(long)blockIdx.z * HW + i] == c;
+}
+
+// grid (K - 1, N): class blockIdx.x + 1 of image blockIdx.y.  centers was zeroed by the launch function.
+__global__ __launch_bounds__(256) void mt_class_centers_kernel(const int* __restrict__ counts, const unsigned char* __restrict__ label_class,
+                                                               const int* __restrict__ area, const long long* __restrict__ sum_y,
+                                                               const long long* __restrict__ sum_x, int* __restrict__ centers,
+                                                               int* __restrict__ c_count, int cap) {
+    __shared__ int wcnt[4];
+    const int n = blockIdx.y, c = blockIdx.x + 1, lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const int nl = min(max(counts[n], 0), cap);
+    const long row = (long)n * cap;
+    int* out = centers + ((long)n * gridDim.x + blockIdx.x) * cap * 2;
+    int run = 0;                                                 // workgroup-uniform
+    for (int i0 = 0; i0 < nl; i0 += 256) {
+        const int i = i0 + threadIdx.x;
+        const bool f = i < nl && label_class[row + i] == c;
+        const unsigned long long b = __ballot(f);
+        if (lane == 0) wcnt[wv] = __popcll(b);
+        __syncthreads();
+        int pre = 0;
+        for (int j = 0; j < wv; ++j) pre += wcnt[j];
+        const int tot = wcnt[0] + wcnt[1] + wcnt[2] + wcnt[3];
+        if (f) {
+            const int pos = run + pre + __popcll(b & ((1ull << lane) - 1ull));      // < nl <= cap
+            const int a = area[row + i];
+            int x = 0, y = 0;
+            if (a > 0 && sum_x[row + i] >= 0 && sum_y[row + i] >= 0) {
+                x = mt_round_div(sum_x[row + i], a);
+                y = mt_round_div(sum_y[row + i], a);
+            }
+            out[2 * pos] = x;
+            out[2 * pos + 1] = y;
+        }
+        run += tot;
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) c_count[(long)n * gridDim.x + blockIdx.x] = run;
+}
+
 struct DotPlan {
     int hw, nblk;
     size_t total;
@@ -447,6 +498,30 @@ extern "C" int umi_scatter_centers(const int* centers, const int* c_count, int c
     const hipError_t e = hipMemsetAsync(map, 0, (size_t)N * H * W, s);
     if (e != hipSuccess) return (int)e;
     hipLaunchKernelGGL(mt_scatter_kernel, dim3(umi_cdiv((long)N * cap, 256)), dim3(256), 0, s, centers, c_count, cap, map, N, H, W);
+    UMI_LAUNCH_CHECK();
+    return UMI_OK;
+}
+
+extern "C" int umi_split_classes(const unsigned char* map, unsigned char* planes, int N, int H, int W, int n_classes, umi_stream_t stream) {
+    if (!map || !planes || N <= 0 || H <= 0 || W <= 0 || n_classes < 2) return UMI_ERR_BADARG;
+    if (n_classes > 256 || (long)N * (n_classes - 1) * H * W >= (1L << 31) || N > 65535) return UMI_ERR_UNSUPPORTED;
+    hipLaunchKernelGGL(mt_split_classes_kernel, dim3(umi_cdiv((long)H * W, 256), n_classes - 1, N), dim3(256), 0, (hipStream_t)stream, map,
+                       planes, H * W);
+    UMI_LAUNCH_CHECK();
+    return UMI_OK;
+}
+
+extern "C" int umi_class_center_lists(const int* counts, const unsigned char* label_class, const int* area, const long long* sum_y,
+                                      const long long* sum_x, int* centers, int* c_count, int N, int cap, int n_classes,
+                                      umi_stream_t stream) {
+    if (!counts || !label_class || !area || !sum_y || !sum_x || !centers || !c_count || N <= 0 || cap <= 0 || n_classes < 2)
+        return UMI_ERR_BADARG;
+    if (n_classes > 256 || (long)N * (n_classes - 1) * cap >= (1L << 30) || N > 65535) return UMI_ERR_UNSUPPORTED;
+    hipStream_t s = (hipStream_t)stream;
+    const hipError_t e = hipMemsetAsync(centers, 0, (size_t)N * (n_classes - 1) * cap * 2 * sizeof(int), s);
+    if (e != hipSuccess) return (int)e;
+    hipLaunchKernelGGL(mt_class_centers_kernel, dim3(n_classes - 1, N), dim3(256), 0, s, counts, label_class, area, sum_y, sum_x, centers,
+                       c_count, cap);
     UMI_LAUNCH_CHECK();
     return UMI_OK;
 }

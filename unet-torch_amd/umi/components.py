@@ -4,6 +4,8 @@
 order of each component's first pixel (scipy.ndimage.label with a full 3x3 structure numbers them the same way;
 tests/test_binary_infer.py compares the maps with `==`), counts, and per-label area and integer coordinate sums in rows of
 `components_cap(H, W)` entries.  `loss.MRAccuracy` uses it for CPU tensors and the GPU tests use it as their live oracle.
+`label_class_components_numpy(mask, n_classes)` is the same statement for class-valued masks (components of equal non-zero
+value, numbered over all classes), the counterpart of `umi.infer.label_class_components`.
 
 Run-based two-pass: the rows are cut into runs of foreground pixels, runs of adjacent rows that touch (8-connectivity: column
 ranges overlapping after widening one of them by a pixel on each side) are linked, and the run graph is reduced to its
@@ -121,6 +123,75 @@ def label_components_numpy(mask, return_first=False):
     if single:
         labels = labels[0]
     out = (labels, counts, area, sum_y, sum_x)
+    return out + (firsts,) if return_first else out
+
+
+MAX_CLASSES = 8                      # class values 0 .. 7 (csrc/components.hip CC_MAX_CLASSES)
+
+
+def class_components_cap(H, W, n_classes):
+    """Upper bound on the number of same-class 8-connected components of an H x W mask with values 0 .. n_classes - 1: the
+    four pixels of a 2 x 2 block are mutually adjacent, so a block meets at most one component per class and at most four."""
+    return min(min(n_classes - 1, 4) * components_cap(H, W), H * W)
+
+
+def label_class_components_numpy(mask, n_classes, max_components=None, return_first=False):
+    """Class-aware labelling of an (N, H, W) or (H, W) array of class values 0 .. n_classes - 1: two pixels are in one
+    component iff they are 8-connected through pixels of the same non-zero value (scipy.ndimage.label(mask == c, ones((3, 3)))
+    for every c).  A value >= n_classes is background.  Returns what umi.infer.label_class_components returns:
+      labels int32 (the mask's shape; 0 = background, 1..n over ALL classes in the raster order of each component's first pixel),
+      counts int32 (N,), class_counts int32 (N, n_classes) (column 0 is 0), label_class uint8 (N, cap), area int32 (N, cap),
+      sum_y and sum_x int64 (N, cap); cap = max_components or class_components_cap(H, W, n_classes); rows beyond counts[n]
+      are 0 and an image with more than cap components keeps exact counts and labels and the rows of its first cap labels.
+    return_first=True appends a list with each image's vector of first-pixel flat indices, one per label."""
+    mask = np.asarray(mask)
+    if mask.ndim == 2:
+        mask = mask[None]
+        single = True
+    elif mask.ndim == 3:
+        single = False
+    else:
+        raise ValueError(f"expected an (N, H, W) or (H, W) mask, got {mask.shape}")
+    if not 2 <= n_classes <= MAX_CLASSES:
+        raise ValueError(f"n_classes must be in 2..{MAX_CLASSES}")
+    N, H, W = mask.shape
+    if H < 1 or W < 1:
+        raise ValueError(f"empty mask {mask.shape}")
+    cap = class_components_cap(H, W, n_classes) if max_components is None else int(max_components)
+    if not 1 <= cap <= H * W:
+        raise ValueError(f"max_components must be in 1..{H * W}")
+    labels = np.zeros((N, H, W), dtype=np.int32)
+    counts = np.zeros(N, dtype=np.int32)
+    class_counts = np.zeros((N, n_classes), dtype=np.int32)
+    label_class = np.zeros((N, cap), dtype=np.uint8)
+    area = np.zeros((N, cap), dtype=np.int32)
+    sum_y = np.zeros((N, cap), dtype=np.int64)
+    sum_x = np.zeros((N, cap), dtype=np.int64)
+    firsts = []
+    for n in range(N):
+        per = []
+        for c in range(1, n_classes):
+            lab, cnt, a, sy, sx, first = _label_one(mask[n] == c)
+            class_counts[n, c] = cnt
+            per.append((c, lab, a[:cnt], sy[:cnt], sx[:cnt], first))
+        first = np.concatenate([p[5] for p in per])
+        order = np.argsort(first, kind="stable")                # first pixels are distinct: the global raster order
+        counts[n] = first.size
+        k = min(first.size, cap)
+        for name, j in ((area, 2), (sum_y, 3), (sum_x, 4)):
+            name[n, :k] = np.concatenate([p[j] for p in per])[order][:k]
+        label_class[n, :k] = np.concatenate([np.full(p[5].size, p[0], dtype=np.uint8) for p in per])[order][:k]
+        number = np.empty(first.size, dtype=np.int32)
+        number[order] = np.arange(1, first.size + 1, dtype=np.int32)
+        at = 0
+        for c, lab, *_rest, f in per:
+            lut = np.concatenate([np.zeros(1, dtype=np.int32), number[at:at + f.size]])
+            labels[n] += lut[lab]
+            at += f.size
+        firsts.append(first[order])
+    if single:
+        labels = labels[0]
+    out = (labels, counts, class_counts, label_class, area, sum_y, sum_x)
     return out + (firsts,) if return_first else out
 
 

@@ -15,6 +15,12 @@ Binary (one-logit) models, the reference's test.py:391-455 and loss.py:422-440:
 
     scores = infer.score_binary_masks(mask, gt_dots, [5, 20], np.arange(0.5, 1, 0.05))   # localisation metrics per image
 
+Multi-class models, the rest of test_mc3serousv5.py (Results2Class / Results3Class) after predict_mask:
+
+    labels, counts, class_counts, label_class, area, sum_y, sum_x = infer.label_class_components(mask, n_classes)
+    class_counts = infer.count_class_objects(mask, n_classes)
+    scores = infer.score_multiclass_masks(mask, gt_dots, n_classes, [10, 20], np.arange(0.5, 1, 0.05))
+
 No CPU path: the arithmetic is libunetmi kernels (the resize restates SciPy's spline algorithm, oracle/ref_resize.py).
 """
 import struct
@@ -342,3 +348,137 @@ def score_binary_masks(mask, gt_dots, sigma_list, sigma_thresh_list, dist_thresh
                     "arr_prec": arr_prec, "arr_recall": arr_recall, "arr_f1": arr_f1,
                     "precision": prec, "recall": recall, "f1": f1})
     return out
+
+
+# ---- class-valued masks ----------------------------------------------------------------------------------------------------------
+_CLASS_FAULTS = {5: "the mask holds a value >= n_classes (taken as background)",
+                 6: "an image has more components than max_components; counts and labels are exact, the statistics rows hold "
+                    "the first max_components labels only"}
+
+
+def _raise_on_class_fault(code, what):
+    code = int(code)
+    if code:
+        raise RuntimeError(f"{what}: " + _CLASS_FAULTS.get(code, f"the union-find reported fault {code} (iteration cap reached or "
+                                                                 "parent chain corrupted); the results are invalid"))
+
+
+def _class_component_mask(mask, n_classes):
+    from .components import MAX_CLASSES
+    K = int(n_classes)
+    if not 2 <= K <= MAX_CLASSES:
+        raise ValueError(f"n_classes must be in 2..{MAX_CLASSES}, got {n_classes}")
+    m, N, H, W, _ = _component_mask(mask)
+    nbytes = L.fn("umi_class_components_ws_bytes")(N, H, W, K)
+    if nbytes == 0:
+        raise ValueError(f"label_class_components: unsupported mask shape {tuple(mask.shape)}")
+    return m, N, H, W, K, nbytes
+
+
+def _label_class_components(mask, n_classes, max_components):
+    """label_class_components' seven outputs and the int32 view of the kernels' fault word."""
+    from .components import class_components_cap
+    m, N, H, W, K, nbytes = _class_component_mask(mask, n_classes)
+    cap = class_components_cap(H, W, K) if max_components is None else int(max_components)
+    if not 1 <= cap <= H * W:
+        raise ValueError(f"max_components must be in 1..{H * W}, got {max_components}")
+    dev = m.device
+    labels = torch.empty((N, H, W), dtype=torch.int32, device=dev)
+    counts = torch.empty(N, dtype=torch.int32, device=dev)
+    class_counts = torch.empty((N, K), dtype=torch.int32, device=dev)
+    label_class = torch.empty((N, cap), dtype=torch.uint8, device=dev)
+    area = torch.empty((N, cap), dtype=torch.int32, device=dev)
+    sum_y = torch.empty((N, cap), dtype=torch.int64, device=dev)
+    sum_x = torch.empty((N, cap), dtype=torch.int64, device=dev)
+    ws = ops.workspace(nbytes, dev)
+    L.check(L.fn("umi_label_class_components")(m.data_ptr(), labels.data_ptr(), counts.data_ptr(), class_counts.data_ptr(),
+                                               label_class.data_ptr(), area.data_ptr(), sum_y.data_ptr(), sum_x.data_ptr(), N, H, W, K,
+                                               cap, ws.data_ptr(), nbytes, ops._stream()), "umi_label_class_components")
+    return ((labels[0] if mask.dim() == 2 else labels), counts, class_counts, label_class, area, sum_y, sum_x), \
+        ws[:4].view(torch.int32)
+
+
+def label_class_components(mask, n_classes, max_components=None, check=False):
+    """Class-aware 8-connected components of a uint8 (N,H,W) or (H,W) device mask of class values 0 .. n_classes - 1
+    (2 <= n_classes <= 8), e.g. predict_mask's output: two pixels belong to one component iff they are 8-connected through
+    pixels of the same non-zero value -- scipy.ndimage.label(mask == c, ones((3, 3))) for every c, all classes in one set of
+    launches (reference test_mc3serousv5.py:410-443 `_findObjects` loops over the classes on the host).  Returns, all on the
+    device and without a host synchronisation:
+      labels int32, the mask's shape: 0 = background, 1..n over ALL classes in the raster order of each component's first pixel;
+      counts int32 (N,);  class_counts int32 (N, n_classes), column 0 is 0;  label_class uint8 (N, cap): the class of label i + 1;
+      area int32 (N, cap);  sum_y, sum_x int64 (N, cap);  rows beyond counts[n] are 0.
+    cap = max_components (1 .. H * W), by default min(n_classes - 1, 4) * ceil(H/2) * ceil(W/2) (at most H * W), which no mask
+    exceeds: a 2 x 2 block meets one component per class.  With a smaller max_components an image that has more components
+    keeps exact counts, class_counts and labels, gets the rows of its first cap labels, and sets a fault code; a mask value
+    >= n_classes is taken as background and sets another (the first of the two stays; a union-find fault overrides both).  check=True reads the fault word back (one synchronisation) and
+    raises on either, and on a union-find fault.  With n_classes = 2 and the default cap, labels, counts, area and the sums
+    are label_components' bit for bit on a 0/1 mask."""
+    outs, fault = _label_class_components(mask, n_classes, max_components)
+    if check:
+        _raise_on_class_fault(fault.item(), "label_class_components")
+    return outs
+
+
+def count_class_objects(mask, n_classes, check=False):
+    """Number of components per image and class, int32 (N, n_classes) on the device (column 0 is 0): label_class_components'
+    `class_counts` without the flatten, rank, relabel and statistics passes."""
+    m, N, H, W, K, nbytes = _class_component_mask(mask, n_classes)
+    class_counts = torch.empty((N, K), dtype=torch.int32, device=m.device)
+    ws = ops.workspace(nbytes, m.device)
+    L.check(L.fn("umi_count_class_components")(m.data_ptr(), class_counts.data_ptr(), N, H, W, K, ws.data_ptr(), nbytes,
+                                               ops._stream()), "umi_count_class_components")
+    if check:
+        _raise_on_class_fault(ws[:4].view(torch.int32).item(), "count_class_objects")
+    return class_counts
+
+
+def score_multiclass_masks(mask, gt_dots, n_classes, sigma_list, sigma_thresh_list, size=512, max_components=65536):
+    """What the reference's multi-class evaluation (test_mc3serousv5.py `Results2Class.compareImages` :481-566, and for four
+    classes the counts and ratios of `Results3Class.compareImages` :218-255) records for each image of a batch, computed on
+    the device with ONE device-to-host copy.  `mask` uint8 (N,H,W) class values 0 .. n_classes - 1 (predict_mask's output, after
+    zoom_nearest if the sizes differ), `gt_dots` uint8 (N,H,W) whose value is the class of the dot.
+    label_class_components -> per-class centre lists; split_classes(gt_dots) -> per-class dot lists; Gaussian matching
+    (CrowdMatchingTest, inputType='Coordinates') and the 8 x 8 grid sums of the dot planes and of the maps with a 1 at every
+    centre (GMAE levels 1-3 over `size` pixels), each per (image, class).
+
+    Returns a list of N dicts.  d[c] for c in 1 .. n_classes - 1: 'GT' (dots of value c), 'Pred' (components of class c),
+    'AbsDiff', 'Accuracy', 'AccuracyRelative', 'AccuracyRelativePD' (CrowdMatching.countAccuracyMetric), 'G1', 'G2', 'G3'
+    (each [gmae, relative, relativePD], CrowdMatching.game_from_cells), 'arr_prec', 'arr_recall', 'arr_f1' ((S, T) float64).
+    For n_classes >= 3, d['ratio']: class 2 / (class 1 + class 2) of the ground truth and the prediction with the four metrics
+    (umi.matching.ratio_metrics, :499-501).  For n_classes == 4, d['ratio3']: Results3Class's three count accuracies and two
+    ratios with their 1e-6 smoothing (umi.matching.ratio3_metrics); the ground-truth counts there are the dot counts.
+
+    Every float is the reference's expression on Python ints.  Where the reference is undefined: a prediction without a
+    component of class 1 or 2 raises ZeroDivisionError, as the reference's ratio does; the reference's ground-truth counts are
+    numpy.uint64, so its abs(gt - pred) wraps to ~1.8e19 when the prediction is larger -- that is NOT reproduced, the
+    differences are those of ints; a ground truth without a dot of class 1 or 2 gives d['ratio']['GT'] = nan (the reference's
+    uint64 0 / 0).  More than max_components components in an image raises RuntimeError.
+
+    As on the binary path: 'Pred' is the number of 8-connected components (the reference's len(cv2.findContours(RETR_EXTERNAL))
+    may leave out a component inside a hole of another; OpenCV is not available, so that is not claimed); centres are pixel
+    centroids, not contour moments; Results3Class's cv2.minEnclosingCircle matching (:257-289) is not restated."""
+    from . import matching as M
+    if gt_dots.shape != mask.shape or mask.dim() != 3:
+        raise ValueError(f"score_multiclass_masks expects (N,H,W) masks and dot maps of one shape, got {tuple(mask.shape)} "
+                         f"{tuple(gt_dots.shape)}")
+    ops._need_cuda(mask, gt_dots)
+    N, H, W = mask.shape
+    K = int(n_classes)
+    cap = min(int(max_components), H * W)
+    (_, counts, class_counts, label_class, area, sum_y, sum_x), cc_fault = _label_class_components(mask, K, cap)
+    cc_fault = cc_fault.clone()
+    centers, c_count = M.class_center_lists(counts, label_class, area, sum_y, sum_x, K)
+    planes = M.split_classes(gt_dots, K).view(N * (K - 1), H, W)
+    dots, g_count, dot_fault = M.dot_lists(planes, _fault=True)
+    crowd = M.crowd_match(dots, g_count, centers, c_count, sigma_list, sigma_thresh_list)
+    cells_gt = M.grid_sums(planes, size)
+    cells_pred = M.grid_sums(M.scatter_centers(centers, c_count, H, W), size)
+    parts = (cc_fault, dot_fault, class_counts, g_count, c_count, crowd, cells_gt, cells_pred)
+    back = torch.cat([t.reshape(-1).to(torch.int64) for t in parts]).cpu().numpy()
+    _raise_on_class_fault(back[0], "score_multiclass_masks")
+    M.raise_on_dot_overflow(back[1])
+    host, at = [], 2
+    for t in parts[2:]:
+        host.append(back[at:at + t.numel()].reshape(t.shape))
+        at += t.numel()
+    return M.multiclass_scores(*host, K)

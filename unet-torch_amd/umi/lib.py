@@ -198,6 +198,13 @@ SIGNATURES = {
                                    c_void_p, c_size_t, c_void_p]),
     "umi_grid_sums": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
     "umi_scatter_centers": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_void_p]),
+    "umi_class_components_ws_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
+    "umi_count_class_components": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p]),
+    "umi_label_class_components": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
+                                           c_int, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p]),
+    "umi_split_classes": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
+    "umi_class_center_lists": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
+                                       c_void_p]),
 }
 
 for _name, (_res, _args) in SIGNATURES.items():

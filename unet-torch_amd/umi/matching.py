@@ -17,7 +17,9 @@ The reference's evaluation scripts (CrowdMatching.py) score a prediction three w
   grid_sums        the 8 x 8 grid of cell sums `GMAE` (:309-331) derives its three levels from.
 
 `dot_lists` turns dot maps into raster-ordered coordinate lists and `component_centers` turns `label_components`' statistics
-into centres.  Coordinate pairs are (x, y) throughout, the order of the reference's `(e_coord_x, e_coord_y)`.
+into centres.  For class-valued masks and dot maps (the reference's test_mc3serousv5.py) `split_classes` gives one 0/1 plane per
+class, `class_center_lists` one centre list per (image, class), and `multiclass_scores` forms the script's per-class and ratio
+metrics from the integers.  Coordinate pairs are (x, y) throughout, the order of the reference's `(e_coord_x, e_coord_y)`.
 
 Device tensors run the HIP kernels of csrc/matching.hip (batched, no host synchronisation, safe to capture in a graph once
 `match_tables` has been called for the sigma and threshold lists).  NumPy arrays run the `*_numpy` statements below, which
@@ -215,6 +217,108 @@ def level_sums(cells, L):
     return c.reshape(c.shape[:-2] + (1 << L, k, 1 << L, k)).sum(axis=(-3, -1))
 
 
+# ---- class-valued masks and dot maps (reference test_mc3serousv5.py Results2Class / Results3Class) -------------------------
+def split_classes_numpy(class_map, n_classes):
+    """(N,H,W) or (H,W) class-valued map -> uint8 (N, n_classes - 1, H, W): plane c - 1 is 1 where the map equals c."""
+    m, _ = _batched(class_map, 3)
+    return np.stack([(m == c).astype(np.uint8) for c in range(1, n_classes)], axis=1)
+
+
+def class_center_lists_numpy(counts, label_class, area, sum_y, sum_x, n_classes):
+    """label_class_components' statistics (rows of cap entries) -> centers int32 (N * (n_classes - 1), cap, 2) and c_count
+    int32 (N * (n_classes - 1),): per (image, class) the centres of that class's labels in label order, (0, 0) beyond."""
+    counts, label_class = np.asarray(counts).reshape(-1), np.asarray(label_class)
+    N, cap = label_class.shape
+    allc = component_centers_numpy(np.minimum(counts, cap), area, sum_y, sum_x)
+    centers = np.zeros((N * (n_classes - 1), cap, 2), dtype=np.int32)
+    c_count = np.zeros(N * (n_classes - 1), dtype=np.int32)
+    for n in range(N):
+        live = np.arange(cap) < counts[n]
+        for c in range(1, n_classes):
+            pick = np.flatnonzero(live & (label_class[n] == c))
+            j = n * (n_classes - 1) + c - 1
+            c_count[j] = pick.size
+            centers[j, :pick.size] = allc[n, pick]
+    return centers, c_count
+
+
+def ratio_metrics(cell_gt, immune_gt, cell_pred, immune_pred):
+    """The ratio block of the reference's Results2Class.compareImages (test_mc3serousv5.py:499-501, 518-523) on Python ints:
+    immune / (cell + immune) of the ground truth and of the prediction and countAccuracyMetric of the two.  A prediction
+    without a cell or immune object raises ZeroDivisionError as the reference does; a ground truth without either gives a
+    ratio of nan (the reference's numpy.uint64 0 / 0), and the metrics derived from it are whatever the reference's
+    expressions make of nan."""
+    import CrowdMatching as CM
+    cell_gt, immune_gt, cell_pred, immune_pred = int(cell_gt), int(immune_gt), int(cell_pred), int(immune_pred)
+    ratio_gt = immune_gt / (cell_gt + immune_gt) if cell_gt + immune_gt else float("nan")
+    ratio_pred = immune_pred / (cell_pred + immune_pred)
+    abs_diff, acc, rel, rel_pd = CM.countAccuracyMetric(ratio_gt, ratio_pred)
+    return {"GT": ratio_gt, "Pred": ratio_pred, "AbsDiff": round(abs_diff, 4), "Accuracy": acc, "AccuracyRelative": rel,
+            "AccuracyRelativePD": rel_pd}
+
+
+def ratio3_metrics(gt, pred, smooth=1e-6):
+    """The count accuracies and the two ratios of the reference's Results3Class.compareImages (test_mc3serousv5.py:226-228,
+    242-252) on Python ints; gt / pred = (cell, immune, tumor) counts = classes (1, 2, 3)."""
+    (cg, ig, tg), (cp, ip, tp) = (int(v) for v in gt), (int(v) for v in pred)
+    r_immo_gt, r_immo_pred = ig / (ig + tg + cg + smooth), ip / (ip + tp + cp + smooth)
+    r_it_gt, r_it_pred = ig / (ig + tg + smooth), ip / (ip + tp + smooth)
+    return {"cellAccuracy": round(abs(cg - cp) / (cg + smooth), 4), "immuneAccuracy": round(abs(ig - ip) / (ig + smooth), 4),
+            "tumorAccuracy": round(abs(tg - tp) / (tg + smooth), 4),
+            "GTImmo": r_immo_gt, "PredImmo": r_immo_pred, "AccuracyImmo": round(abs(r_immo_gt - r_immo_pred), 4),
+            "GTImmoTummor": r_it_gt, "PredImmoTummor": r_it_pred, "AccuracyImmoTummor": round(abs(r_it_gt - r_it_pred), 4)}
+
+
+def multiclass_scores(class_counts, g_count, c_count, crowd, cells_gt, cells_pred, n_classes):
+    """The host half of score_multiclass_masks: integers (class_counts (N, K), and per (image, class) row j = n * (K - 1) + c - 1
+    the dot count g_count[j], the centre count c_count[j], the matching result crowd[j] (S, T, 2) and the two 8 x 8 cell sums)
+    -> the list of N result dicts, every float formed by the reference's expressions on Python ints."""
+    import CrowdMatching as CM
+    K = int(n_classes)
+    class_counts = np.asarray(class_counts).reshape(-1, K)
+    out = []
+    for n in range(class_counts.shape[0]):
+        d = {}
+        for c in range(1, K):
+            j = n * (K - 1) + c - 1
+            gt, pred = int(g_count[j]), int(class_counts[n, c])
+            abs_diff, acc, rel, rel_pd = CM.countAccuracyMetric(gt, pred)
+            arr_prec, arr_recall, arr_f1 = CM.precision_recall_f1(crowd[j], gt, int(c_count[j]))
+            d[c] = {"GT": gt, "Pred": pred, "AbsDiff": abs_diff, "Accuracy": acc, "AccuracyRelative": rel,
+                    "AccuracyRelativePD": rel_pd,
+                    "G1": CM.game_from_cells(1, cells_gt[j], cells_pred[j]), "G2": CM.game_from_cells(2, cells_gt[j], cells_pred[j]),
+                    "G3": CM.game_from_cells(3, cells_gt[j], cells_pred[j]),
+                    "arr_prec": arr_prec, "arr_recall": arr_recall, "arr_f1": arr_f1}
+        if K >= 3:
+            d["ratio"] = ratio_metrics(d[1]["GT"], d[2]["GT"], d[1]["Pred"], d[2]["Pred"])
+        if K == 4:
+            d["ratio3"] = ratio3_metrics([d[c]["GT"] for c in (1, 2, 3)], [d[c]["Pred"] for c in (1, 2, 3)])
+        out.append(d)
+    return out
+
+
+def score_multiclass_numpy(mask, gt_dots, n_classes, sigma_list, sigma_thresh_list, size=512, max_components=65536):
+    """umi.infer.score_multiclass_masks on NumPy arrays, every step by the NumPy statements of this module and of
+    umi/components.py: `mask` (N,H,W) class values, `gt_dots` (N,H,W) map whose value is the class of the dot."""
+    from .components import label_class_components_numpy
+    mask, gt_dots = np.asarray(mask), np.asarray(gt_dots)
+    if mask.ndim != 3 or gt_dots.shape != mask.shape:
+        raise ValueError(f"expected (N,H,W) masks and dot maps of one shape, got {mask.shape} {gt_dots.shape}")
+    N, H, W = mask.shape
+    K = int(n_classes)
+    cap = min(int(max_components), H * W)
+    _, counts, class_counts, label_class, area, sum_y, sum_x = label_class_components_numpy(mask, K, cap)
+    if (counts > cap).any():
+        raise RuntimeError(f"score_multiclass_masks: an image has more than max_components = {cap} components")
+    centers, c_count = class_center_lists_numpy(counts, label_class, area, sum_y, sum_x, K)
+    planes = split_classes_numpy(gt_dots, K).reshape(N * (K - 1), H, W)
+    dots, g_count = dot_lists_numpy(planes)
+    crowd = crowd_match_numpy(dots, g_count, centers, c_count, sigma_list, sigma_thresh_list)
+    cells_gt = grid_sums_numpy(planes, size)
+    cells_pred = grid_sums_numpy(scatter_centers_numpy(centers, c_count, H, W), size)
+    return multiclass_scores(class_counts, g_count, c_count, crowd, cells_gt, cells_pred, K)
+
+
 # ---- device entries ------------------------------------------------------------------------------------------------------
 def _is_dev(x):
     import torch
@@ -390,3 +494,49 @@ def scatter_centers(centers, c_count, H, W):
     L.check(L.fn("umi_scatter_centers")(centers.data_ptr(), c_count.contiguous().data_ptr(), cap, out.data_ptr(), N, H, W,
                                         ops._stream()), "umi_scatter_centers")
     return out
+
+
+def split_classes(class_map, n_classes):
+    """uint8 (N, n_classes - 1, H, W) 0/1 planes of a class-valued uint8 (N,H,W) or (H,W) map, plane c - 1 = (map == c): the
+    reference's `gt_dot_other[gt_dot == 1] = 1`, `gt_dot_immune[gt_dot == 2] = 1` (test_mc3serousv5.py:482-485).  dot_lists and
+    grid_sums take the (N * (n_classes - 1), H, W) view."""
+    if not _is_dev(class_map):
+        return split_classes_numpy(_to_np(class_map), n_classes)
+    import torch
+    L, ops = _dev_modules()
+    if class_map.dim() not in (2, 3) or class_map.dtype != torch.uint8:
+        raise ValueError(f"split_classes expects a uint8 (N,H,W) or (H,W) map, got {tuple(class_map.shape)} {class_map.dtype}")
+    m = (class_map.unsqueeze(0) if class_map.dim() == 2 else class_map).contiguous()
+    N, H, W = m.shape
+    K = int(n_classes)
+    if not 2 <= K <= 256 or min(N, H, W) < 1 or N * (K - 1) * H * W >= 2 ** 31 or N > 65535:
+        raise ValueError(f"split_classes: unsupported shape {tuple(class_map.shape)} for {K} classes")
+    planes = torch.empty((N, K - 1, H, W), dtype=torch.uint8, device=m.device)
+    L.check(L.fn("umi_split_classes")(m.data_ptr(), planes.data_ptr(), N, H, W, K, ops._stream()), "umi_split_classes")
+    return planes
+
+
+def class_center_lists(counts, label_class, area, sum_y, sum_x, n_classes):
+    """Per (image, class 1 .. n_classes - 1) the centres of that class's components, from label_class_components' outputs:
+    centers int32 (N * (n_classes - 1), cap, 2) in label order (the raster order of first pixels within the class), (0, 0)
+    beyond the count, and c_count int32 (N * (n_classes - 1),) -- the layout crowd_match, distance_match and scatter_centers
+    take.  Centres are the pixel centroids of component_centers.  A fixed-order compaction: two runs give the same lists."""
+    if not _is_dev(area):
+        return class_center_lists_numpy(_to_np(counts), _to_np(label_class), _to_np(area), _to_np(sum_y), _to_np(sum_x), n_classes)
+    import torch
+    L, ops = _dev_modules()
+    if area.dim() != 2 or area.dtype != torch.int32 or counts.dtype != torch.int32 or label_class.dtype != torch.uint8 or \
+            sum_y.dtype != torch.int64 or sum_x.dtype != torch.int64 or sum_y.shape != area.shape or sum_x.shape != area.shape or \
+            label_class.shape != area.shape or counts.numel() != area.shape[0]:
+        raise ValueError("class_center_lists expects label_class_components' counts (N,), label_class uint8 (N,cap), area int32 "
+                         "(N,cap) and sum_y, sum_x int64 (N,cap)")
+    N, cap = area.shape
+    K = int(n_classes)
+    if not 2 <= K <= 256 or N * (K - 1) * cap >= 2 ** 30:
+        raise ValueError(f"class_center_lists: unsupported size N = {N}, cap = {cap}, {K} classes")
+    centers = torch.empty((N * (K - 1), cap, 2), dtype=torch.int32, device=area.device)
+    c_count = torch.empty(N * (K - 1), dtype=torch.int32, device=area.device)
+    L.check(L.fn("umi_class_center_lists")(counts.contiguous().data_ptr(), label_class.contiguous().data_ptr(),
+                                           area.contiguous().data_ptr(), sum_y.contiguous().data_ptr(), sum_x.contiguous().data_ptr(),
+                                           centers.data_ptr(), c_count.data_ptr(), N, cap, K, ops._stream()), "umi_class_center_lists")
+    return centers, c_count
