@@ -209,6 +209,7 @@ int umi_conv_wgrad_deferred(const void* x, int ldx, const void* txa, const void*
                             float* dW, long s_co, long s_ci, long s_t, float out_scale, int N, int H, int W, int Ci, int Co,
                             int R, int S, int stride, int pad, int Ho, int Wo, int dtype, int flags, void* ws, size_t ws_bytes,
                             umi_wgrad_pending* out, umi_stream_t stream);
+/* UMI_ERR_BADARG (nothing launched, no dW written) if ANY of the n entries has a null part / dW or splits, RS, Ci or Co <= 0. */
 int umi_wgrad_reduce_group(int n, const void* items /* umi_wgrad_pending[n], host */, umi_stream_t stream);
 /* Weight AND bias gradient of ConvTranspose2d(2,2) (reference Model.py:56-57 under autograd) in one pass over d(up): the arguments of
  * umi_conv_wgrad_deferred for that layer (x = d(up) [N,H,W,Ci], dy = the ConvT's input [N,Ho,Wo,Co] with its transform txb) plus

@@ -1144,6 +1144,10 @@ __global__ __launch_bounds__(256) void wgrad_reduce_group_kernel(WgTable t) {
 extern "C" int umi_wgrad_reduce_group(int n, const void* items, umi_stream_t stream) {
     if (n <= 0 || !items) return UMI_ERR_BADARG;
     const WgPending* it = (const WgPending*)items;
+    // the whole table before the first launch: a bad entry anywhere leaves every dW untouched (RS, Ci, Co divide in the
+    // kernel's index arithmetic and size its grid)
+    for (int i = 0; i < n; ++i)
+        if (!it[i].part || !it[i].dW || it[i].splits <= 0 || it[i].RS <= 0 || it[i].Ci <= 0 || it[i].Co <= 0) return UMI_ERR_BADARG;
     for (int g0 = 0; g0 < n; g0 += 16) {
         const int cnt = n - g0 < 16 ? n - g0 : 16;
         WgTable t;
@@ -1152,7 +1156,6 @@ extern "C" int umi_wgrad_reduce_group(int n, const void* items, umi_stream_t str
             t.e[i] = it[g0 + (i < cnt ? i : 0)];
             t.blk0[i] = total_blk;
             if (i >= cnt) continue;                              // (padding entries own no workgroups)
-            if (!t.e[i].part || !t.e[i].dW || t.e[i].splits <= 0) return UMI_ERR_BADARG;
             const bool vec = t.e[i].Co % 4 == 0 && (((uintptr_t)t.e[i].part) & 15) == 0;
             long g = ((long)t.e[i].RS * t.e[i].Ci * t.e[i].Co / (vec ? 4 : 1) + 31) / 32;
             if (wg_tmode(t.e[i])) g = (long)(t.e[i].Co / WGT_CO) * (t.e[i].Ci / WGT_CI);

@@ -729,12 +729,28 @@ def convT_wgrad_bias(g, y, txy, dW, dbias, out_scale, defer=None):
     return True
 
 
+def wgrad_pending(part, dW, s_co, s_ci, s_t, scale, splits, RS, Ci, Co):
+    """A umi_wgrad_pending record over caller-owned memory: `part` = splits slabs [RS][Ci][Co] of fp32, reduced into
+    dW[co*s_co + ci*s_ci + t*s_t] * scale.  `part` / `dW`: a tensor or a raw device address (the caller keeps them alive)."""
+    addr = [p.data_ptr() if torch.is_tensor(p) else p for p in (part, dW)]
+    return _WgPending(addr[0], addr[1], s_co, s_ci, s_t, scale, splits, RS, Ci, Co)
+
+
+def wgrad_reduce_group(pending, check=True):
+    """umi_wgrad_reduce_group over a sequence of umi_wgrad_pending records (16 per launch).  Returns the status; raises on a
+    non-zero one unless check=False."""
+    import ctypes
+    arr = (_WgPending * max(len(pending), 1))(*pending)
+    st = L.fn("umi_wgrad_reduce_group")(len(pending), ctypes.addressof(arr), _stream())
+    if check:
+        L.check(st, "umi_wgrad_reduce_group")
+    return st
+
+
 def wgrad_reduce_flush(defer):
     """Run the reductions recorded by conv_wgrad(defer=...) and empty the list."""
-    import ctypes
     if defer:
-        arr = (_WgPending * len(defer))(*[d[0] for d in defer])
-        L.check(L.fn("umi_wgrad_reduce_group")(len(defer), ctypes.addressof(arr), _stream()), "umi_wgrad_reduce_group")
+        wgrad_reduce_group([d[0] for d in defer])
         del defer[:]
 
 
