@@ -93,9 +93,15 @@ int umi_linear_fused(const void* x, int ldx, const void* wp8, const float* bias,
                      int epi, float p, unsigned seed, const unsigned* seed_dev, void* mask, const void* aux, int ldaux,
                      void* y2, int ldy2, int dtype, umi_stream_t stream);
 
-/* Which kernel umi_conv_fwd will take for this problem: *layout = 0 -> weights packed with umi_pack_kn,
- * 1 -> umi_pack_kn8 (MFMA path: fp16, 3x3, stride 1, pad 1, Ci%16==0, Co%64==0, no bias, 16-B aligned
- * rows); *stat_rows = rows of `stat_part` the call will write. */
+/* Which kernel umi_conv_fwd will take for this problem (the same selector answers both): *layout = 0 -> weights packed with
+ * umi_pack_kn, 1 -> umi_pack_kn8, for the two matrix-core kernels.  Both need fp16 in and out, ldx % 8 == ldy % 8 == 0 and no
+ * UMI_CONV_FORCE_GENERIC:
+ *   3x3:  R = S = 3, stride 1, pad 1, Ci % 16 == 0, Co % 8 == 0, no bias, no UMI_CONV_UPSAMPLE2 / UMI_CONV_DGRAD_STRIDED;
+ *   pointwise / tap-gather:  R = S = 1, stride 1, pad 0 with Ci, Co multiples of 8 and >= 16; or, with Ci % 64 == Co % 64 == 0
+ *         and R * S <= 49: stride >= 2, UMI_CONV_DGRAD_STRIDED, or UMI_CONV_UPSAMPLE2 with R = S = 2 -- as long as two source
+ *         images stay within 31-bit byte offsets (2 * H * W * ldx * 2 < 0x7FFFFFF0).  (It writes no statistics: umi_conv_fwd
+ *         with `stat_part` is UMI_ERR_UNSUPPORTED there.)
+ * *stat_rows = rows of `stat_part` the call will write.  UMI_ERR_UNSUPPORTED: UMI_CONV_ACCUMULATE off the pointwise kernel. */
 int umi_conv_fwd_plan(int N, int H, int W, int Ci, int Co, int R, int S, int stride, int pad,
                       int ldx, int ldy, int in_dtype, int out_dtype, int flags, int has_bias,
                       int* layout, int* stat_rows);
@@ -157,7 +163,8 @@ int umi_head_dgrad_bnred(const void* dl, int lddl, const void* wp, void* da, int
                          const void* txbn, const float* rstd, float* part, long P, int Ci, int Co, int dtype,
                          umi_stream_t stream);
 /* ... and the head's weight gradient from the same pass (its input is the activated ybn): dW[k * s_co + c * s_ci] <- out_scale *
- * sum_p tx(ybn[p][c]) * dl[p][k] (k < Ci logit channels, c < Co feature channels).  ws: umi_head_bwd_fused_ws_bytes. */
+ * sum_p tx(ybn[p][c]) * dl[p][k] (k < Ci logit channels, c < Co feature channels).  ws: umi_head_bwd_fused_ws_bytes.
+ * Co <= 256; UMI_ERR_UNSUPPORTED (nothing launched) above that or where umi_head_dgrad_bnred_rows is 0. */
 size_t umi_head_bwd_fused_ws_bytes(long P, int Ci, int Co);
 int umi_head_bwd_fused(const void* dl, int lddl, const void* wp, void* da, int ldda, const void* ybn, int ldybn,
                        const void* txbn, const float* rstd, float* part, float* dW, long s_co, long s_ci, float out_scale,

@@ -286,6 +286,7 @@ class _Conv:
         xd, dyd = x.to(dtype).to(DEV), dy.to(dtype).to(DEV)
         td = t.to(DEV) if use_tx else None
         self.RS, self.Ci, self.Co = R * R, Ci, Co
+        self.dev = (xd, td, dyd)
 
         def run(gw, defer=None):
             ops.conv_wgrad(xd, td, dyd, None, gw, Ci * R * R, R * R, 1, scale, R, R, stride, pad, flags=flags, defer=defer)
@@ -312,6 +313,7 @@ class _ConvT:
         F.conv_transpose2d(a, wr, br, stride=2).backward(dup.permute(0, 3, 1, 2).double())
         self.ref, self.ref_bias = wr.grad * scale, br.grad * scale
         xd, td, dupd = x.half().to(DEV), t.to(DEV), dup.half().to(DEV)
+        self.dev = (dupd, xd, td)                           # d(up), the ConvT's input, its transform
         self.RS, self.Ci, self.Co = 4, Cout, Cin            # the kernel's view: x = d(up), "dy" = the ConvT's input
         self.bias = []
 
@@ -384,6 +386,100 @@ def test_deferred_reduction_equals_immediate_on_the_256_thread_conv3x3_form():
     r = subprocess.run([sys.executable, "-c", code], env=dict(os.environ, UMI_WGRAD_CLASSIC="1"), cwd=REPO, capture_output=True,
                        text=True, timeout=300)
     assert r.returncode == 0 and "ran 3" in r.stdout, r.stdout[-2000:] + r.stderr[-4000:]
+
+
+# ---- (c') a refused call arms nothing: the sinks are arguments of that call alone ------------------------------------------------
+WORKSPACE = -3               # UMI_ERR_WORKSPACE
+
+
+def test_a_failed_deferred_call_leaves_nothing_armed():
+    """umi_conv_wgrad_deferred with a workspace four bytes short: refused before any launch, nothing recorded, dW untouched --
+    and the next, immediate call on this thread reduces at once into its own dW."""
+    import ctypes
+    lib, ops = _gpu()
+    p = _paths(lib)["head"]().build(ops, seed=500)
+    N, H, W, Ci, Co, R, stride, pad, _, scale, _, flags = p.args
+    xd, td, dyd = p.dev
+    nb = lib.fn("umi_conv_wgrad_ws_bytes")(N, H, W, Ci, Co, R, R, lib.UMI_F16, flags)
+    ws = torch.empty(nb, dtype=torch.uint8, device=DEV)
+    gw = p.new(SENTINEL)
+    pend = ops.wgrad_pending(ws, gw, 1, 1, 1, 1.0, 1, 1, 1, 1)           # stale contents: the call must clear `part`
+    st = lib.fn("umi_conv_wgrad_deferred")(xd.data_ptr(), Ci, td.data_ptr(), dyd.data_ptr(), Co, None, gw.data_ptr(), Ci * R * R, R * R,
+                                           1, scale, N, H, W, Ci, Co, R, R, stride, pad, H, W, lib.UMI_F16, flags, ws.data_ptr(),
+                                           nb - 4, ctypes.addressof(pend), ops._stream())
+    torch.cuda.synchronize()
+    assert st == WORKSPACE and not pend.part
+    assert (gw == SENTINEL).all()
+    p.run(gw)                                                            # immediate
+    torch.cuda.synchronize()
+    assert torch.equal(gw.cpu().double(), p.ref)
+
+
+def test_a_failed_bias_call_leaves_no_bias_sink_armed():
+    """The same for umi_conv_wgrad_bias: refused for its workspace, dbias untouched; the plain weight gradient of the same
+    2x2 / stride-2 problem that follows gives the reference dW and writes no bias gradient anywhere near that buffer."""
+    lib, ops = _gpu()
+    p = _paths(lib)["convT"]().build(ops, seed=501)
+    N, h, w, Cin, Cout, scale = p.args
+    dupd, xd, td = p.dev
+    Ci, Co = Cout, Cin                                                   # the kernel's view: x = d(up), dy = the ConvT's input
+    nb = lib.fn("umi_conv_wgrad_ws_bytes")(N, h, w, Ci, Co, 2, 2, lib.UMI_F16, 0)
+    ws = torch.empty(nb, dtype=torch.uint8, device=DEV)
+    gw = p.new(SENTINEL)
+    dbias = torch.full((GUARD + Ci + GUARD,), float("nan"), device=DEV)
+    st = lib.fn("umi_conv_wgrad_bias")(dupd.data_ptr(), Ci, xd.data_ptr(), Co, td.data_ptr(), gw.data_ptr(), Ci * 4, 4, 1,
+                                       dbias.data_ptr() + 4 * GUARD, scale, N, 2 * h, 2 * w, Ci, Co, h, w, lib.UMI_F16, 0,
+                                       ws.data_ptr(), nb - 4, None, ops._stream())
+    torch.cuda.synchronize()
+    assert st == WORKSPACE
+    assert torch.isnan(dbias).all() and (gw == SENTINEL).all()
+    ops.conv_wgrad(dupd, None, xd, td, gw, Ci * 4, 4, 1, scale, 2, 2, 2, 0)
+    torch.cuda.synchronize()
+    assert torch.equal(gw.cpu().double(), p.ref)
+    assert torch.isnan(dbias).all()
+
+
+def _head_fused(ops, C, seed):
+    """OutConv's fused backward (ops.head_dgrad_bnred with dW) on a 1x8x8 map, 2 logit channels, C feature channels, integer data.
+    Returns the partial rows (None: refused), da, dW, the float64 dW and the device operands."""
+    g = torch.Generator().manual_seed(seed)
+    y = _ints((1, 8, 8, C), -2, 2, g)                                    # the BatchNorm layer's raw output
+    t = _int_tx(C, g)
+    dl = _ints((1, 8, 8, 2), -1, 1, g)
+    wo = _ints((2, C, 1, 1), -1, 1, g)
+    ref = torch.einsum("nhwc,nhwk->kc", _apply(y, t).double(), dl.double()).reshape(2, C, 1, 1) * 0.5
+    dev = (dl.half().to(DEV), ops.pack_conv_dgrad(wo.to(DEV), torch.float16, k8=False), y.half().to(DEV), t.to(DEV),
+           torch.ones(C, device=DEV))
+    da = torch.full((1, 8, 8, C), SENTINEL, device=DEV, dtype=torch.float16)
+    gw = torch.full((2, C, 1, 1), SENTINEL, device=DEV)
+    part = ops.head_dgrad_bnred(dev[0], dev[1], da, dev[2], dev[3], dev[4], dW=gw, out_scale=0.5)
+    torch.cuda.synchronize()
+    return part, da, gw, ref, dev
+
+
+def test_head_fusion_at_the_channel_limit():
+    """The fused kernel keeps a workgroup's weight-gradient rows in LDS, 256 feature channels at the most: above that the call
+    is refused as unsupported before anything is launched (the caller runs the separate kernels), at the limit it runs."""
+    lib, ops = _gpu()
+    C = 512
+    part, da, gw, _, (dl, wp, y, t, rstd) = _head_fused(ops, C, seed=502)
+    assert part is None
+    assert (da == SENTINEL).all() and (gw == SENTINEL).all()
+    # the C call itself, with partial rows of our own: unsupported, and they stay untouched too
+    rows = lib.fn("umi_head_dgrad_bnred_rows")(64, 2, C, C, lib.UMI_F16)
+    assert rows > 0
+    rows_buf = torch.full((rows * 2 * C,), SENTINEL, device=DEV)
+    ws = torch.empty(max(lib.fn("umi_head_bwd_fused_ws_bytes")(64, 2, C), 16), dtype=torch.uint8, device=DEV)
+    st = lib.fn("umi_head_bwd_fused")(dl.data_ptr(), 2, wp.data_ptr(), da.data_ptr(), C, y.data_ptr(), C, t.data_ptr(), rstd.data_ptr(),
+                                      rows_buf.data_ptr(), gw.data_ptr(), C, 1, 0.5, ws.data_ptr(), ws.numel(), 64, 2, C, lib.UMI_F16,
+                                      ops._stream())
+    torch.cuda.synchronize()
+    assert st == -2                                                      # UMI_ERR_UNSUPPORTED
+    assert (rows_buf == SENTINEL).all() and (da == SENTINEL).all() and (gw == SENTINEL).all()
+    part, da, gw, ref, _ = _head_fused(ops, 256, seed=503)
+    assert part is not None and part.numel() % (2 * 256) == 0 and torch.isfinite(part).all()
+    assert torch.equal(gw.cpu().double(), ref)
+    assert not (da == SENTINEL).any()
 
 
 # ---- (d) model level: the A/B knob ------------------------------------------------------------------------------------------------

@@ -1,105 +1,17 @@
 // C-ABI dispatch layer of libunetmi: validates arguments and picks the MFMA fast path or the
 // generic kernel.  See include/unetmi.h for the contract of every entry point.
-#include "common.h"
+#include "kernels.h"
 #include <stdio.h>
 #include <stdlib.h>
 
-// generic_kernels.hip
-int umi_conv_fwd_generic(const void* x, int ldx, const void* tx, const void* wp, const float* bias, void* y, int ldy,
-                         float* stat_part, int N, int H, int W, int Ci, int Co, int R, int S, int stride, int pad,
-                         int Ho, int Wo, int off_h, int off_w, int out_H, int out_W, int in_dtype, int out_dtype,
-                         int flags, hipStream_t s);
-size_t umi_conv_wgrad_generic_ws_bytes(int N, int Ho, int Wo, int Ci, int Co, int R, int S);
-int umi_conv_wgrad_generic(const void* x, int ldx, const void* txa, const void* dy, int lddy, const void* txb, float* dW,
-                           long s_co, long s_ci, long s_t, float out_scale, int N, int H, int W, int Ci, int Co, int R,
-                           int S, int stride, int pad, int Ho, int Wo, int dtype, void* ws, size_t ws_bytes,
-                           hipStream_t st);
-// conv_mfma.hip
-bool umi_conv3x3_mfma_ok(int N, int H, int W, int Ci, int Co, int R, int S, int stride, int pad, int Ho, int Wo,
-                         int ldx, int ldy, int in_dtype, int out_dtype, int flags, const float* bias);
-int umi_conv3x3_mfma_stat_rows(int N, int Ho, int Wo, int Ci, int Co, int ldx);
-int umi_conv3x3_mfma(const void* x, int ldx, const void* tx, const void* wp8, void* y, int ldy, float* stat_part,
-                     int N, int H, int W, int Ci, int Co, hipStream_t s);
-// conv1x1_mfma.hip
-bool umi_conv1x1_mfma_ok(int Ci, int Co, int R, int S, int stride, int pad, int ldx, int ldy, int in_dtype,
-                         int out_dtype, int flags);
-struct UmiLinearEpi { int mode; float p; unsigned seed; const unsigned* seed_dev; void* mask; const void* aux; int ldaux; void* y2; int ldy2;
-                      const void* bn_tx; const float* bn_rstd; float* bn_part; };
-int umi_conv1x1_bnred_rows(long M, int Ntot);
-int umi_conv1x1_mfma(const void* x, int ldx, const void* tx, const void* wp8, const float* bias, void* y, int ldy,
-                     int N, int H, int W, int Ci, int Co, int R, int S, int stride, int pad, int Ho, int Wo, int off_h,
-                     int off_w, int out_H, int out_W, int flags, hipStream_t s, const UmiLinearEpi* epi = nullptr);
-// stem_head.hip
-bool umi_stem_fwd_ok(int Ci, int Co, int R, int S, int stride, int pad, int ldy, int in_dtype, int out_dtype, int flags,
-                     const float* bias);
-int umi_stem_stat_rows(int N, int H, int W);
-int umi_stem_fwd(const void* x, int ldx, const void* tx, const void* wp, void* y, int ldy, float* part, int N, int H, int W,
-                 int Ci, int Co, hipStream_t s);
-bool umi_stem_wgrad_ok(int Ci, int Co, int R, int S, int stride, int pad, int lddy, int dtype, int flags, const void* txb);
-size_t umi_stem_wgrad_ws_bytes(int N, int H, int W, int Ci, int Co);
-int umi_stem_wgrad_bnapply(const void* x, int ldx, const void* txa, const void* da, int ldda, const void* y, int ldy,
-                           const void* tx_bn, const float* rstd, const float* sum_dz, const float* sum_dzx, float* dW, long s_co,
-                           long s_ci, long s_t, float out_scale, int N, int H, int W, int Ci, int Co, void* ws, size_t ws_bytes,
-                           hipStream_t s);
-int umi_stem_wgrad(const void* x, int ldx, const void* txa, const void* dy, int lddy, float* dW, long s_co, long s_ci,
-                   long s_t, float out_scale, int N, int H, int W, int Ci, int Co, void* ws, size_t ws_bytes, hipStream_t s);
-bool umi_head_fwd_ok(int Ci, int Co, int R, int S, int stride, int pad, int ldx, int in_dtype, int out_dtype, int flags);
-int umi_head_fwd(const void* x, int ldx, const void* tx, const void* wp, const float* bias, void* y, int ldy, float* part,
-                 long P, int Ci, int Co, int out_dtype, hipStream_t s);
-int umi_head_stat_rows(long P, int Ci);
-bool umi_smallk_fwd_ok(int Ci, int Co, int R, int S, int stride, int pad, int ldy, int in_dtype, int out_dtype, int flags,
-                       const void* tx, const float* bias);
-int umi_smallk_fwd(const void* x, int ldx, const void* wp, void* y, int ldy, long P, int Ci, int Co, hipStream_t s);
-bool umi_head_wgrad_ok(int Ci, int Co, int R, int S, int stride, int pad, int ldx, int dtype, int flags, const void* txb);
-size_t umi_head_wgrad_ws_bytes(long P, int Ci, int Co);
-int umi_head_wgrad(const void* x, int ldx, const void* txa, const void* dy, int lddy, float* dW, long s_co, long s_ci,
-                   long s_t, float out_scale, long P, int Ci, int Co, void* ws, size_t ws_bytes, hipStream_t s);
-bool umi_wgrad1x1_mfma_ok(long M, int Ci, int Co, int R, int S, int stride, int pad, int ldx, int lddy, int dtype, int flags,
-                          const void* txb);
-size_t umi_wgrad1x1_mfma_ws_bytes(long M, int Ci, int Co);
-int umi_wgrad1x1_mfma(const void* x, int ldx, const void* txa, const void* dy, int lddy, float* dW, long s_co, long s_ci,
-                      long s_t, float out_scale, long M, int Ci, int Co, void* ws, size_t ws_bytes, hipStream_t s);
-bool umi_wgradT_mfma_ok(int H, int W, int Ci, int Co, int R, int S, int stride, int pad, int Ho, int Wo, int ldx,
-                        int lddy, int dtype, int flags, const void* txa);
-size_t umi_wgradT_mfma_ws_bytes(int N, int Ho, int Wo, int Ci, int Co);
-int umi_wgradT_mfma(const void* x, int ldx, const void* dy, int lddy, const void* txb, float* dW, long s_co, long s_ci,
-                    long s_t, float out_scale, int N, int Ho, int Wo, int Ci, int Co, void* ws, size_t ws_bytes,
-                    hipStream_t s);
-// narrow_convs.hip
-bool umi_root_fwd_ok(int Ci, int Co, int R, int S, int stride, int pad, int ldy, int in_dtype, int out_dtype, int flags,
-                     const void* tx, const float* bias);
-int umi_root_fwd(const void* x, int ldx, const void* wp, void* y, int ldy, int N, int H, int W, int Ho, int Wo, int Co,
-                 hipStream_t s);
-bool umi_root_wgrad_ok(int Ci, int Co, int R, int S, int stride, int pad, int lddy, int dtype, int flags, const void* txa,
-                       const void* txb);
-size_t umi_root_wgrad_ws_bytes(int N, int Ho, int Wo, int Co);
-int umi_root_wgrad(const void* x, int ldx, const void* dy, int lddy, float* dW, long s_co, long s_ci, long s_t, float out_scale,
-                   int N, int H, int W, int Ho, int Wo, int Co, void* ws, size_t ws_bytes, hipStream_t s);
-bool umi_head3_fwd_ok(int Ci, int Co, int R, int S, int stride, int pad, int ldx, int in_dtype, int out_dtype, int flags);
-int umi_head3_fwd(const void* x, int ldx, const void* tx, const void* wp, const float* bias, void* y, int ldy, int N, int H,
-                  int W, int Ci, int Co, hipStream_t s);
-bool umi_head3_wgrad_ok(int Ci, int Co, int R, int S, int stride, int pad, int ldx, int dtype, int flags, const void* txb);
-size_t umi_head3_wgrad_ws_bytes(long P, int Ci, int Co);
-int umi_head3_wgrad(const void* x, int ldx, const void* txa, const void* dy, int lddy, float* dW, long s_co, long s_ci, long s_t,
-                    float out_scale, int N, int H, int W, int Ci, int Co, void* ws, size_t ws_bytes, hipStream_t s);
-bool umi_wgrad_gather_mfma_ok(int N, int H, int W, int Ci, int Co, int R, int S, int stride, int pad, int Ho, int Wo, int ldx,
-                              int lddy, int dtype, int flags, const void* txb);
-size_t umi_wgrad_gather_mfma_ws_bytes(int N, int Ho, int Wo, int Ci, int Co, int R, int S);
-int umi_wgrad_gather_mfma(const void* x, int ldx, const void* txa, const void* dy, int lddy, float* dW, long s_co, long s_ci,
-                          long s_t, float out_scale, int N, int H, int W, int Ci, int Co, int R, int S, int stride, int pad,
-                          int Ho, int Wo, void* ws, size_t ws_bytes, hipStream_t s);
-bool umi_wgrad3x3_mfma_ok(int N, int H, int W, int Ci, int Co, int R, int S, int stride, int pad, int Ho, int Wo,
-                          int ldx, int lddy, int dtype, int flags, const void* txb);
-size_t umi_wgrad3x3_mfma_ws_bytes(int N, int H, int W, int Ci, int Co);
-int umi_wgrad1x1_mfma_group(int n, const void* const* x, int ldx, const void* const* dy, int lddy, float* const* dW, long s_co,
-                            long s_ci, float out_scale, long M, int Ci, int Co, hipStream_t s);
-int umi_wgrad3x3_mfma_bnapply(const void* x, int ldx, const void* txa, const void* da, int ldda, const void* ybn, int ldybn,
-                              const void* txbn, const float* rstd, const float* sum_dz, const float* sum_dzx, void* dz,
-                              int lddz, float* dW, long s_co, long s_ci, long s_t, float out_scale, int N, int H, int W, int Ci,
-                              int Co, void* ws, size_t ws_bytes, hipStream_t s);
-int umi_wgrad3x3_mfma(const void* x, int ldx, const void* txa, const void* dy, int lddy, float* dW, long s_co,
-                      long s_ci, long s_t, float out_scale, int N, int H, int W, int Ci, int Co, void* ws,
-                      size_t ws_bytes, hipStream_t s);
+static ConvFwdProblem fwd_problem(int N, int H, int W, int Ci, int Co, int R, int S, int stride, int pad, int Ho, int Wo, int ldx,
+                                  int ldy, int in_dtype, int out_dtype, int flags, bool has_tx, bool has_bias, bool has_stats) {
+    return ConvFwdProblem{N, H, W, Ci, Co, R, S, stride, pad, Ho, Wo, ldx, ldy, in_dtype, out_dtype, flags, has_tx, has_bias, has_stats};
+}
+// a 3x3 / stride 1 / pad 1 problem without bias or statistics: "is this on the 3x3 matrix-core kernel"
+static ConvFwdProblem fwd_problem_3x3(int N, int H, int W, int Ci, int Co, int ldx, int ldy, int dtype, bool has_tx) {
+    return fwd_problem(N, H, W, Ci, Co, 3, 3, 1, 1, H, W, ldx, ldy, dtype, dtype, 0, has_tx, false, false);
+}
 
 extern "C" int umi_version(void) { return 1; }
 extern "C" const char* umi_arch(void) { return "gfx950"; }
@@ -116,11 +28,11 @@ extern "C" int umi_linear_fused(const void* x, int ldx, const void* wp8, const f
     if (!x || !wp8 || !y || !mask || M <= 0 || M >= (1L << 31) || Ci <= 0 || Co <= 0 || p < 0.f || p >= 1.f) return UMI_ERR_BADARG;
     if (epi != 1 && epi != 2) return UMI_ERR_BADARG;
     if ((epi == 1 && (!y2 || ldy2 % 8)) || (epi == 2 && (!aux || ldaux % 8))) return UMI_ERR_BADARG;
-    if (dtype != UMI_F16 || !umi_conv1x1_mfma_ok(Ci, Co, 1, 1, 1, 0, ldx, ldy, UMI_F16, UMI_F16, 0)) return UMI_ERR_UNSUPPORTED;
+    const ConvFwdProblem pr = fwd_problem(1, 1, (int)M, Ci, Co, 1, 1, 1, 0, 1, (int)M, ldx, ldy, dtype, dtype, 0, false, bias != nullptr, false);
+    if (umi_conv_fwd_path(pr) != FWD_MFMA1X1) return UMI_ERR_UNSUPPORTED;
     if (((uintptr_t)x | (uintptr_t)y | (uintptr_t)wp8 | (uintptr_t)y2 | (uintptr_t)aux) & 15 || ((uintptr_t)mask & 7)) return UMI_ERR_UNSUPPORTED;
     const UmiLinearEpi e{epi, p, seed, seed_dev, mask, aux, ldaux, y2, ldy2, nullptr, nullptr, nullptr};
-    return umi_conv1x1_mfma(x, ldx, nullptr, wp8, bias, y, ldy, 1, 1, (int)M, Ci, Co, 1, 1, 1, 0, 1, (int)M, 0, 0, 1, (int)M, 0,
-                            (hipStream_t)stream, &e);
+    return umi_conv1x1_mfma(pr, x, nullptr, wp8, bias, y, 0, 0, 1, (int)M, (hipStream_t)stream, &e);
 }
 
 // A data gradient on the pointwise / tap-gather matrix-core kernel (ConvTranspose2d(2,2)'s = a stride-2 2x2 conv over d(up),
@@ -130,8 +42,9 @@ extern "C" int umi_linear_fused(const void* x, int ldx, const void* wp8, const f
 extern "C" int umi_conv_gather_bnred_rows(int N, int H, int W, int Ci, int Co, int R, int S, int stride, int pad, int Ho, int Wo,
                                           int ldx, int ldy, int dtype, int flags) {
     if (flags & (UMI_CONV_UPSAMPLE2 | UMI_CONV_ACCUMULATE | UMI_CONV_FORCE_GENERIC)) return 0;
-    if (umi_conv3x3_mfma_ok(N, H, W, Ci, Co, R, S, stride, pad, Ho, Wo, ldx, ldy, dtype, dtype, flags, nullptr)) return 0;
-    if (!umi_conv1x1_mfma_ok(Ci, Co, R, S, stride, pad, ldx, ldy, dtype, dtype, flags)) return 0;
+    const ConvFwdProblem p = fwd_problem(N, H, W, Ci, Co, R, S, stride, pad, Ho, Wo, ldx, ldy, dtype, dtype, flags, false, false, false);
+    // (a 3x3 / stride-1 data gradient has umi_conv_dgrad_bnred, with UMI_CONV_DGRAD_STRIDED set as without)
+    if (umi_conv_fwd_path(p) != FWD_MFMA1X1 || umi_conv3x3_mfma_ok(p)) return 0;
     return umi_conv1x1_bnred_rows((long)N * Ho * Wo, Co);
 }
 extern "C" int umi_conv_gather_bnred(const void* x, int ldx, const void* wp8, void* y, int ldy, const void* ybn, int ldybn,
@@ -142,8 +55,8 @@ extern "C" int umi_conv_gather_bnred(const void* x, int ldx, const void* wp8, vo
         return UMI_ERR_UNSUPPORTED;
     if (((uintptr_t)x | (uintptr_t)y | (uintptr_t)wp8 | (uintptr_t)ybn) & 15) return UMI_ERR_BADARG;
     const UmiLinearEpi e{3, 0.f, 0u, nullptr, nullptr, ybn, ldybn, nullptr, 0, txbn, rstd, part};
-    return umi_conv1x1_mfma(x, ldx, nullptr, wp8, nullptr, y, ldy, N, H, W, Ci, Co, R, S, stride, pad, Ho, Wo, 0, 0, Ho, Wo, flags,
-                            (hipStream_t)stream, &e);
+    const ConvFwdProblem p = fwd_problem(N, H, W, Ci, Co, R, S, stride, pad, Ho, Wo, ldx, ldy, dtype, dtype, flags, false, false, false);
+    return umi_conv1x1_mfma(p, x, nullptr, wp8, nullptr, y, 0, 0, Ho, Wo, (hipStream_t)stream, &e);
 }
 
 extern "C" int umi_conv_fwd_plan(int N, int H, int W, int Ci, int Co, int R, int S, int stride, int pad, int ldx,
@@ -152,28 +65,19 @@ extern "C" int umi_conv_fwd_plan(int N, int H, int W, int Ci, int Co, int R, int
     if (N <= 0 || H <= 0 || W <= 0 || Ci <= 0 || Co <= 0 || R <= 0 || S <= 0 || stride <= 0) return UMI_ERR_BADARG;
     const bool ups = flags & UMI_CONV_UPSAMPLE2;
     const int Ho = ups ? H : (H + 2 * pad - R) / stride + 1, Wo = ups ? W : (W + 2 * pad - S) / stride + 1;
-    static const float one = 1.f;
-    const bool dgs = flags & UMI_CONV_DGRAD_STRIDED;      // only the tap-gather MFMA kernel or the generic one take these
-    const bool mfma = !dgs && umi_conv3x3_mfma_ok(N, H, W, Ci, Co, R, S, stride, pad, Ho, Wo, ldx, ldy, in_dtype, out_dtype,
-                                                  flags, has_bias ? &one : nullptr);
-    const bool mfma1 = !mfma && umi_conv1x1_mfma_ok(Ci, Co, R, S, stride, pad, ldx, ldy, in_dtype, out_dtype, flags);
-    if ((flags & UMI_CONV_ACCUMULATE) && !mfma1) return UMI_ERR_UNSUPPORTED;
-    if (layout) *layout = (mfma || mfma1) ? 1 : 0;
-    const bool stem = !mfma && !mfma1 && !dgs &&
-                      umi_stem_fwd_ok(Ci, Co, R, S, stride, pad, ldy, in_dtype, out_dtype, flags, has_bias ? &one : nullptr);
-    const bool head = !mfma && !mfma1 && !dgs && !stem && out_dtype == UMI_F16 &&
-                      umi_head_fwd_ok(Ci, Co, R, S, stride, pad, ldx, in_dtype, out_dtype, flags);
+    // the plan is asked before the call's pointers exist: it answers for a call that wants statistics (the rows are only read
+    // then; the packing does not depend on it)
+    const ConvFwdPath path = umi_conv_fwd_path(fwd_problem(N, H, W, Ci, Co, R, S, stride, pad, Ho, Wo, ldx, ldy, in_dtype, out_dtype,
+                                                           flags, false, has_bias != 0, true));
+    if ((flags & UMI_CONV_ACCUMULATE) && path != FWD_MFMA1X1) return UMI_ERR_UNSUPPORTED;
+    if (layout) *layout = (path == FWD_MFMA3X3 || path == FWD_MFMA1X1) ? 1 : 0;
     if (stat_rows)
-        *stat_rows = mfma ? umi_conv3x3_mfma_stat_rows(N, H, W, Ci, Co, ldx)
-                          : (stem ? umi_stem_stat_rows(N, H, W)
-                                  : (head ? umi_head_stat_rows((long)N * H * W, Ci) : umi_cdiv((long)N * Ho * Wo, 64)));
+        *stat_rows = path == FWD_MFMA3X3 ? umi_conv3x3_mfma_stat_rows(N, H, W, Co)
+                     : path == FWD_STEM  ? umi_stem_stat_rows(N, H, W)
+                     : path == FWD_HEAD  ? umi_head_stat_rows((long)N * H * W, Ci)
+                                         : umi_cdiv((long)N * Ho * Wo, 64);
     return UMI_OK;
 }
-
-int umi_conv3x3_mfma_bnred(const void* dy, int lddy, const void* wp8, void* da, int ldda, const void* ybn, int ldybn,
-                           const void* txbn, const float* rstd, float* part, int N, int H, int W, int Ci, int Co,
-                           hipStream_t s);
-void umi_launch_reduce_rows2(const float* ws, int rows, int C, float* out0, float* out1, float scale, hipStream_t s);
 
 // 3x3 / stride 1 / pad 1 data gradient (x = dy, Ci = the forward conv's Co, weights rotated + transposed as for umi_conv_fwd)
 // fused with stage 1 of the BatchNorm+ReLU backward of the layer whose activated output the gradient belongs to:
@@ -183,30 +87,27 @@ extern "C" int umi_conv_dgrad_bnred(const void* dy, int lddy, const void* wp8, v
                                     const void* txbn, const float* rstd, float* part, int N, int H, int W, int Ci, int Co,
                                     int dtype, umi_stream_t stream) {
     if (!dy || !wp8 || !da || !ybn || !txbn || !rstd || !part || N <= 0 || H <= 0 || W <= 0) return UMI_ERR_BADARG;
-    if (!umi_conv3x3_mfma_ok(N, H, W, Ci, Co, 3, 3, 1, 1, H, W, lddy, ldda, dtype, dtype, 0, nullptr) || ldybn % 8 || ldybn < Co)
-        return UMI_ERR_UNSUPPORTED;
+    const ConvFwdProblem p = fwd_problem_3x3(N, H, W, Ci, Co, lddy, ldda, dtype, false);
+    if (umi_conv_fwd_path(p) != FWD_MFMA3X3 || ldybn % 8 || ldybn < Co) return UMI_ERR_UNSUPPORTED;
     if (((uintptr_t)dy | (uintptr_t)da | (uintptr_t)wp8 | (uintptr_t)ybn) & 15) return UMI_ERR_BADARG;
-    return umi_conv3x3_mfma_bnred(dy, lddy, wp8, da, ldda, ybn, ldybn, txbn, rstd, part, N, H, W, Ci, Co, (hipStream_t)stream);
+    return umi_conv3x3_mfma_bnred(p, dy, wp8, da, ybn, ldybn, txbn, rstd, part, (hipStream_t)stream);
 }
-
-int umi_smallk_bnred_rows(long P, int Co);
-int umi_smallk_fwd_bnred(const void* x, int ldx, const void* wp, void* y, int ldy, const void* ybn, int ldybn, const void* txbn,
-                         const float* rstd, float* part, long P, int Ci, int Co, hipStream_t s, float* dW = nullptr, long s_co = 0,
-                         long s_ci = 0, float out_scale = 1.f, void* ws = nullptr, size_t ws_bytes = 0);
 
 // The same fusion for the data gradient of a narrow pointwise conv (the segmentation head `OutConv`, reference Model.py:89-93:
 // Ci <= 8 logit channels -> Co feature channels): da = dl * W^T plus stage 1 of the BatchNorm+ReLU backward of the layer whose
 // activated output feeds the head.  rows = umi_head_dgrad_bnred_rows(P, Co).  wp = the generic [1][Ci][Co] fp16 packing.
+static bool head_dgrad_ok(int Ci, int Co, int ldda, int dtype) {       // (the predicate reads no pixel counts and no ldx)
+    return umi_smallk_fwd_ok(fwd_problem(1, 1, 1, Ci, Co, 1, 1, 1, 0, 1, 1, Ci, ldda, dtype, dtype, 0, false, false, false));
+}
 extern "C" int umi_head_dgrad_bnred_rows(long P, int Ci, int Co, int ldda, int dtype) {
-    if (!umi_smallk_fwd_ok(Ci, Co, 1, 1, 1, 0, ldda, dtype, dtype, 0, nullptr, nullptr)) return 0;
+    if (!head_dgrad_ok(Ci, Co, ldda, dtype)) return 0;
     return umi_smallk_bnred_rows(P, Co);
 }
 extern "C" int umi_head_dgrad_bnred(const void* dl, int lddl, const void* wp, void* da, int ldda, const void* ybn, int ldybn,
                                     const void* txbn, const float* rstd, float* part, long P, int Ci, int Co, int dtype,
                                     umi_stream_t stream) {
     if (!dl || !wp || !da || !ybn || !txbn || !rstd || !part || P <= 0) return UMI_ERR_BADARG;
-    if (!umi_smallk_fwd_ok(Ci, Co, 1, 1, 1, 0, ldda, dtype, dtype, 0, nullptr, nullptr) || ldybn % 8 || ldybn < Co || lddl < Ci)
-        return UMI_ERR_UNSUPPORTED;
+    if (!head_dgrad_ok(Ci, Co, ldda, dtype) || ldybn % 8 || ldybn < Co || lddl < Ci) return UMI_ERR_UNSUPPORTED;
     return umi_smallk_fwd_bnred(dl, lddl, wp, da, ldda, ybn, ldybn, txbn, rstd, part, P, Ci, Co, (hipStream_t)stream);
 }
 // ... and the head's WEIGHT gradient as well (reference Model.py:89-93 under autograd: dW[k][c] = sum_p act(ybn)[p][c] * dl[p][k]; the
@@ -218,14 +119,11 @@ extern "C" int umi_head_bwd_fused(const void* dl, int lddl, const void* wp, void
                                   const void* txbn, const float* rstd, float* part, float* dW, long s_co, long s_ci, float out_scale,
                                   void* ws, size_t ws_bytes, long P, int Ci, int Co, int dtype, umi_stream_t stream) {
     if (!dl || !wp || !da || !ybn || !txbn || !rstd || !part || !dW || !ws || P <= 0) return UMI_ERR_BADARG;
-    if (!umi_smallk_fwd_ok(Ci, Co, 1, 1, 1, 0, ldda, dtype, dtype, 0, nullptr, nullptr) || ldybn % 8 || ldybn < Co || lddl < Ci)
-        return UMI_ERR_UNSUPPORTED;
+    // (Co > 256: the weight-gradient rows of a workgroup no longer fit its LDS)
+    if (!head_dgrad_ok(Ci, Co, ldda, dtype) || Co > 256 || ldybn % 8 || ldybn < Co || lddl < Ci) return UMI_ERR_UNSUPPORTED;
     return umi_smallk_fwd_bnred(dl, lddl, wp, da, ldda, ybn, ldybn, txbn, rstd, part, P, Ci, Co, (hipStream_t)stream, dW, s_co, s_ci,
                                 out_scale, ws, ws_bytes);
 }
-
-int umi_conv3x3_mfma_act(const void* x, int ldx, const void* tx, const void* wp8, const void* out_tx, void* y, int ldy, int N,
-                         int H, int W, int Ci, int Co, hipStream_t s);
 
 // Inference form of conv3x3 + BatchNorm + ReLU (reference Model.py:15-22 under model.eval(), test_mc3serousv5.py:877-887):
 // y = max(out_tx.scale * conv(tx(x), w) + out_tx.shift, out_tx.lo) stored activated, no statistics.  UMI_ERR_UNSUPPORTED
@@ -233,14 +131,11 @@ int umi_conv3x3_mfma_act(const void* x, int ldx, const void* tx, const void* wp8
 extern "C" int umi_conv3x3_fwd_act(const void* x, int ldx, const void* tx, const void* wp8, const void* out_tx, void* y, int ldy,
                                    int N, int H, int W, int Ci, int Co, int dtype, umi_stream_t stream) {
     if (!x || !wp8 || !out_tx || !y || N <= 0 || H <= 0 || W <= 0 || ldx < Ci || ldy < Co) return UMI_ERR_BADARG;
-    if (!umi_conv3x3_mfma_ok(N, H, W, Ci, Co, 3, 3, 1, 1, H, W, ldx, ldy, dtype, dtype, 0, nullptr)) return UMI_ERR_UNSUPPORTED;
+    const ConvFwdProblem p = fwd_problem_3x3(N, H, W, Ci, Co, ldx, ldy, dtype, tx != nullptr);
+    if (umi_conv_fwd_path(p) != FWD_MFMA3X3) return UMI_ERR_UNSUPPORTED;
     if (((uintptr_t)x | (uintptr_t)y | (uintptr_t)wp8 | (uintptr_t)out_tx) & 15) return UMI_ERR_BADARG;
-    return umi_conv3x3_mfma_act(x, ldx, tx, wp8, out_tx, y, ldy, N, H, W, Ci, Co, (hipStream_t)stream);
+    return umi_conv3x3_mfma_act(p, x, tx, wp8, out_tx, y, (hipStream_t)stream);
 }
-
-// stage 2 of the BatchNorm backward reduction on partial rows produced by umi_conv_dgrad_bnred
-int umi_colsum_rows_f16v(long M, int C);
-bool umi_bn_stats_f16v(const void* x, int ldx, float* part, long M, int C, hipStream_t s);
 
 // BatchNorm batch statistics of a stored fp16 tensor as partial rows part[rows][2][C] (sum, sum of squares) for umi_bn_finalize:
 // for producers without a statistics epilogue (the pointwise MFMA convolution).  rows = umi_bn_stats_rows(M, C) (0: unsupported).
@@ -251,10 +146,6 @@ extern "C" int umi_bn_stats(const void* x, int ldx, float* part, long M, int C, 
     UMI_LAUNCH_CHECK();
     return UMI_OK;
 }
-
-int umi_pool2_bwd_bnred_rows(int N, int H, int W, int C);
-bool umi_pool2_bwd_bnred_f16v(const void* dp, int lddp, const void* x, int ldx, const void* tx, const float* rstd, void* da,
-                              int ldda, int accumulate, float* part, int N, int H, int W, int C, hipStream_t s);
 
 // MaxPool2d(2) backward into `da` + stage 1 of the BatchNorm backward of the pooled layer (x = its raw output): only when
 // this is the last contribution to `da`.  *rows receives the partial rows written (part[rows][2][C]).
@@ -294,134 +185,119 @@ extern "C" int umi_conv_fwd(const void* x, int ldx, const void* tx, const void* 
     if (!x || !wp || !y || N <= 0 || H <= 0 || W <= 0 || Ci <= 0 || Co <= 0 || R <= 0 || S <= 0 || stride <= 0 ||
         Ho <= 0 || Wo <= 0 || ldx < Ci || ldy < Co || out_H <= 0 || out_W <= 0)
         return UMI_ERR_BADARG;
-    if (flags & UMI_CONV_ACCUMULATE) {
-        // only the pointwise / tap-gather MFMA kernel adds into y, and where it is eligible it is the path taken below (the 3x3
-        // kernel's stride-1 pad-1 problems are never eligible for it)
-        if (stat_part || !umi_conv1x1_mfma_ok(Ci, Co, R, S, stride, pad, ldx, ldy, in_dtype, out_dtype, flags))
-            return UMI_ERR_UNSUPPORTED;
-    }
+    const ConvFwdProblem p = fwd_problem(N, H, W, Ci, Co, R, S, stride, pad, Ho, Wo, ldx, ldy, in_dtype, out_dtype, flags,
+                                         tx != nullptr, bias != nullptr, stat_part != nullptr);
+    const ConvFwdPath path = umi_conv_fwd_path(p);
+    // only the pointwise / tap-gather MFMA kernel adds into y
+    if ((flags & UMI_CONV_ACCUMULATE) && (stat_part || path != FWD_MFMA1X1)) return UMI_ERR_UNSUPPORTED;
     if (flags & UMI_CONV_DGRAD_STRIDED) {
         // x = dy of a strided conv (H x W), output grid = the conv's input image (Ho x Wo)
         if (flags & UMI_CONV_UPSAMPLE2) return UMI_ERR_BADARG;
         if (H != (Ho + 2 * pad - R) / stride + 1 || W != (Wo + 2 * pad - S) / stride + 1) return UMI_ERR_BADARG;
         if (out_H != Ho || out_W != Wo || off_h || off_w || stat_part) return UMI_ERR_BADARG;
-        if (umi_conv1x1_mfma_ok(Ci, Co, R, S, stride, pad, ldx, ldy, in_dtype, out_dtype, flags)) {
-            if (((uintptr_t)x | (uintptr_t)y | (uintptr_t)wp) & 15) return UMI_ERR_BADARG;
-            return umi_conv1x1_mfma(x, ldx, tx, wp, bias, y, ldy, N, H, W, Ci, Co, R, S, stride, pad, Ho, Wo, 0, 0, Ho, Wo,
-                                    flags, (hipStream_t)stream);
-        }
-        UMI_TRACE("dgrad_strided");
-        return umi_conv_fwd_generic(x, ldx, tx, wp, bias, y, ldy, stat_part, N, H, W, Ci, Co, R, S, stride, pad, Ho, Wo,
-                                    off_h, off_w, out_H, out_W, in_dtype, out_dtype, flags, (hipStream_t)stream);
-    }
-    if (!(flags & UMI_CONV_UPSAMPLE2)) {
+    } else if (!(flags & UMI_CONV_UPSAMPLE2)) {
         if (Ho != (H + 2 * pad - R) / stride + 1 || Wo != (W + 2 * pad - S) / stride + 1) return UMI_ERR_BADARG;
         if (out_H != Ho || out_W != Wo || off_h || off_w) return UMI_ERR_BADARG;
     } else {
         if (Ho != H || Wo != W) return UMI_ERR_BADARG;
     }
-    if (umi_conv3x3_mfma_ok(N, H, W, Ci, Co, R, S, stride, pad, Ho, Wo, ldx, ldy, in_dtype, out_dtype, flags, bias)) {
+    const hipStream_t s = (hipStream_t)stream;
+    switch (path) {
+    case FWD_MFMA3X3:
         // the caller packed the weights for this path (umi_conv_fwd_plan said layout 1): misalignment is an error,
         // not a reason to silently reinterpret them
         if (((uintptr_t)x | (uintptr_t)y | (uintptr_t)wp) & 15) return UMI_ERR_BADARG;
-        return umi_conv3x3_mfma(x, ldx, tx, wp, y, ldy, stat_part, N, H, W, Ci, Co, (hipStream_t)stream);
-    }
-    if (umi_conv1x1_mfma_ok(Ci, Co, R, S, stride, pad, ldx, ldy, in_dtype, out_dtype, flags)) {
+        return umi_conv3x3_mfma(p, x, tx, wp, y, stat_part, s);
+    case FWD_MFMA1X1:
         if (stat_part) return UMI_ERR_UNSUPPORTED;      // no BatchNorm follows a pointwise conv on this path
         if (((uintptr_t)x | (uintptr_t)y | (uintptr_t)wp) & 15) return UMI_ERR_BADARG;
-        return umi_conv1x1_mfma(x, ldx, tx, wp, bias, y, ldy, N, H, W, Ci, Co, R, S, stride, pad, Ho, Wo, off_h, off_w,
-                                out_H, out_W, flags, (hipStream_t)stream);
+        return umi_conv1x1_mfma(p, x, tx, wp, bias, y, off_h, off_w, out_H, out_W, s);
+    case FWD_STEM: return umi_stem_fwd(p, x, tx, wp, y, stat_part, s);
+    case FWD_HEAD: return umi_head_fwd(p, x, tx, wp, bias, y, stat_part, s);
+    case FWD_SMALLK: return umi_smallk_fwd(p, x, wp, y, s);
+    case FWD_ROOT: return umi_root_fwd(p, x, wp, y, s);
+    case FWD_HEAD3: return umi_head3_fwd(p, x, tx, wp, bias, y, s);
+    case FWD_GENERIC: break;
     }
-    if (umi_stem_fwd_ok(Ci, Co, R, S, stride, pad, ldy, in_dtype, out_dtype, flags, bias))
-        return umi_stem_fwd(x, ldx, tx, wp, y, ldy, stat_part, N, H, W, Ci, Co, (hipStream_t)stream);
-    if ((!stat_part || out_dtype == UMI_F16) && umi_head_fwd_ok(Ci, Co, R, S, stride, pad, ldx, in_dtype, out_dtype, flags))
-        return umi_head_fwd(x, ldx, tx, wp, bias, y, ldy, stat_part, (long)N * H * W, Ci, Co, out_dtype, (hipStream_t)stream);
-    if (!stat_part && umi_smallk_fwd_ok(Ci, Co, R, S, stride, pad, ldy, in_dtype, out_dtype, flags, tx, bias))
-        return umi_smallk_fwd(x, ldx, wp, y, ldy, (long)N * H * W, Ci, Co, (hipStream_t)stream);
-    if (!stat_part && umi_root_fwd_ok(Ci, Co, R, S, stride, pad, ldy, in_dtype, out_dtype, flags, tx, bias)) {
-        const int st = umi_root_fwd(x, ldx, wp, y, ldy, N, H, W, Ho, Wo, Co, (hipStream_t)stream);
-        if (st != UMI_ERR_UNSUPPORTED) return st;          // (rows too wide for its LDS staging: the generic kernel below)
-    }
-    if (!stat_part && umi_head3_fwd_ok(Ci, Co, R, S, stride, pad, ldx, in_dtype, out_dtype, flags))
-        return umi_head3_fwd(x, ldx, tx, wp, bias, y, ldy, N, H, W, Ci, Co, (hipStream_t)stream);
-    UMI_TRACE("fwd");
-    return umi_conv_fwd_generic(x, ldx, tx, wp, bias, y, ldy, stat_part, N, H, W, Ci, Co, R, S, stride, pad, Ho, Wo,
-                                off_h, off_w, out_H, out_W, in_dtype, out_dtype, flags, (hipStream_t)stream);
+    UMI_TRACE((flags & UMI_CONV_DGRAD_STRIDED) ? "dgrad_strided" : "fwd");
+    return umi_conv_fwd_generic(p, x, tx, wp, bias, y, stat_part, off_h, off_w, out_H, out_W, s);
+}
+
+static WgradProblem wgrad_problem(int N, int H, int W, int Ci, int Co, int R, int S, int stride, int pad, int Ho, int Wo, int ldx,
+                                  int lddy, int dtype, int flags, bool has_txa, bool has_txb) {
+    return WgradProblem{N, H, W, Ci, Co, R, S, stride, pad, Ho, Wo, ldx, lddy, dtype, flags, has_txa, has_txb};
 }
 
 extern "C" size_t umi_conv_wgrad_ws_bytes(int N, int Ho, int Wo, int Ci, int Co, int R, int S, int dtype, int flags) {
-    // the call picks its path from more arguments than this query has; size for whichever needs more
-    size_t g = umi_conv_wgrad_generic_ws_bytes(N, Ho, Wo, Ci, Co, R, S);
-    if (umi_wgrad3x3_mfma_ok(N, Ho, Wo, Ci, Co, R, S, 1, 1, Ho, Wo, 8, 8, dtype, flags, nullptr)) {
-        size_t m = umi_wgrad3x3_mfma_ws_bytes(N, Ho, Wo, Ci, Co);
-        if (m > g) g = m;
+    // the call picks its path from more arguments than this query has: size for whichever path could need most
+    const WgradProblem p = wgrad_problem(N, 0, 0, Ci, Co, R, S, 0, 0, Ho, Wo, 0, 0, dtype, flags, false, false);
+    const size_t bounds[] = {umi_wgrad3x3_mfma_ws_bound(p), umi_wgrad1x1_mfma_ws_bound(p), umi_wgradT_mfma_ws_bound(p),
+                             umi_wgrad_gather_mfma_ws_bound(p), umi_stem_wgrad_ws_bound(p), umi_head_wgrad_ws_bound(p),
+                             umi_root_wgrad_ws_bound(p), umi_head3_wgrad_ws_bound(p), umi_conv_wgrad_generic_ws_bound(p)};
+    size_t most = 0;
+    for (size_t b : bounds) most = b > most ? b : most;
+    return most;
+}
+
+// The weight gradient of problem `p` on `path` (= umi_conv_wgrad_path(p)), with the sinks of `o`.
+static int conv_wgrad(const WgradProblem& p, WgradPath path, const void* x, const void* txa, const void* dy, const void* txb,
+                      const WgradOut& o, hipStream_t s) {
+    if (!x || !dy || !o.dW || !o.ws || p.N <= 0 || p.H <= 0 || p.W <= 0 || p.Ci <= 0 || p.Co <= 0 || p.ldx < p.Ci || p.lddy < p.Co)
+        return UMI_ERR_BADARG;
+    switch (path) {
+    case WGRAD_MFMA3X3: return umi_wgrad3x3_mfma(p, x, txa, dy, o, s);
+    case WGRAD_MFMA1X1: return umi_wgrad1x1_mfma(p, x, txa, dy, o, s);
+    case WGRAD_T: return umi_wgradT_mfma(p, x, dy, txb, o, s);
+    case WGRAD_GATHER: return umi_wgrad_gather_mfma(p, x, txa, dy, o, s);
+    case WGRAD_STEM: return umi_stem_wgrad(p, x, txa, dy, o, s);
+    case WGRAD_HEAD: return umi_head_wgrad(p, x, txa, dy, o, s);
+    case WGRAD_ROOT: return umi_root_wgrad(p, x, dy, o, s);
+    case WGRAD_HEAD3: return umi_head3_wgrad(p, x, txa, dy, o, s);
+    case WGRAD_GENERIC: break;
     }
-    if (umi_wgrad1x1_mfma_ok((long)N * Ho * Wo, Ci, Co, R, S, 1, 0, 8, 8, dtype, flags, nullptr)) {
-        size_t m = umi_wgrad1x1_mfma_ws_bytes((long)N * Ho * Wo, Ci, Co);
-        if (m > g) g = m;
-    }
-    if (umi_wgradT_mfma_ok(2 * Ho, 2 * Wo, Ci, Co, R, S, 2, 0, Ho, Wo, 8, 8, dtype, flags, nullptr)) {
-        size_t m = umi_wgradT_mfma_ws_bytes(N, Ho, Wo, Ci, Co);
-        if (m > g) g = m;
-    }
-    if (dtype == UMI_F16 && Ci % 64 == 0 && Co % 64 == 0 && R * S <= 49 && !(flags & UMI_CONV_FORCE_GENERIC)) {
-        size_t m = umi_wgrad_gather_mfma_ws_bytes(N, Ho, Wo, Ci, Co, R, S);
-        if (m > g) g = m;
-    }
-    if (umi_stem_wgrad_ok(Ci, Co, R, S, 1, 1, 8, dtype, flags, nullptr)) {
-        size_t m = umi_stem_wgrad_ws_bytes(N, Ho, Wo, Ci, Co);
-        if (m > g) g = m;
-    }
-    if (umi_head_wgrad_ok(Ci, Co, R, S, 1, 0, 8, dtype, flags, nullptr)) {
-        size_t m = umi_head_wgrad_ws_bytes((long)N * Ho * Wo, Ci, Co);
-        if (m > g) g = m;
-    }
-    if (umi_root_wgrad_ok(Ci, Co, R, S, 2, 3, 8, dtype, flags, nullptr, nullptr)) {
-        size_t m = umi_root_wgrad_ws_bytes(N, Ho, Wo, Co);
-        if (m > g) g = m;
-    }
-    if (umi_head3_wgrad_ok(Ci, Co, R, S, 1, 1, 8, dtype, flags, nullptr)) {
-        size_t m = umi_head3_wgrad_ws_bytes((long)N * Ho * Wo, Ci, Co);
-        if (m > g) g = m;
-    }
-    return g;
+    if (trace_generic())
+        fprintf(stderr, "[umi generic wgrad] N=%d H=%d W=%d Ci=%d Co=%d R=%d stride=%d pad=%d flags=%d\n", p.N, p.H, p.W, p.Ci, p.Co,
+                p.R, p.stride, p.pad, p.flags);
+    return umi_conv_wgrad_generic(p, x, txa, dy, txb, o, s);
+}
+
+extern "C" int umi_conv_wgrad(const void* x, int ldx, const void* txa, const void* dy, int lddy, const void* txb,
+                              float* dW, long s_co, long s_ci, long s_t, float out_scale, int N, int H, int W, int Ci,
+                              int Co, int R, int S, int stride, int pad, int Ho, int Wo, int dtype, int flags, void* ws,
+                              size_t ws_bytes, umi_stream_t stream) {
+    const WgradProblem p = wgrad_problem(N, H, W, Ci, Co, R, S, stride, pad, Ho, Wo, ldx, lddy, dtype, flags, txa != nullptr, txb != nullptr);
+    const WgradOut o{dW, s_co, s_ci, s_t, out_scale, ws, ws_bytes, nullptr, nullptr};
+    return conv_wgrad(p, umi_conv_wgrad_path(p), x, txa, dy, txb, o, (hipStream_t)stream);
 }
 
 // umi_conv_wgrad whose final split-K reduction is RECORDED in *out instead of launched (umi_wgrad_reduce_group runs many of
 // them at once).  `ws` must then stay untouched until that launch; out->part == NULL when the path taken had no separate
-// reduction (the gradient is already in dW).
-void umi_wgrad_defer_set(void* slot);
+// reduction (the gradient is already in dW) or the call failed.
 extern "C" int umi_conv_wgrad_deferred(const void* x, int ldx, const void* txa, const void* dy, int lddy, const void* txb,
                                        float* dW, long s_co, long s_ci, long s_t, float out_scale, int N, int H, int W, int Ci,
                                        int Co, int R, int S, int stride, int pad, int Ho, int Wo, int dtype, int flags, void* ws,
                                        size_t ws_bytes, umi_wgrad_pending* out, umi_stream_t stream) {
     if (!out) return UMI_ERR_BADARG;
     out->part = nullptr;
-    umi_wgrad_defer_set(out);
-    const int st = umi_conv_wgrad(x, ldx, txa, dy, lddy, txb, dW, s_co, s_ci, s_t, out_scale, N, H, W, Ci, Co, R, S, stride, pad, Ho,
-                                  Wo, dtype, flags, ws, ws_bytes, stream);
-    umi_wgrad_defer_set(nullptr);
-    return st;
+    const WgradProblem p = wgrad_problem(N, H, W, Ci, Co, R, S, stride, pad, Ho, Wo, ldx, lddy, dtype, flags, txa != nullptr, txb != nullptr);
+    const WgradOut o{dW, s_co, s_ci, s_t, out_scale, ws, ws_bytes, out, nullptr};
+    return conv_wgrad(p, umi_conv_wgrad_path(p), x, txa, dy, txb, o, (hipStream_t)stream);
 }
 
 // ConvTranspose2d(2,2) weight gradient (called like umi_conv_wgrad_deferred for it: x = d(up), dy = the ConvT's input) that also
 // produces the BIAS gradient d bias[c] = out_scale * sum over pixels of x[.][c] from the operand tiles it stages (reference
 // Model.py:56-57 under autograd; replaces umi_colsum's pass over x).  UMI_ERR_UNSUPPORTED (nothing launched) where the 2x2 / stride-2
 // matrix-core kernel does not take the problem: run umi_colsum + umi_conv_wgrad instead.  `out` may be NULL (reduce at once).
-void umi_wgradT_bias_set(float* bias_out);
 extern "C" int umi_conv_wgrad_bias(const void* x, int ldx, const void* dy, int lddy, const void* txb, float* dW, long s_co,
                                    long s_ci, long s_t, float* dbias, float out_scale, int N, int H, int W, int Ci, int Co, int Ho,
                                    int Wo, int dtype, int flags, void* ws, size_t ws_bytes, umi_wgrad_pending* out,
                                    umi_stream_t stream) {
     if (!dbias) return UMI_ERR_BADARG;
-    if (!umi_wgradT_mfma_ok(H, W, Ci, Co, 2, 2, 2, 0, Ho, Wo, ldx, lddy, dtype, flags, nullptr)) return UMI_ERR_UNSUPPORTED;
-    if (out) { out->part = nullptr; umi_wgrad_defer_set(out); }
-    umi_wgradT_bias_set(dbias);
-    const int st = umi_conv_wgrad(x, ldx, nullptr, dy, lddy, txb, dW, s_co, s_ci, s_t, out_scale, N, H, W, Ci, Co, 2, 2, 2, 0, Ho, Wo,
-                                  dtype, flags, ws, ws_bytes, stream);
-    umi_wgradT_bias_set(nullptr);
-    umi_wgrad_defer_set(nullptr);
-    return st;
+    const WgradProblem p = wgrad_problem(N, H, W, Ci, Co, 2, 2, 2, 0, Ho, Wo, ldx, lddy, dtype, flags, false, txb != nullptr);
+    if (umi_conv_wgrad_path(p) != WGRAD_T) return UMI_ERR_UNSUPPORTED;
+    if (out) out->part = nullptr;
+    const WgradOut o{dW, s_co, s_ci, s_t, out_scale, ws, ws_bytes, out, dbias};
+    return conv_wgrad(p, WGRAD_T, x, nullptr, dy, txb, o, (hipStream_t)stream);
 }
 
 // umi_conv_wgrad for `n` pointwise convs / nn.Linear layers of ONE shape (M rows, Ci -> Co, same row strides) in one launch:
@@ -433,7 +309,10 @@ extern "C" int umi_conv_wgrad_group(int n, const void* const* x, int ldx, const 
     if (n <= 0 || !x || !dy || !dW || M <= 0 || Ci <= 0 || Co <= 0 || ldx < Ci || lddy < Co) return UMI_ERR_BADARG;
     for (int i = 0; i < n; ++i)
         if (!x[i] || !dy[i] || !dW[i]) return UMI_ERR_BADARG;
-    if (!umi_wgrad1x1_mfma_ok(M, Ci, Co, 1, 1, 1, 0, ldx, lddy, dtype, 0, nullptr)) return UMI_ERR_UNSUPPORTED;
+    // (M rows as one image row; the predicate's own offset test refuses any M near 2^31 first)
+    if (M >= (1L << 31) ||
+        umi_conv_wgrad_path(wgrad_problem(1, 1, (int)M, Ci, Co, 1, 1, 1, 0, 1, (int)M, ldx, lddy, dtype, 0, false, false)) != WGRAD_MFMA1X1)
+        return UMI_ERR_UNSUPPORTED;
     return umi_wgrad1x1_mfma_group(n, x, ldx, dy, lddy, dW, s_co, s_ci, out_scale, M, Ci, Co, (hipStream_t)stream);
 }
 
@@ -447,57 +326,20 @@ extern "C" int umi_conv_wgrad_bnapply(const void* x, int ldx, const void* txa, c
                                       void* dz, int lddz, float* dW, long s_co, long s_ci, long s_t, float out_scale, int N,
                                       int H, int W, int Ci, int Co, int R, int S, int stride, int pad, int dtype, int flags,
                                       void* ws, size_t ws_bytes, umi_stream_t stream) {
+    if (!x || !da || !y || !tx_bn || !rstd || !sum_dz || !sum_dzx || !dW || !ws || N <= 0 || H <= 0 || W <= 0 || Ci <= 0 ||
+        Co <= 0 || ldx < Ci || ldda < Co || ldy < Co || (dz && (lddz < Co || dz == da || dz == y)))
+        return UMI_ERR_BADARG;
+    const WgradProblem p = wgrad_problem(N, H, W, Ci, Co, R, S, stride, pad, H, W, ldx, ldda, dtype, flags, txa != nullptr, false);
+    const WgradPath path = umi_conv_wgrad_path(p);
+    const WgradOut o{dW, s_co, s_ci, s_t, out_scale, ws, ws_bytes, nullptr, nullptr};
+    const WgradBnApply bna{y, ldy, tx_bn, rstd, sum_dz, sum_dzx, dz, lddz};
     if (!dz) {
         // dz == NULL: nothing else needs dz (the layer's input takes no gradient: the network's first conv) -- the narrow-input
         // weight-gradient kernel forms it on the fly and never stores it
-        if (!x || !da || !y || !tx_bn || !rstd || !sum_dz || !sum_dzx || !dW || !ws || N <= 0 || H <= 0 || W <= 0 || Ci <= 0 ||
-            Co <= 0 || ldx < Ci || ldda < Co || ldy < Co)
-            return UMI_ERR_BADARG;
-        if (!umi_stem_wgrad_ok(Ci, Co, R, S, stride, pad, ldda, dtype, flags, nullptr) || ldy % 8) return UMI_ERR_UNSUPPORTED;
-        return umi_stem_wgrad_bnapply(x, ldx, txa, da, ldda, y, ldy, tx_bn, rstd, sum_dz, sum_dzx, dW, s_co, s_ci, s_t, out_scale,
-                                      N, H, W, Ci, Co, ws, ws_bytes, (hipStream_t)stream);
+        if (path != WGRAD_STEM || ldy % 8) return UMI_ERR_UNSUPPORTED;
+        return umi_stem_wgrad(p, x, txa, da, o, (hipStream_t)stream, &bna);
     }
-    if (!x || !da || !y || !tx_bn || !rstd || !sum_dz || !sum_dzx || !dz || !dW || !ws || N <= 0 || H <= 0 || W <= 0 ||
-        Ci <= 0 || Co <= 0 || ldx < Ci || ldda < Co || ldy < Co || lddz < Co || dz == da || dz == y)
-        return UMI_ERR_BADARG;
-    if (!umi_wgrad3x3_mfma_ok(N, H, W, Ci, Co, R, S, stride, pad, H, W, ldx, ldda, dtype, flags, nullptr) || ldy % 8 || lddz % 8 ||
-        (long)H * W * (ldy > lddz ? ldy : lddz) * 2 >= 0x7FFFFFF0L)
+    if (path != WGRAD_MFMA3X3 || ldy % 8 || lddz % 8 || (long)H * W * (ldy > lddz ? ldy : lddz) * 2 >= 0x7FFFFFF0L)
         return UMI_ERR_UNSUPPORTED;
-    return umi_wgrad3x3_mfma_bnapply(x, ldx, txa, da, ldda, y, ldy, tx_bn, rstd, sum_dz, sum_dzx, dz, lddz, dW, s_co, s_ci, s_t,
-                                     out_scale, N, H, W, Ci, Co, ws, ws_bytes, (hipStream_t)stream);
-}
-
-extern "C" int umi_conv_wgrad(const void* x, int ldx, const void* txa, const void* dy, int lddy, const void* txb,
-                              float* dW, long s_co, long s_ci, long s_t, float out_scale, int N, int H, int W, int Ci,
-                              int Co, int R, int S, int stride, int pad, int Ho, int Wo, int dtype, int flags, void* ws,
-                              size_t ws_bytes, umi_stream_t stream) {
-    if (!x || !dy || !dW || !ws || N <= 0 || H <= 0 || W <= 0 || Ci <= 0 || Co <= 0 || ldx < Ci || lddy < Co)
-        return UMI_ERR_BADARG;
-    if (umi_wgrad3x3_mfma_ok(N, H, W, Ci, Co, R, S, stride, pad, Ho, Wo, ldx, lddy, dtype, flags, txb))
-        return umi_wgrad3x3_mfma(x, ldx, txa, dy, lddy, dW, s_co, s_ci, s_t, out_scale, N, H, W, Ci, Co, ws, ws_bytes,
-                                 (hipStream_t)stream);
-    if (umi_wgrad1x1_mfma_ok((long)N * H * W, Ci, Co, R, S, stride, pad, ldx, lddy, dtype, flags, txb))
-        return umi_wgrad1x1_mfma(x, ldx, txa, dy, lddy, dW, s_co, s_ci, s_t, out_scale, (long)N * H * W, Ci, Co, ws, ws_bytes,
-                                 (hipStream_t)stream);
-    if (umi_wgradT_mfma_ok(H, W, Ci, Co, R, S, stride, pad, Ho, Wo, ldx, lddy, dtype, flags, txa))
-        return umi_wgradT_mfma(x, ldx, dy, lddy, txb, dW, s_co, s_ci, s_t, out_scale, N, Ho, Wo, Ci, Co, ws, ws_bytes,
-                               (hipStream_t)stream);
-    if (umi_wgrad_gather_mfma_ok(N, H, W, Ci, Co, R, S, stride, pad, Ho, Wo, ldx, lddy, dtype, flags, txb))
-        return umi_wgrad_gather_mfma(x, ldx, txa, dy, lddy, dW, s_co, s_ci, s_t, out_scale, N, H, W, Ci, Co, R, S, stride, pad,
-                                     Ho, Wo, ws, ws_bytes, (hipStream_t)stream);
-    if (umi_stem_wgrad_ok(Ci, Co, R, S, stride, pad, lddy, dtype, flags, txb))
-        return umi_stem_wgrad(x, ldx, txa, dy, lddy, dW, s_co, s_ci, s_t, out_scale, N, H, W, Ci, Co, ws, ws_bytes,
-                              (hipStream_t)stream);
-    if (umi_head_wgrad_ok(Ci, Co, R, S, stride, pad, ldx, dtype, flags, txb))
-        return umi_head_wgrad(x, ldx, txa, dy, lddy, dW, s_co, s_ci, s_t, out_scale, (long)N * H * W, Ci, Co, ws,
-                              ws_bytes, (hipStream_t)stream);
-    if (umi_root_wgrad_ok(Ci, Co, R, S, stride, pad, lddy, dtype, flags, txa, txb))
-        return umi_root_wgrad(x, ldx, dy, lddy, dW, s_co, s_ci, s_t, out_scale, N, H, W, Ho, Wo, Co, ws, ws_bytes,
-                              (hipStream_t)stream);
-    if (umi_head3_wgrad_ok(Ci, Co, R, S, stride, pad, ldx, dtype, flags, txb))
-        return umi_head3_wgrad(x, ldx, txa, dy, lddy, dW, s_co, s_ci, s_t, out_scale, N, H, W, Ci, Co, ws, ws_bytes,
-                               (hipStream_t)stream);
-    UMI_TRACE("wgrad");
-    return umi_conv_wgrad_generic(x, ldx, txa, dy, lddy, txb, dW, s_co, s_ci, s_t, out_scale, N, H, W, Ci, Co, R, S,
-                                  stride, pad, Ho, Wo, dtype, ws, ws_bytes, (hipStream_t)stream);
+    return umi_wgrad3x3_mfma(p, x, txa, da, o, (hipStream_t)stream, &bna);
 }

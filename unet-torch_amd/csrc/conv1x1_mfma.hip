@@ -15,7 +15,7 @@
 // pixels x BN output channels, K staged in 64-channel chunks through registers (issue-early / write-late)
 // into LDS rows of 144 B (128 B data + 16 B pad = 9 slots, odd -> conflict-free ds_read_b128), consumer-side
 // BN+ReLU transform applied on the way.  Epilogue through an LDS tile for 16-B coalesced (scattered) stores.
-#include "common.h"
+#include "kernels.h"
 #include <stdlib.h>
 #include <string.h>
 
@@ -24,10 +24,6 @@ typedef _Float16 half4 __attribute__((ext_vector_type(4)));
 typedef float floatx16 __attribute__((ext_vector_type(16)));
 typedef float floatx4 __attribute__((ext_vector_type(4)));
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-
-// epilogue fusion request of umi_linear_fused (api.hip); mode 0 = none
-struct UmiLinearEpi { int mode; float p; unsigned seed; const unsigned* seed_dev; void* mask; const void* aux; int ldaux; void* y2; int ldy2;
-                      const void* bn_tx; const float* bn_rstd; float* bn_part; };   // mode 3: aux = the BatchNorm layer's raw output
 
 namespace {
 
@@ -481,7 +477,7 @@ int launch(bool s2d, bool ups, const void* x, int ldx, const void* tx, const voi
 
 // mode: 0 = plain 1x1, 1 = ConvT(2,2) forward (UMI_CONV_UPSAMPLE2), 2 = tap gather (ConvT data gradient = stride-2 2x2 conv,
 // strided R x S convs, data gradient of a strided conv)
-int umi_conv1x1_mode(int R, int S, int stride, int pad, int flags) {
+static int umi_conv1x1_mode(int R, int S, int stride, int pad, int flags) {
     if (flags & UMI_CONV_UPSAMPLE2) return (R == 2 && S == 2) ? 1 : -1;
     if (R * S > 49 || pad < 0 || pad >= 1 << 20) return -1;
     if (flags & UMI_CONV_DGRAD_STRIDED) return stride >= 1 ? 2 : -1;
@@ -490,18 +486,20 @@ int umi_conv1x1_mode(int R, int S, int stride, int pad, int flags) {
     return -1;
 }
 
-bool umi_conv1x1_mfma_ok(int Ci, int Co, int R, int S, int stride, int pad, int ldx, int ldy, int in_dtype,
-                         int out_dtype, int flags) {
-    if (flags & UMI_CONV_FORCE_GENERIC) return false;
-    if (in_dtype != UMI_F16 || out_dtype != UMI_F16) return false;
-    const int mode = umi_conv1x1_mode(R, S, stride, pad, flags);
+bool umi_conv1x1_mfma_ok(const ConvFwdProblem& p) {
+    if (p.flags & UMI_CONV_FORCE_GENERIC) return false;
+    if (p.in_dtype != UMI_F16 || p.out_dtype != UMI_F16) return false;
+    const int mode = umi_conv1x1_mode(p.R, p.S, p.stride, p.pad, p.flags);
     if (mode < 0) return false;
-    if (ldx % 8 || ldy % 8) return false;
-    if ((long)(OUT_UPS_TAPS_MAX) * Ci * Co * 2 >= 0x7FFFFFF0L) return false;        // weights behind one 31-bit buffer resource
+    if (p.ldx % 8 || p.ldy % 8) return false;
+    if ((long)(OUT_UPS_TAPS_MAX) * p.Ci * p.Co * 2 >= 0x7FFFFFF0L) return false;        // weights behind one 31-bit buffer resource
     // plain 1x1: any Ci, Co that are multiples of 8 (partial last K chunk / output tile; the attention gates' 32-channel
     // branches); the tap-gather / transposed-conv modes keep whole 64-channel tiles
-    if (mode == 0) return Ci % 8 == 0 && Co % 8 == 0 && Ci >= 16 && Co >= 16;
-    if (Ci % 64 || Co % 64) return false;
+    if (mode == 0) return p.Ci % 8 == 0 && p.Co % 8 == 0 && p.Ci >= 16 && p.Co >= 16;
+    if (p.Ci % 64 || p.Co % 64) return false;
+    // the gather / scatter modes address a source image with 31-bit byte offsets relative to the tile's first image (two
+    // images in reach): refuse what does not fit instead of wrapping (~1 GB per image, no shipped config)
+    if (2L * p.H * p.W * p.ldx * 2 >= 0x7FFFFFF0L) return false;
     return true;
 }
 
@@ -531,10 +529,10 @@ int umi_conv1x1_bnred_rows(long M, int Ntot) {
     return (int)((M + P - 1) / P);
 }
 
-int umi_conv1x1_mfma(const void* x, int ldx, const void* tx, const void* wp8, const float* bias, void* y, int ldy,
-                     int N, int H, int W, int Ci, int Co, int R, int S, int stride, int pad, int Ho, int Wo, int off_h,
-                     int off_w, int out_H, int out_W, int flags, hipStream_t s, const UmiLinearEpi* epi) {
-    const int mode = umi_conv1x1_mode(R, S, stride, pad, flags);
+int umi_conv1x1_mfma(const ConvFwdProblem& p, const void* x, const void* tx, const void* wp8, const float* bias, void* y,
+                     int off_h, int off_w, int out_H, int out_W, hipStream_t s, const UmiLinearEpi* epi) {
+    const int N = p.N, H = p.H, W = p.W, Ci = p.Ci, Co = p.Co, Ho = p.Ho, Wo = p.Wo, ldx = p.ldx, ldy = p.ldy, flags = p.flags;
+    const int mode = umi_conv1x1_mode(p.R, p.S, p.stride, p.pad, flags);
     if (epi && epi->mode && epi->mode != 3 && (mode != 0 || (flags & UMI_CONV_ACCUMULATE) || Co % 8)) return UMI_ERR_UNSUPPORTED;
     if (epi && epi->mode == 3 && (mode == 1 || Co % 8)) return UMI_ERR_UNSUPPORTED;        // (not for the scattering ConvT forward)
     Geo geo;
@@ -548,13 +546,10 @@ int umi_conv1x1_mfma(const void* x, int ldx, const void* tx, const void* wp8, co
         M = (long)N * H * W;
         Ntot = 4 * Co;
     } else {                           // source is HxW, GEMM grid = Ho x Wo, K = R*S taps x Ci
-        geo = Geo{Ho, Wo, H, W, 0, 0, Ho, Wo, 0, 0, S, stride, pad, (flags & UMI_CONV_DGRAD_STRIDED) ? 1 : 0};
+        geo = Geo{Ho, Wo, H, W, 0, 0, Ho, Wo, 0, 0, p.S, p.stride, p.pad, (flags & UMI_CONV_DGRAD_STRIDED) ? 1 : 0};
         M = (long)N * Ho * Wo;
-        ntaps = R * S;
+        ntaps = p.R * p.S;
     }
-    // the gather / scatter modes address a source image with 31-bit byte offsets relative to the tile's first image (two
-    // images in reach): refuse what does not fit instead of wrapping (ADVICE round 2; ~1 GB per image, no shipped config)
-    if (mode != 0 && 2L * H * W * ldx * 2 >= 0x7FFFFFF0L) return UMI_ERR_UNSUPPORTED;
     geo.accum = (flags & UMI_CONV_ACCUMULATE) ? 1 : 0;
     geo.epi = 0; geo.drop_p = 0.f; geo.seed = 0; geo.seed_dev = nullptr; geo.mask = nullptr; geo.aux = nullptr; geo.ldaux = 0;
     geo.y2 = nullptr; geo.ldy2 = 0; geo.bn_tx = nullptr; geo.bn_rstd = nullptr; geo.bn_part = nullptr;

@@ -44,7 +44,7 @@
 // Epilogue: accumulators -> fp16 -> LDS tile [pixel][BN] -> coalesced 16-B global stores, and the
 // per-channel sum / sum-of-squares of the *stored* values (BatchNorm statistics) are taken column-wise
 // from that LDS tile and written as one deterministic partial row per pixel tile.
-#include "common.h"
+#include "kernels.h"
 #include <stdlib.h>
 
 typedef _Float16 half8 __attribute__((ext_vector_type(8)));
@@ -807,13 +807,12 @@ int launch(const void* x, int ldx, const void* tx, const void* wp8, void* y, int
 }  // namespace
 
 // Shapes the MFMA path takes; everything else goes to the generic kernel.
-bool umi_conv3x3_mfma_ok(int N, int H, int W, int Ci, int Co, int R, int S, int stride, int pad, int Ho, int Wo,
-                         int ldx, int ldy, int in_dtype, int out_dtype, int flags, const float* bias) {
-    if (flags & (UMI_CONV_UPSAMPLE2 | UMI_CONV_FORCE_GENERIC)) return false;
-    if (in_dtype != UMI_F16 || out_dtype != UMI_F16 || bias) return false;
-    if (R != 3 || S != 3 || stride != 1 || pad != 1 || Ho != H || Wo != W) return false;
-    if (Ci % 16 || Co % 8 || ldx % 8 || ldy % 8) return false;
-    if ((long)N * H * W * (long)(ldx > ldy ? ldx : ldy) >= (1L << 40)) return false;
+bool umi_conv3x3_mfma_ok(const ConvFwdProblem& p) {
+    if (p.flags & (UMI_CONV_UPSAMPLE2 | UMI_CONV_FORCE_GENERIC)) return false;
+    if (p.in_dtype != UMI_F16 || p.out_dtype != UMI_F16 || p.has_bias) return false;
+    if (p.R != 3 || p.S != 3 || p.stride != 1 || p.pad != 1 || p.Ho != p.H || p.Wo != p.W) return false;
+    if (p.Ci % 16 || p.Co % 8 || p.ldx % 8 || p.ldy % 8) return false;
+    if ((long)p.N * p.H * p.W * (long)(p.ldx > p.ldy ? p.ldx : p.ldy) >= (1L << 40)) return false;
     return true;
 }
 
@@ -836,36 +835,40 @@ extern "C" int umi_tune_conv3x3_impl(int impl) {
 
 static int pick_th(int Co) { return use_bn128(Co) ? 8 : 16; }
 
-int umi_conv3x3_mfma_stat_rows(int N, int H, int W, int Ci, int Co, int ldx) {
+int umi_conv3x3_mfma_stat_rows(int N, int H, int W, int Co) {
     const int th = pick_th(Co);
     return N * ((W + 31) / 32) * ((H + th - 1) / th);
 }
 
-#define UMI_GO(...)                                                                          \
+// (x, ldx, tx, wp8, y, ldy, stat_part, N, H, W, Ci, Co, BnRed*, stream[, out_tx]) of problem `p`
+#define UMI_GO(x, tx, wp8, y, part, ...)                                                     \
     do {                                                                                     \
-        if (use_bn128(Co) && Ci % 32 == 0 && g_impl != 2) return launch<8, 128, 2, true>(__VA_ARGS__); \
-        if (use_bn128(Co)) return launch<8, 128, 1>(__VA_ARGS__);                            \
-        if (Ci % 32 == 0 && g_impl == 3) return launch<16, 64, 2, true>(__VA_ARGS__);        \
-        if (Ci % 32 == 0 && g_impl != 2) return launch<16, 64, 2>(__VA_ARGS__);              \
-        return launch<16, 64, 1>(__VA_ARGS__);                                               \
+        const int Ci = p.Ci, Co = p.Co;                                                      \
+        if (use_bn128(Co) && Ci % 32 == 0 && g_impl != 2)                                    \
+            return launch<8, 128, 2, true>(x, p.ldx, tx, wp8, y, p.ldy, part, p.N, p.H, p.W, Ci, Co, __VA_ARGS__); \
+        if (use_bn128(Co)) return launch<8, 128, 1>(x, p.ldx, tx, wp8, y, p.ldy, part, p.N, p.H, p.W, Ci, Co, __VA_ARGS__); \
+        if (Ci % 32 == 0 && g_impl == 3)                                                     \
+            return launch<16, 64, 2, true>(x, p.ldx, tx, wp8, y, p.ldy, part, p.N, p.H, p.W, Ci, Co, __VA_ARGS__); \
+        if (Ci % 32 == 0 && g_impl != 2)                                                     \
+            return launch<16, 64, 2>(x, p.ldx, tx, wp8, y, p.ldy, part, p.N, p.H, p.W, Ci, Co, __VA_ARGS__); \
+        return launch<16, 64, 1>(x, p.ldx, tx, wp8, y, p.ldy, part, p.N, p.H, p.W, Ci, Co, __VA_ARGS__); \
     } while (0)
 
-int umi_conv3x3_mfma(const void* x, int ldx, const void* tx, const void* wp8, void* y, int ldy, float* stat_part,
-                     int N, int H, int W, int Ci, int Co, hipStream_t s) {
-    UMI_GO(x, ldx, tx, wp8, y, ldy, stat_part, N, H, W, Ci, Co, nullptr, s);
+int umi_conv3x3_mfma(const ConvFwdProblem& p, const void* x, const void* tx, const void* wp8, void* y, float* stat_part,
+                     hipStream_t s) {
+    UMI_GO(x, tx, wp8, y, stat_part, nullptr, s);
 }
 
 // data gradient + stage 1 of the BatchNorm backward of the layer whose activated-output gradient it produces (EPI 2)
-int umi_conv3x3_mfma_bnred(const void* dy, int lddy, const void* wp8, void* da, int ldda, const void* ybn, int ldybn,
-                           const void* txbn, const float* rstd, float* part, int N, int H, int W, int Ci, int Co,
-                           hipStream_t s) {
+int umi_conv3x3_mfma_bnred(const ConvFwdProblem& p, const void* dy, const void* wp8, void* da, const void* ybn, int ldybn,
+                           const void* txbn, const float* rstd, float* part, hipStream_t s) {
     const BnRed bn{(const half_t*)ybn, ldybn, (const float4*)txbn, rstd};
-    UMI_GO(dy, lddy, nullptr, wp8, da, ldda, part, N, H, W, Ci, Co, &bn, s);
+    UMI_GO(dy, nullptr, wp8, da, part, &bn, s);
 }
 
 // inference: conv + this layer's BatchNorm (running statistics) + ReLU on store (EPI 3)
-int umi_conv3x3_mfma_act(const void* x, int ldx, const void* tx, const void* wp8, const void* out_tx, void* y, int ldy, int N,
-                         int H, int W, int Ci, int Co, hipStream_t s) {
-    UMI_GO(x, ldx, tx, wp8, y, ldy, nullptr, N, H, W, Ci, Co, nullptr, s, out_tx);
+int umi_conv3x3_mfma_act(const ConvFwdProblem& p, const void* x, const void* tx, const void* wp8, const void* out_tx, void* y,
+                         hipStream_t s) {
+    UMI_GO(x, tx, wp8, y, nullptr, nullptr, s, out_tx);
 }
 #undef UMI_GO

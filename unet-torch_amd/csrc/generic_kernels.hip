@@ -2,20 +2,7 @@
 // VALU kernels templated on the storage type.  They are the fp32 parity path and the
 // fallback for shapes the MFMA kernels do not take; written for gfx950 (64-wide waves,
 // 256-thread workgroups = 4 waves, float4 LDS reads).
-#include "common.h"
-
-// elementwise_f16.hip: 16-B vectorised fp16 fast paths (return false when the shape does not qualify)
-int umi_bn_bwd_rpb_f16v(long M);
-int umi_colsum_rows_f16v(long M, int C);
-bool umi_colsum_f16v(const void* x, int ldx, float* ws, long M, int C, hipStream_t s);
-bool umi_bn_bwd_reduce1_f16v(const void* da, int ldda, const void* y, int ldy, const void* tx, const float* rstd, float* ws,
-                             long M, int C, hipStream_t s);
-bool umi_bn_bwd_apply_f16v(void* da, int ldda, const void* y, int ldy, const void* tx, const float* rstd,
-                           const float* sum_dz, const float* sum_dzx, long M, int C, hipStream_t s);
-bool umi_pool2_fwd_f16v(const void* x, int ldx, const void* tx, void* y, int ldy, int N, int H, int W, int C,
-                        hipStream_t s);
-bool umi_pool2_bwd_f16v(const void* dp, int lddp, const void* x, int ldx, const void* tx, void* da, int ldda,
-                        int accumulate, int N, int H, int W, int C, hipStream_t s);
+#include "kernels.h"
 
 // ------------------------------------------------------------------------------------------
 // weight packing
@@ -219,10 +206,10 @@ __global__ __launch_bounds__(256) void conv_generic_kernel(
     }
 }
 
-int umi_conv_fwd_generic(const void* x, int ldx, const void* tx, const void* wp, const float* bias, void* y, int ldy,
-                         float* stat_part, int N, int H, int W, int Ci, int Co, int R, int S, int stride, int pad,
-                         int Ho, int Wo, int off_h, int off_w, int out_H, int out_W, int in_dtype, int out_dtype,
-                         int flags, hipStream_t s) {
+int umi_conv_fwd_generic(const ConvFwdProblem& p, const void* x, const void* tx, const void* wp, const float* bias, void* y,
+                         float* stat_part, int off_h, int off_w, int out_H, int out_W, hipStream_t s) {
+    const int N = p.N, H = p.H, W = p.W, Ci = p.Ci, Co = p.Co, R = p.R, S = p.S, stride = p.stride, pad = p.pad, Ho = p.Ho, Wo = p.Wo,
+              ldx = p.ldx, ldy = p.ldy, in_dtype = p.in_dtype, out_dtype = p.out_dtype, flags = p.flags;
     const bool ups = flags & UMI_CONV_UPSAMPLE2;
     const bool dgs = flags & UMI_CONV_DGRAD_STRIDED;
     if (ups && (R != 2 || S != 2 || stat_part)) return UMI_ERR_BADARG;
@@ -795,8 +782,6 @@ extern "C" size_t umi_colsum_ws_bytes(long M, int C) {
 
 // umi_colsum for n tensors of one shape in two launches per 16 (fp16, C % 8 == 0; UMI_ERR_UNSUPPORTED otherwise): `ws` needs
 // min(n, 16) * umi_colsum_ws_bytes(M, C) bytes
-bool umi_colsum_group_f16v(int n, const void* const* xs, int ldx, float* const* outs, float scale, float* ws, long M, int C,
-                           hipStream_t s);
 extern "C" int umi_colsum_group(int n, const void* const* xs, int ldx, float* const* outs, float out_scale, long M, int C,
                                 int dtype, void* ws, size_t ws_bytes, umi_stream_t stream) {
     if (n <= 0 || !xs || !outs || M <= 0 || C <= 0 || !ws) return UMI_ERR_BADARG;
@@ -1005,13 +990,10 @@ __global__ __launch_bounds__(256) void wgrad_reduce_v4_kernel(const float* __res
     }
 }
 
-// Deferred form: umi_conv_wgrad_deferred arms a slot; the one reduction a weight-gradient path would launch is recorded there
-// instead, and umi_wgrad_reduce_group later runs the reductions of many layers in one launch per 16 (a split-K reduction of a
-// small weight is a ~8-us launch for a few hundred KB; a U-Net step has 22 of them, a TransUNet step 62).
-struct WgPending { const float* part; float* dW; long s_co, s_ci, s_t; float scale; int splits, RS, Ci, Co; };   // = umi_wgrad_pending
-static thread_local WgPending* g_wgrad_defer = nullptr;
-void umi_wgrad_defer_set(void* slot) { g_wgrad_defer = (WgPending*)slot; }
-
+// Deferred form (umi_conv_wgrad_deferred): the one reduction a weight-gradient path would launch is recorded in the caller's
+// umi_wgrad_pending instead, and umi_wgrad_reduce_group later runs the reductions of many layers in one launch per 16 (a split-K
+// reduction of a small weight is a ~8-us launch for a few hundred KB; a U-Net step has 22 of them, a TransUNet step 62).
+//
 // Transposing form for the large weights (round 3).  The slabs are [tap][ci][co] (co fastest), the parameter is OIHW (or IOHW for
 // ConvTranspose2d): written element by element the outputs of a workgroup are 4-byte stores a whole row apart -- 31 M of them per
 // U-Net step, partial lines that leave L2 before their neighbours arrive (0.44 ms/step for 0.7 GB = 1.6 TB/s).  Here a workgroup
@@ -1020,14 +1002,14 @@ void umi_wgrad_defer_set(void* slot) { g_wgrad_defer = (WgPending*)slot; }
 // values in LDS in the parameter's order and writes runs of 8 * RS (OIHW) or 32 * RS (IOHW) consecutive floats.
 // Taken where it yields >= 512 tiles (small weights keep the element-wise form: their parallelism is in the split dimension).
 constexpr int WGT_CO = 32, WGT_CI = 8;
-__host__ __device__ inline int wg_tmode(const WgPending& d) {       // 0 = element-wise, 1 = OIHW tiles, 2 = IOHW tiles
+__host__ __device__ inline int wg_tmode(const umi_wgrad_pending& d) {       // 0 = element-wise, 1 = OIHW tiles, 2 = IOHW tiles
     if (d.Co % WGT_CO || d.Ci % WGT_CI || d.RS > 9 || d.s_t != 1 || (((uintptr_t)d.part) & 15)) return 0;
     if ((long)(d.Co / WGT_CO) * (d.Ci / WGT_CI) < 512) return 0;
     if (d.s_ci == d.RS && d.s_co == (long)d.Ci * d.RS) return 1;
     if (d.s_co == d.RS && d.s_ci == (long)d.Co * d.RS) return 2;
     return 0;
 }
-__device__ void wg_reduce_tiles(const WgPending& d, int mode, int my_blk, int n_blk) {
+__device__ void wg_reduce_tiles(const umi_wgrad_pending& d, int mode, int my_blk, int n_blk) {
     __shared__ float4 redt[8][33];
     __shared__ float tile[WGT_CO * WGT_CI * 9 + 64];
     const int ox = threadIdx.x & 31, sl = threadIdx.x >> 5;
@@ -1081,13 +1063,13 @@ __device__ void wg_reduce_tiles(const WgPending& d, int mode, int my_blk, int n_
 
 // up to 16 recorded reductions per launch: blockIdx.y = entry, the block loop and the arithmetic (lane l sums splits l, l+8, ...
 // in two chains, lanes added in order) are wgrad_reduce_v4_kernel's / wgrad_reduce_kernel's, so the results are identical
-struct WgTable { WgPending e[16]; int blk0[17]; };          // blk0: first workgroup of each entry (entry i owns blk0[i+1] - blk0[i])
+struct WgTable { umi_wgrad_pending e[16]; int blk0[17]; };          // blk0: first workgroup of each entry (entry i owns blk0[i+1] - blk0[i])
 __global__ __launch_bounds__(256) void wgrad_reduce_group_kernel(WgTable t) {
     __shared__ float4 red[8][33];
     int ent = 0;
 #pragma unroll
     for (int i = 1; i < 16; ++i) ent += (int)blockIdx.x >= t.blk0[i];
-    const WgPending d = t.e[ent];
+    const umi_wgrad_pending d = t.e[ent];
     const int my_blk = (int)blockIdx.x - t.blk0[ent], n_blk = t.blk0[ent + 1] - t.blk0[ent];
     if (const int tm = wg_tmode(d)) { wg_reduce_tiles(d, tm, my_blk, n_blk); return; }
     const int ox = threadIdx.x & 31, sl = threadIdx.x >> 5;
@@ -1143,7 +1125,7 @@ __global__ __launch_bounds__(256) void wgrad_reduce_group_kernel(WgTable t) {
 
 extern "C" int umi_wgrad_reduce_group(int n, const void* items, umi_stream_t stream) {
     if (n <= 0 || !items) return UMI_ERR_BADARG;
-    const WgPending* it = (const WgPending*)items;
+    const umi_wgrad_pending* it = (const umi_wgrad_pending*)items;
     // the whole table before the first launch: a bad entry anywhere leaves every dW untouched (RS, Ci, Co divide in the
     // kernel's index arithmetic and size its grid)
     for (int i = 0; i < n; ++i)
@@ -1168,15 +1150,17 @@ extern "C" int umi_wgrad_reduce_group(int n, const void* items, umi_stream_t str
     return UMI_OK;
 }
 
-void umi_launch_wgrad_reduce(const float* part, int splits, int RS, int Ci, int Co, float* dW, long s_co, long s_ci,
-                             long s_t, float scale, hipStream_t st) {
-    if (g_wgrad_defer) {
-        *g_wgrad_defer = WgPending{part, dW, s_co, s_ci, s_t, scale, splits, RS, Ci, Co};
-        g_wgrad_defer = nullptr;
+void umi_launch_wgrad_reduce(int splits, int RS, int Ci, int Co, const WgradOut& o, hipStream_t st) {
+    const float* part = (const float*)o.ws;
+    float* const dW = o.dW;
+    const long s_co = o.s_co, s_ci = o.s_ci, s_t = o.s_t;
+    const float scale = o.out_scale;
+    if (o.defer) {
+        *o.defer = umi_wgrad_pending{part, dW, s_co, s_ci, s_t, scale, splits, RS, Ci, Co};
         return;
     }
     {
-        const WgPending one{part, dW, s_co, s_ci, s_t, scale, splits, RS, Ci, Co};
+        const umi_wgrad_pending one{part, dW, s_co, s_ci, s_t, scale, splits, RS, Ci, Co};
         if (wg_tmode(one)) {                                    // large weight: the transposing tile form (a one-entry group launch)
             WgTable t;
             for (int i = 0; i < 16; ++i) { t.e[i] = one; t.blk0[i] = 0; }
@@ -1212,27 +1196,27 @@ static void wgrad_generic_plan(long P, int Ci, int Co, int RS, int* splits, long
     *splits = (int)((P + ch - 1) / ch);
 }
 
-size_t umi_conv_wgrad_generic_ws_bytes(int N, int Ho, int Wo, int Ci, int Co, int R, int S) {
+size_t umi_conv_wgrad_generic_ws_bound(const WgradProblem& p) {      // every problem, whatever its geometry and strides
     int splits; long chunk;
-    wgrad_generic_plan((long)N * Ho * Wo, Ci, Co, R * S, &splits, &chunk);
-    return (size_t)splits * R * S * Ci * Co * sizeof(float);
+    wgrad_generic_plan((long)p.N * p.Ho * p.Wo, p.Ci, p.Co, p.R * p.S, &splits, &chunk);
+    return (size_t)splits * p.R * p.S * p.Ci * p.Co * sizeof(float);
 }
 
-int umi_conv_wgrad_generic(const void* x, int ldx, const void* txa, const void* dy, int lddy, const void* txb, float* dW,
-                           long s_co, long s_ci, long s_t, float out_scale, int N, int H, int W, int Ci, int Co, int R,
-                           int S, int stride, int pad, int Ho, int Wo, int dtype, void* ws, size_t ws_bytes,
-                           hipStream_t st) {
+int umi_conv_wgrad_generic(const WgradProblem& p, const void* x, const void* txa, const void* dy, const void* txb,
+                           const WgradOut& o, hipStream_t st) {
+    const int N = p.N, H = p.H, W = p.W, Ci = p.Ci, Co = p.Co, R = p.R, S = p.S, stride = p.stride, pad = p.pad, Ho = p.Ho, Wo = p.Wo,
+              ldx = p.ldx, lddy = p.lddy, dtype = p.dtype;
+    void* const ws = o.ws;
+    if (o.ws_bytes < umi_conv_wgrad_generic_ws_bound(p)) return UMI_ERR_WORKSPACE;
     int splits; long chunk;
-    const long P = (long)N * Ho * Wo;
-    wgrad_generic_plan(P, Ci, Co, R * S, &splits, &chunk);
-    if (ws_bytes < (size_t)splits * R * S * Ci * Co * sizeof(float)) return UMI_ERR_WORKSPACE;
+    wgrad_generic_plan((long)N * Ho * Wo, Ci, Co, R * S, &splits, &chunk);
     const int tiles_co = umi_cdiv(Co, 64);
     dim3 grid(umi_cdiv(Ci, 64) * tiles_co, R * S, splits), block(256);
     if (dtype == UMI_F32) hipLaunchKernelGGL(wgrad_generic_kernel<float>, grid, block, 0, st, (const float*)x, ldx, (const float4*)txa, (const float*)dy, lddy, (const float4*)txb, (float*)ws, N, H, W, Ci, Co, R, S, stride, pad, Ho, Wo, chunk, tiles_co);
     else if (dtype == UMI_F16) hipLaunchKernelGGL(wgrad_generic_kernel<half_t>, grid, block, 0, st, (const half_t*)x, ldx, (const float4*)txa, (const half_t*)dy, lddy, (const float4*)txb, (float*)ws, N, H, W, Ci, Co, R, S, stride, pad, Ho, Wo, chunk, tiles_co);
     else return UMI_ERR_BADARG;
     UMI_LAUNCH_CHECK();
-    umi_launch_wgrad_reduce((const float*)ws, splits, R * S, Ci, Co, dW, s_co, s_ci, s_t, out_scale, st);
+    umi_launch_wgrad_reduce(splits, R * S, Ci, Co, o, st);
     UMI_LAUNCH_CHECK();
     return UMI_OK;
 }

@@ -7,12 +7,9 @@
 //            <= 4 and runs on the stem kernel.)
 // Same scheme as stem_head.hip: thread = pixel x 8 wide-side channels (16-B accesses), per-channel reductions through
 // registers -> LDS -> one deterministic partial row per workgroup, reduced in fixed order by wgrad_reduce_kernel.
-#include "common.h"
+#include "kernels.h"
 
 typedef _Float16 half8 __attribute__((ext_vector_type(8)));
-
-void umi_launch_wgrad_reduce(const float* part, int splits, int RS, int Ci, int Co, float* dW, long s_co, long s_ci,
-                             long s_t, float scale, hipStream_t st);
 
 namespace {
 
@@ -274,84 +271,91 @@ int grid_for(long items) {
 }  // namespace
 
 // ---- dispatch helpers used by api.hip -------------------------------------------------------------------------------
-bool umi_root_fwd_ok(int Ci, int Co, int R, int S, int stride, int pad, int ldy, int in_dtype, int out_dtype, int flags,
-                     const void* tx, const float* bias) {
-    if (flags & (UMI_CONV_UPSAMPLE2 | UMI_CONV_FORCE_GENERIC | UMI_CONV_DGRAD_STRIDED)) return false;
-    return in_dtype == UMI_F16 && out_dtype == UMI_F16 && !tx && !bias && R == 7 && S == 7 && stride == 2 && pad == 3 &&
-           Ci == 3 && groups_ok(Co) && ldy % 8 == 0 && (size_t)49 * 3 * Co * 4 <= 48 * 1024;
+static size_t root_fwd_smem(int W, int Co) { return (size_t)49 * 3 * Co * 4 + (size_t)7 * (W + 8) * 3 * 2; }
+bool umi_root_fwd_ok(const ConvFwdProblem& p) {
+    if (p.flags & (UMI_CONV_UPSAMPLE2 | UMI_CONV_FORCE_GENERIC | UMI_CONV_DGRAD_STRIDED)) return false;
+    return p.in_dtype == UMI_F16 && p.out_dtype == UMI_F16 && !p.has_tx && !p.has_bias && p.R == 7 && p.S == 7 && p.stride == 2 &&
+           p.pad == 3 && p.Ci == 3 && groups_ok(p.Co) && p.ldy % 8 == 0 && (size_t)49 * 3 * p.Co * 4 <= 48 * 1024 &&
+           root_fwd_smem(p.W, p.Co) <= 64 * 1024;          // (the 7 staged input rows: too wide an image goes to the generic kernel)
 }
-int umi_root_fwd(const void* x, int ldx, const void* wp, void* y, int ldy, int N, int H, int W, int Ho, int Wo, int Co,
-                 hipStream_t s) {
+int umi_root_fwd(const ConvFwdProblem& p, const void* x, const void* wp, void* y, hipStream_t s) {
     if (!al16(y)) return UMI_ERR_BADARG;
-    const int blocks = N * ((Ho + ROOT_ROWS - 1) / ROOT_ROWS);
-    const size_t smem = (size_t)49 * 3 * Co * 4 + (size_t)7 * (W + 8) * 3 * 2;
-    if (smem > 64 * 1024) return UMI_ERR_UNSUPPORTED;
-    hipLaunchKernelGGL((root_fwd_kernel<3, 7, 2, 3>), dim3(blocks), dim3(256), smem, s, (const half_t*)x, ldx,
-                       (const half_t*)wp, (half_t*)y, ldy, N, H, W, Ho, Wo, Co);
+    const int blocks = p.N * ((p.Ho + ROOT_ROWS - 1) / ROOT_ROWS);
+    hipLaunchKernelGGL((root_fwd_kernel<3, 7, 2, 3>), dim3(blocks), dim3(256), root_fwd_smem(p.W, p.Co), s, (const half_t*)x, p.ldx,
+                       (const half_t*)wp, (half_t*)y, p.ldy, p.N, p.H, p.W, p.Ho, p.Wo, p.Co);
     UMI_LAUNCH_CHECK();
     return UMI_OK;
 }
 
-bool umi_root_wgrad_ok(int Ci, int Co, int R, int S, int stride, int pad, int lddy, int dtype, int flags, const void* txa,
-                       const void* txb) {
-    if (flags & UMI_CONV_FORCE_GENERIC) return false;
-    return dtype == UMI_F16 && !txa && !txb && R == 7 && S == 7 && stride == 2 && pad == 3 && Ci == 3 && groups_ok(Co) &&
-           Co <= 256 && lddy % 8 == 0;
+bool umi_root_wgrad_ok(const WgradProblem& p) {
+    if (p.flags & UMI_CONV_FORCE_GENERIC) return false;
+    return p.dtype == UMI_F16 && !p.has_txa && !p.has_txb && p.R == 7 && p.S == 7 && p.stride == 2 && p.pad == 3 && p.Ci == 3 &&
+           groups_ok(p.Co) && p.Co <= 256 && p.lddy % 8 == 0;
 }
-size_t umi_root_wgrad_ws_bytes(int N, int Ho, int Wo, int Co) {
-    const long blocks = (long)N * ((Ho + ROOT_WROWS - 1) / ROOT_WROWS);
-    return (size_t)blocks * 49 * 3 * Co * sizeof(float);
+static size_t root_wgrad_ws_bytes(const WgradProblem& p) {
+    const long blocks = (long)p.N * ((p.Ho + ROOT_WROWS - 1) / ROOT_WROWS);
+    return (size_t)blocks * 49 * 3 * p.Co * sizeof(float);
 }
-int umi_root_wgrad(const void* x, int ldx, const void* dy, int lddy, float* dW, long s_co, long s_ci, long s_t, float out_scale,
-                   int N, int H, int W, int Ho, int Wo, int Co, void* ws, size_t ws_bytes, hipStream_t s) {
-    if (ws_bytes < umi_root_wgrad_ws_bytes(N, Ho, Wo, Co)) return UMI_ERR_WORKSPACE;
+size_t umi_root_wgrad_ws_bound(const WgradProblem& facts) {
+    WgradProblem p = facts;                    // the one geometry the kernel takes; the workspace does not depend on the row strides
+    p.stride = 2; p.pad = 3; p.ldx = p.lddy = 8;
+    return umi_root_wgrad_ok(p) ? root_wgrad_ws_bytes(p) : 0;
+}
+int umi_root_wgrad(const WgradProblem& p, const void* x, const void* dy, const WgradOut& o, hipStream_t s) {
+    if (o.ws_bytes < root_wgrad_ws_bytes(p)) return UMI_ERR_WORKSPACE;
     if (!al16(dy)) return UMI_ERR_BADARG;
-    const int blocks = N * ((Ho + ROOT_WROWS - 1) / ROOT_WROWS);
-    const size_t smem = (size_t)256 * 9 * 4 + (size_t)(W + 8) * 3 * 2;
-    hipLaunchKernelGGL((root_wgrad_kernel<3, 7, 2, 3>), dim3(blocks, 7), dim3(256), smem, s, (const half_t*)x, ldx,
-                       (const half_t*)dy, lddy, (float*)ws, N, H, W, Ho, Wo, Co);
+    const int blocks = p.N * ((p.Ho + ROOT_WROWS - 1) / ROOT_WROWS);
+    const size_t smem = (size_t)256 * 9 * 4 + (size_t)(p.W + 8) * 3 * 2;
+    hipLaunchKernelGGL((root_wgrad_kernel<3, 7, 2, 3>), dim3(blocks, 7), dim3(256), smem, s, (const half_t*)x, p.ldx,
+                       (const half_t*)dy, p.lddy, (float*)o.ws, p.N, p.H, p.W, p.Ho, p.Wo, p.Co);
     UMI_LAUNCH_CHECK();
-    umi_launch_wgrad_reduce((const float*)ws, blocks, 49, 3, Co, dW, s_co, s_ci, s_t, out_scale, s);
+    umi_launch_wgrad_reduce(blocks, 49, 3, p.Co, o, s);
     UMI_LAUNCH_CHECK();
     return UMI_OK;
 }
 
-bool umi_head3_fwd_ok(int Ci, int Co, int R, int S, int stride, int pad, int ldx, int in_dtype, int out_dtype, int flags) {
-    if (flags & (UMI_CONV_UPSAMPLE2 | UMI_CONV_FORCE_GENERIC | UMI_CONV_DGRAD_STRIDED)) return false;
-    return in_dtype == UMI_F16 && out_dtype == UMI_F32 && R == 3 && S == 3 && stride == 1 && pad == 1 && Co >= 1 && Co <= 4 &&
-           groups_ok(Ci) && Ci <= 64 && ldx % 8 == 0;
+bool umi_head3_fwd_ok(const ConvFwdProblem& p) {
+    if (p.flags & (UMI_CONV_UPSAMPLE2 | UMI_CONV_FORCE_GENERIC | UMI_CONV_DGRAD_STRIDED)) return false;
+    return p.in_dtype == UMI_F16 && p.out_dtype == UMI_F32 && p.R == 3 && p.S == 3 && p.stride == 1 && p.pad == 1 && p.Co >= 1 &&
+           p.Co <= 4 && groups_ok(p.Ci) && p.Ci <= 64 && p.ldx % 8 == 0;
 }
-int umi_head3_fwd(const void* x, int ldx, const void* tx, const void* wp, const float* bias, void* y, int ldy, int N, int H,
-                  int W, int Ci, int Co, hipStream_t s) {
+int umi_head3_fwd(const ConvFwdProblem& p, const void* x, const void* tx, const void* wp, const float* bias, void* y,
+                  hipStream_t s) {
     if (!al16(x)) return UMI_ERR_BADARG;
-    const int grid = grid_for((long)N * H * W * (Ci / 8));
+    const int Ci = p.Ci, Co = p.Co;
+    const int grid = grid_for((long)p.N * p.H * p.W * (Ci / 8));
     const size_t smem = (size_t)9 * Ci * Co * 4;
-#define GO(NC) hipLaunchKernelGGL(head3x3_fwd_kernel<NC>, dim3(grid), dim3(256), smem, s, (const half_t*)x, ldx, (const float4*)tx, (const half_t*)wp, bias, (float*)y, ldy, N, H, W, Ci)
+#define GO(NC) hipLaunchKernelGGL(head3x3_fwd_kernel<NC>, dim3(grid), dim3(256), smem, s, (const half_t*)x, p.ldx, (const float4*)tx, (const half_t*)wp, bias, (float*)y, p.ldy, p.N, p.H, p.W, Ci)
     switch (Co) { case 1: GO(1); break; case 2: GO(2); break; case 3: GO(3); break; default: GO(4); }
 #undef GO
     UMI_LAUNCH_CHECK();
     return UMI_OK;
 }
 
-bool umi_head3_wgrad_ok(int Ci, int Co, int R, int S, int stride, int pad, int ldx, int dtype, int flags, const void* txb) {
-    if (flags & UMI_CONV_FORCE_GENERIC) return false;
-    return dtype == UMI_F16 && !txb && R == 3 && S == 3 && stride == 1 && pad == 1 && Co >= 1 && Co <= 4 && groups_ok(Ci) &&
-           Ci <= 256 && ldx % 8 == 0;
+bool umi_head3_wgrad_ok(const WgradProblem& p) {
+    if (p.flags & UMI_CONV_FORCE_GENERIC) return false;
+    return p.dtype == UMI_F16 && !p.has_txb && p.R == 3 && p.S == 3 && p.stride == 1 && p.pad == 1 && p.Co >= 1 && p.Co <= 4 &&
+           groups_ok(p.Ci) && p.Ci <= 256 && p.ldx % 8 == 0;
 }
-size_t umi_head3_wgrad_ws_bytes(long P, int Ci, int Co) {
+static size_t head3_wgrad_ws_bytes(long P, int Ci, int Co) {
     return (size_t)((P + WG_PPB - 1) / WG_PPB) * 9 * Ci * Co * sizeof(float);
 }
-int umi_head3_wgrad(const void* x, int ldx, const void* txa, const void* dy, int lddy, float* dW, long s_co, long s_ci, long s_t,
-                    float out_scale, int N, int H, int W, int Ci, int Co, void* ws, size_t ws_bytes, hipStream_t s) {
-    const long P = (long)N * H * W;
-    if (ws_bytes < umi_head3_wgrad_ws_bytes(P, Ci, Co)) return UMI_ERR_WORKSPACE;
+size_t umi_head3_wgrad_ws_bound(const WgradProblem& facts) {
+    WgradProblem p = facts;
+    p.stride = p.pad = 1; p.ldx = p.lddy = 8;
+    return umi_head3_wgrad_ok(p) ? head3_wgrad_ws_bytes((long)p.N * p.Ho * p.Wo, p.Ci, p.Co) : 0;
+}
+int umi_head3_wgrad(const WgradProblem& p, const void* x, const void* txa, const void* dy, const WgradOut& o, hipStream_t s) {
+    const long P = (long)p.N * p.H * p.W;
+    const int Ci = p.Ci, Co = p.Co;
+    if (o.ws_bytes < head3_wgrad_ws_bytes(P, Ci, Co)) return UMI_ERR_WORKSPACE;
     if (!al16(x)) return UMI_ERR_BADARG;
     const int blocks = (int)((P + WG_PPB - 1) / WG_PPB);
-#define GO(NC) hipLaunchKernelGGL(head3x3_wgrad_kernel<NC>, dim3(blocks, 9), dim3(256), 0, s, (const half_t*)x, ldx, (const float4*)txa, (const half_t*)dy, lddy, (float*)ws, N, H, W, Ci)
+#define GO(NC) hipLaunchKernelGGL(head3x3_wgrad_kernel<NC>, dim3(blocks, 9), dim3(256), 0, s, (const half_t*)x, p.ldx, (const float4*)txa, (const half_t*)dy, p.lddy, (float*)o.ws, p.N, p.H, p.W, Ci)
     switch (Co) { case 1: GO(1); break; case 2: GO(2); break; case 3: GO(3); break; default: GO(4); }
 #undef GO
     UMI_LAUNCH_CHECK();
-    umi_launch_wgrad_reduce((const float*)ws, blocks, 9, Ci, Co, dW, s_co, s_ci, s_t, out_scale, s);
+    umi_launch_wgrad_reduce(blocks, 9, Ci, Co, o, s);
     UMI_LAUNCH_CHECK();
     return UMI_OK;
 }

@@ -13,24 +13,6 @@
 
 namespace {
 
-struct OptDesc {           // mirrors umi_optim_desc (include/unetmi.h)
-    float* p;
-    const float* g;
-    float* s0;
-    float* s1;
-    long n;
-    int blk0;
-    int pad_;
-};
-
-struct PackDesc {          // mirrors umi_pack_desc
-    const float* src;
-    void* dst;
-    long st, sk, sn;
-    int T, K, N, flip_t, Kpad, Npad, k8, blk0;
-    int ldn, pad_;         // ldn: row length of the destination when this entry fills a column slice of a wider matrix (0 = Npad)
-};
-
 constexpr int OPT_BLOCK = 4096;      // elements per workgroup (256 threads x 4 x float4)
 constexpr int PACK_BLOCK = 2048;     // packed elements per workgroup
 
@@ -80,13 +62,13 @@ __device__ inline void adam_one(float& p, float g, float& m, float& v, const Ada
 }
 
 template <bool ADAM, typename A>
-__global__ __launch_bounds__(256) void optim_multi_kernel(const OptDesc* __restrict__ descs, int n_desc, A a) {
+__global__ __launch_bounds__(256) void optim_multi_kernel(const umi_optim_desc* __restrict__ descs, int n_desc, A a) {
     if (a.hp) {                               // learning rate / bias corrections from device memory (graph-safe)
         if constexpr (ADAM) { a.step_size = a.hp->step_size_f; a.bc2_sqrt = a.hp->bc2_sqrt_f; }
         else a.lr = a.hp->lr_f;
     }
     const int blk = blockIdx.x;
-    const OptDesc d = descs[find_desc(descs, n_desc, blk)];
+    const umi_optim_desc d = descs[find_desc(descs, n_desc, blk)];
     const long base = (long)(blk - d.blk0) * OPT_BLOCK;
     const long left = d.n - base;
     const int cnt = left < OPT_BLOCK ? (int)left : OPT_BLOCK;
@@ -141,7 +123,7 @@ __global__ __launch_bounds__(256) void optim_multi_kernel(const OptDesc* __restr
 // (1.26 GB in 0.50 ms on the TransUNet's 105 M parameters, 0.18 ms on the U-Net's 31 M).
 constexpr int PT = 32;
 template <typename T, int U>
-__device__ __forceinline__ void pack_stage(const PackDesc& d, T* tl, int k0, int n0, bool k_inner) {
+__device__ __forceinline__ void pack_stage(const umi_pack_desc& d, T* tl, int k0, int n0, bool k_inner) {
     const int TT = d.T;
     for (int e0 = threadIdx.x; e0 < PT * PT * TT; e0 += 256 * U) {
         float v[U];
@@ -172,7 +154,7 @@ __device__ __forceinline__ void pack_stage(const PackDesc& d, T* tl, int k0, int
 }
 
 template <typename T>
-__device__ void pack_tiles_k8(const PackDesc& d, int my_blk, int n_blk) {
+__device__ void pack_tiles_k8(const umi_pack_desc& d, int my_blk, int n_blk) {
     __shared__ T tl[9 * PT * (PT + 2)];                       // [t][k][n], row pad 2
     const int nkt = (d.Kpad + PT - 1) / PT, nnt = (d.Npad + PT - 1) / PT;
     const int kb8 = d.Kpad >> 3, ldn = d.ldn ? d.ldn : d.Npad, TT = d.T;
@@ -205,9 +187,9 @@ __device__ void pack_tiles_k8(const PackDesc& d, int my_blk, int n_blk) {
 }
 
 template <typename T>
-__global__ __launch_bounds__(256) void pack_multi_kernel(const PackDesc* __restrict__ descs, int n_desc) {
+__global__ __launch_bounds__(256) void pack_multi_kernel(const umi_pack_desc* __restrict__ descs, int n_desc) {
     const int blk = blockIdx.x;
-    const PackDesc d = descs[find_desc(descs, n_desc, blk)];
+    const umi_pack_desc d = descs[find_desc(descs, n_desc, blk)];
     const long total = (long)d.T * d.Kpad * d.Npad;
     if (d.k8 && d.T <= 9 && sizeof(T) == 2) {                 // (uniform per workgroup)
         pack_tiles_k8<T>(d, blk - d.blk0, (int)((total + PACK_BLOCK - 1) / PACK_BLOCK));
@@ -277,7 +259,7 @@ extern "C" int umi_optim_sgd_multi(const void* descs, int n_desc, int total_bloc
     if (!descs || n_desc <= 0 || total_blocks <= 0) return UMI_ERR_BADARG;
     SgdArgs a{(float)lr, (float)momentum, (float)(1.0 - dampening), (float)weight_decay, nesterov, first_step, nullptr};
     hipLaunchKernelGGL((optim_multi_kernel<false, SgdArgs>), dim3(total_blocks), dim3(256), 0, (hipStream_t)stream,
-                       (const OptDesc*)descs, n_desc, a);
+                       (const umi_optim_desc*)descs, n_desc, a);
     UMI_LAUNCH_CHECK();
     return UMI_OK;
 }
@@ -288,7 +270,7 @@ extern "C" int umi_optim_adam_multi(const void* descs, int n_desc, int total_blo
     AdamArgs a{(float)step_size, (float)(1.0 - beta1), (float)beta2, (float)(1.0 - beta2), (float)bc2_sqrt, (float)eps,
                (float)weight_decay, nullptr};
     hipLaunchKernelGGL((optim_multi_kernel<true, AdamArgs>), dim3(total_blocks), dim3(256), 0, (hipStream_t)stream,
-                       (const OptDesc*)descs, n_desc, a);
+                       (const umi_optim_desc*)descs, n_desc, a);
     UMI_LAUNCH_CHECK();
     return UMI_OK;
 }
@@ -333,7 +315,7 @@ extern "C" int umi_optim_sgd_multi_dev(const void* descs, int n_desc, int total_
     if (!descs || !hyper || n_desc <= 0 || total_blocks <= 0) return UMI_ERR_BADARG;
     SgdArgs a{0.f, (float)momentum, (float)(1.0 - dampening), (float)weight_decay, nesterov, first_step, (const Hyper*)hyper};
     hipLaunchKernelGGL((optim_multi_kernel<false, SgdArgs>), dim3(total_blocks), dim3(256), 0, (hipStream_t)stream,
-                       (const OptDesc*)descs, n_desc, a);
+                       (const umi_optim_desc*)descs, n_desc, a);
     UMI_LAUNCH_CHECK();
     return UMI_OK;
 }
@@ -344,7 +326,7 @@ extern "C" int umi_optim_adam_multi_dev(const void* descs, int n_desc, int total
     AdamArgs a{0.f, (float)(1.0 - beta1), (float)beta2, (float)(1.0 - beta2), 1.f, (float)eps, (float)weight_decay,
                (const Hyper*)hyper};
     hipLaunchKernelGGL((optim_multi_kernel<true, AdamArgs>), dim3(total_blocks), dim3(256), 0, (hipStream_t)stream,
-                       (const OptDesc*)descs, n_desc, a);
+                       (const umi_optim_desc*)descs, n_desc, a);
     UMI_LAUNCH_CHECK();
     return UMI_OK;
 }
@@ -353,10 +335,10 @@ extern "C" int umi_pack_kn_multi(const void* descs, int n_desc, int total_blocks
     if (!descs || n_desc <= 0 || total_blocks <= 0) return UMI_ERR_BADARG;
     if (dtype == UMI_F16)
         hipLaunchKernelGGL((pack_multi_kernel<half_t>), dim3(total_blocks), dim3(256), 0, (hipStream_t)stream,
-                           (const PackDesc*)descs, n_desc);
+                           (const umi_pack_desc*)descs, n_desc);
     else if (dtype == UMI_F32)
         hipLaunchKernelGGL((pack_multi_kernel<float>), dim3(total_blocks), dim3(256), 0, (hipStream_t)stream,
-                           (const PackDesc*)descs, n_desc);
+                           (const umi_pack_desc*)descs, n_desc);
     else return UMI_ERR_BADARG;
     UMI_LAUNCH_CHECK();
     return UMI_OK;

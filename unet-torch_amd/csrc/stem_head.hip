@@ -5,12 +5,9 @@
 //            BN+ReLU of the producer applied on load), data gradient (K = n_classes) and weight gradient.
 // One thread = one pixel x 8 channels (16-B accesses, 8 lanes per 128-B line); per-channel reductions go
 // through registers -> LDS -> one deterministic partial row per workgroup.
-#include "common.h"
+#include "kernels.h"
 
 typedef _Float16 half8 __attribute__((ext_vector_type(8)));
-
-void umi_launch_wgrad_reduce(const float* part, int splits, int RS, int Ci, int Co, float* dW, long s_co, long s_ci,
-                             long s_t, float scale, hipStream_t st);
 
 namespace {
 
@@ -487,86 +484,83 @@ bool groups_ok(int C) { return C % 8 == 0 && C / 8 <= 64 && (256 % (C / 8)) == 0
 }  // namespace
 
 // ---- dispatch helpers used by api.hip -------------------------------------------------------------------------
-bool umi_stem_fwd_ok(int Ci, int Co, int R, int S, int stride, int pad, int ldy, int in_dtype, int out_dtype, int flags,
-                     const float* bias) {
-    if (flags & (UMI_CONV_UPSAMPLE2 | UMI_CONV_FORCE_GENERIC)) return false;
-    return in_dtype == UMI_F16 && out_dtype == UMI_F16 && !bias && R == 3 && S == 3 && stride == 1 && pad == 1 &&
-           Ci >= 1 && Ci <= 4 && groups_ok(Co) && ldy % 8 == 0 && 9 * Ci * Co * 4 <= 48 * 1024;
+bool umi_stem_fwd_ok(const ConvFwdProblem& p) {
+    if (p.flags & (UMI_CONV_UPSAMPLE2 | UMI_CONV_FORCE_GENERIC)) return false;
+    return p.in_dtype == UMI_F16 && p.out_dtype == UMI_F16 && !p.has_bias && p.R == 3 && p.S == 3 && p.stride == 1 && p.pad == 1 &&
+           p.Ci >= 1 && p.Ci <= 4 && groups_ok(p.Co) && p.ldy % 8 == 0 && 9 * p.Ci * p.Co * 4 <= 48 * 1024;
 }
 int umi_stem_stat_rows(int N, int H, int W) { return (int)(((long)N * H * W + STEM_PPB - 1) / STEM_PPB); }
 
-int umi_stem_fwd(const void* x, int ldx, const void* tx, const void* wp, void* y, int ldy, float* part, int N, int H, int W,
-                 int Ci, int Co, hipStream_t s) {
+int umi_stem_fwd(const ConvFwdProblem& p, const void* x, const void* tx, const void* wp, void* y, float* part, hipStream_t s) {
     if (!al16(y)) return UMI_ERR_BADARG;
-    const int rows = umi_stem_stat_rows(N, H, W);
+    const int Ci = p.Ci, Co = p.Co;
+    const int rows = umi_stem_stat_rows(p.N, p.H, p.W);
     size_t smem = (size_t)9 * Ci * Co * 4;
     if (smem < 2 * 256 * 9 * 4) smem = 2 * 256 * 9 * 4;
-#define GO(CI) hipLaunchKernelGGL(stem3x3_fwd_kernel<CI>, dim3(rows), dim3(256), smem, s, (const half_t*)x, ldx, (const float4*)tx, (const half_t*)wp, (half_t*)y, ldy, part, N, H, W, Co)
+#define GO(CI) hipLaunchKernelGGL(stem3x3_fwd_kernel<CI>, dim3(rows), dim3(256), smem, s, (const half_t*)x, p.ldx, (const float4*)tx, (const half_t*)wp, (half_t*)y, p.ldy, part, p.N, p.H, p.W, Co)
     switch (Ci) { case 1: GO(1); break; case 2: GO(2); break; case 3: GO(3); break; default: GO(4); }
 #undef GO
     UMI_LAUNCH_CHECK();
     return UMI_OK;
 }
 
-bool umi_stem_wgrad_ok(int Ci, int Co, int R, int S, int stride, int pad, int lddy, int dtype, int flags, const void* txb) {
-    if (flags & UMI_CONV_FORCE_GENERIC) return false;
-    return dtype == UMI_F16 && !txb && R == 3 && S == 3 && stride == 1 && pad == 1 && Ci >= 1 && Ci <= 4 && groups_ok(Co) &&
-           Co <= 256 && lddy % 8 == 0;
+bool umi_stem_wgrad_ok(const WgradProblem& p) {
+    if (p.flags & UMI_CONV_FORCE_GENERIC) return false;
+    return p.dtype == UMI_F16 && !p.has_txb && p.R == 3 && p.S == 3 && p.stride == 1 && p.pad == 1 && p.Ci >= 1 && p.Ci <= 4 &&
+           groups_ok(p.Co) && p.Co <= 256 && p.lddy % 8 == 0;
 }
-size_t umi_stem_wgrad_ws_bytes(int N, int H, int W, int Ci, int Co) {
-    long blocks = ((long)N * H * W + WG_PPB - 1) / WG_PPB;
-    return (size_t)blocks * 9 * Ci * Co * sizeof(float);
+static size_t stem_wgrad_ws_bytes(long P, int Ci, int Co) {
+    return (size_t)((P + WG_PPB - 1) / WG_PPB) * 9 * Ci * Co * sizeof(float);
 }
-int umi_stem_wgrad(const void* x, int ldx, const void* txa, const void* dy, int lddy, float* dW, long s_co, long s_ci,
-                   long s_t, float out_scale, int N, int H, int W, int Ci, int Co, void* ws, size_t ws_bytes, hipStream_t s) {
-    if (ws_bytes < umi_stem_wgrad_ws_bytes(N, H, W, Ci, Co)) return UMI_ERR_WORKSPACE;
-    if (!al16(dy)) return UMI_ERR_BADARG;
+size_t umi_stem_wgrad_ws_bound(const WgradProblem& facts) {
+    WgradProblem p = facts;                    // the one geometry the kernel takes; the workspace does not depend on the row strides
+    p.stride = p.pad = 1; p.ldx = p.lddy = 8;
+    return umi_stem_wgrad_ok(p) ? stem_wgrad_ws_bytes((long)p.N * p.Ho * p.Wo, p.Ci, p.Co) : 0;
+}
+// bna: stage 3 of the following BatchNorm's backward formed on the fly (dy = gradient of the activated output)
+int umi_stem_wgrad(const WgradProblem& p, const void* x, const void* txa, const void* dy, const WgradOut& o, hipStream_t s,
+                   const WgradBnApply* bna) {
+    if (o.ws_bytes < stem_wgrad_ws_bytes((long)p.N * p.H * p.W, p.Ci, p.Co)) return UMI_ERR_WORKSPACE;
+    if (!al16(dy) || (bna && !al16(bna->y))) return UMI_ERR_BADARG;
+    const int N = p.N, H = p.H, W = p.W, Ci = p.Ci, Co = p.Co;
     int blocks = (int)(((long)N * H * W + WG_PPB - 1) / WG_PPB);
-    hipLaunchKernelGGL(stem3x3_wgrad_kernel<false>, dim3(blocks, Ci), dim3(256), 0, s, (const half_t*)x, ldx, (const float4*)txa,
-                       (const half_t*)dy, lddy, (float*)ws, N, H, W, Ci, Co, StemBna{});
+    if (!bna)
+        hipLaunchKernelGGL(stem3x3_wgrad_kernel<false>, dim3(blocks, Ci), dim3(256), 0, s, (const half_t*)x, p.ldx, (const float4*)txa,
+                           (const half_t*)dy, p.lddy, (float*)o.ws, N, H, W, Ci, Co, StemBna{});
+    else {
+        const StemBna ba{(const half_t*)bna->y, bna->ldy, (const float4*)bna->tx_bn, bna->rstd, bna->sum_dz, bna->sum_dzx, (long)N * H * W};
+        hipLaunchKernelGGL(stem3x3_wgrad_kernel<true>, dim3(blocks, Ci), dim3(256), 0, s, (const half_t*)x, p.ldx, (const float4*)txa,
+                           (const half_t*)dy, p.lddy, (float*)o.ws, N, H, W, Ci, Co, ba);
+    }
     UMI_LAUNCH_CHECK();
-    umi_launch_wgrad_reduce((const float*)ws, blocks, 9, Ci, Co, dW, s_co, s_ci, s_t, out_scale, s);
-    UMI_LAUNCH_CHECK();
-    return UMI_OK;
-}
-// the same with stage 3 of the following BatchNorm's backward formed on the fly (da = gradient of the activated output)
-int umi_stem_wgrad_bnapply(const void* x, int ldx, const void* txa, const void* da, int ldda, const void* y, int ldy,
-                           const void* tx_bn, const float* rstd, const float* sum_dz, const float* sum_dzx, float* dW, long s_co,
-                           long s_ci, long s_t, float out_scale, int N, int H, int W, int Ci, int Co, void* ws, size_t ws_bytes,
-                           hipStream_t s) {
-    if (ws_bytes < umi_stem_wgrad_ws_bytes(N, H, W, Ci, Co)) return UMI_ERR_WORKSPACE;
-    if (!al16(da) || !al16(y)) return UMI_ERR_BADARG;
-    int blocks = (int)(((long)N * H * W + WG_PPB - 1) / WG_PPB);
-    const StemBna ba{(const half_t*)y, ldy, (const float4*)tx_bn, rstd, sum_dz, sum_dzx, (long)N * H * W};
-    hipLaunchKernelGGL(stem3x3_wgrad_kernel<true>, dim3(blocks, Ci), dim3(256), 0, s, (const half_t*)x, ldx, (const float4*)txa,
-                       (const half_t*)da, ldda, (float*)ws, N, H, W, Ci, Co, ba);
-    UMI_LAUNCH_CHECK();
-    umi_launch_wgrad_reduce((const float*)ws, blocks, 9, Ci, Co, dW, s_co, s_ci, s_t, out_scale, s);
+    umi_launch_wgrad_reduce(blocks, 9, Ci, Co, o, s);
     UMI_LAUNCH_CHECK();
     return UMI_OK;
 }
 
 // head forward: fp16 in, 1x1, Co <= 8 (weights in generic [1][Ci][Co] fp16 packing); fp32 out (logits) or fp16 out (+ statistics)
-bool umi_head_fwd_ok(int Ci, int Co, int R, int S, int stride, int pad, int ldx, int in_dtype, int out_dtype, int flags) {
-    if (flags & (UMI_CONV_UPSAMPLE2 | UMI_CONV_FORCE_GENERIC)) return false;
-    return in_dtype == UMI_F16 && (out_dtype == UMI_F32 || out_dtype == UMI_F16) && R == 1 && S == 1 && stride == 1 &&
-           pad == 0 && Co >= 1 && Co <= 8 && groups_ok(Ci) && ldx % 8 == 0;
+bool umi_head_fwd_ok(const ConvFwdProblem& p) {
+    if (p.flags & (UMI_CONV_UPSAMPLE2 | UMI_CONV_FORCE_GENERIC)) return false;
+    return p.in_dtype == UMI_F16 && (p.out_dtype == UMI_F32 || p.out_dtype == UMI_F16) && p.R == 1 && p.S == 1 && p.stride == 1 &&
+           p.pad == 0 && p.Co >= 1 && p.Co <= 8 && groups_ok(p.Ci) && p.ldx % 8 == 0;
 }
 int umi_head_stat_rows(long P, int Ci) { return grid_for(P * (Ci / 8)); }
-int umi_head_fwd(const void* x, int ldx, const void* tx, const void* wp, const float* bias, void* y, int ldy, float* part,
-                 long P, int Ci, int Co, int out_dtype, hipStream_t s) {
+int umi_head_fwd(const ConvFwdProblem& p, const void* x, const void* tx, const void* wp, const float* bias, void* y, float* part,
+                 hipStream_t s) {
     if (!al16(x)) return UMI_ERR_BADARG;
+    const long P = (long)p.N * p.H * p.W;
+    const int Ci = p.Ci, out_dtype = p.out_dtype;
     if (part && out_dtype != UMI_F16) return UMI_ERR_UNSUPPORTED;
     int grid = grid_for(P * (Ci / 8));
-#define GO_(NC, TO, ST) hipLaunchKernelGGL((head1x1_fwd_kernel<NC, TO, ST>), dim3(grid), dim3(256), 0, s, (const half_t*)x, ldx, (const float4*)tx, (const half_t*)wp, bias, (TO*)y, ldy, part, P, Ci)
+#define GO_(NC, TO, ST) hipLaunchKernelGGL((head1x1_fwd_kernel<NC, TO, ST>), dim3(grid), dim3(256), 0, s, (const half_t*)x, p.ldx, (const float4*)tx, (const half_t*)wp, bias, (TO*)y, p.ldy, part, P, Ci)
 #define GO(NC)                                                          \
     do {                                                                \
         if (out_dtype == UMI_F32) GO_(NC, float, false);                \
         else if (part) GO_(NC, half_t, true);                           \
         else GO_(NC, half_t, false);                                    \
     } while (0)
-    switch (Co) { case 1: GO(1); break; case 2: GO(2); break; case 3: GO(3); break; case 4: GO(4); break;
-                  case 5: GO(5); break; case 6: GO(6); break; case 7: GO(7); break; default: GO(8); }
+    switch (p.Co) { case 1: GO(1); break; case 2: GO(2); break; case 3: GO(3); break; case 4: GO(4); break;
+                    case 5: GO(5); break; case 6: GO(6); break; case 7: GO(7); break; default: GO(8); }
 #undef GO
 #undef GO_
     UMI_LAUNCH_CHECK();
@@ -574,25 +568,27 @@ int umi_head_fwd(const void* x, int ldx, const void* tx, const void* wp, const f
 }
 
 // tiny-K pointwise conv (the head's data gradient): fp16 -> fp16, Ci <= 8, no transform / bias
-bool umi_smallk_fwd_ok(int Ci, int Co, int R, int S, int stride, int pad, int ldy, int in_dtype, int out_dtype, int flags,
-                       const void* tx, const float* bias) {
-    if (flags & (UMI_CONV_UPSAMPLE2 | UMI_CONV_FORCE_GENERIC)) return false;
-    return in_dtype == UMI_F16 && out_dtype == UMI_F16 && !tx && !bias && R == 1 && S == 1 && stride == 1 && pad == 0 &&
-           Ci >= 1 && Ci <= 8 && groups_ok(Co) && ldy % 8 == 0;
+bool umi_smallk_fwd_ok(const ConvFwdProblem& p) {
+    if (p.flags & (UMI_CONV_UPSAMPLE2 | UMI_CONV_FORCE_GENERIC)) return false;
+    return p.in_dtype == UMI_F16 && p.out_dtype == UMI_F16 && !p.has_tx && !p.has_bias && p.R == 1 && p.S == 1 && p.stride == 1 &&
+           p.pad == 0 && p.Ci >= 1 && p.Ci <= 8 && groups_ok(p.Co) && p.ldy % 8 == 0;
 }
-int umi_smallk_fwd(const void* x, int ldx, const void* wp, void* y, int ldy, long P, int Ci, int Co, hipStream_t s) {
+int umi_smallk_fwd(const ConvFwdProblem& p, const void* x, const void* wp, void* y, hipStream_t s) {
     if (!al16(y)) return UMI_ERR_BADARG;
+    const long P = (long)p.N * p.H * p.W;
+    const int Co = p.Co;
     int grid = grid_for(P * (Co / 8));
-#define GO(NC) hipLaunchKernelGGL(smallk1x1_fwd_kernel<NC>, dim3(grid), dim3(256), 0, s, (const half_t*)x, ldx, (const half_t*)wp, (half_t*)y, ldy, P, Co)
-    switch (Ci) { case 1: GO(1); break; case 2: GO(2); break; case 3: GO(3); break; case 4: GO(4); break;
-                  case 5: GO(5); break; case 6: GO(6); break; case 7: GO(7); break; default: GO(8); }
+#define GO(NC) hipLaunchKernelGGL(smallk1x1_fwd_kernel<NC>, dim3(grid), dim3(256), 0, s, (const half_t*)x, p.ldx, (const half_t*)wp, (half_t*)y, p.ldy, P, Co)
+    switch (p.Ci) { case 1: GO(1); break; case 2: GO(2); break; case 3: GO(3); break; case 4: GO(4); break;
+                    case 5: GO(5); break; case 6: GO(6); break; case 7: GO(7); break; default: GO(8); }
 #undef GO
     UMI_LAUNCH_CHECK();
     return UMI_OK;
 }
 
 int umi_smallk_bnred_rows(long P, int Co) { return grid_for(P * (Co / 8)); }
-// dW != NULL: also the head's weight gradient dW[k * s_co + c * s_ci] = out_scale * sum_p tx(ybn[p][c]) * x[p][k]; ws >= rows * Co * Ci floats
+// dW != NULL: also the head's weight gradient dW[k * s_co + c * s_ci] = out_scale * sum_p tx(ybn[p][c]) * x[p][k]; ws >= rows * Co * Ci
+// floats, Co <= 256 (the caller's refusal: api.hip)
 int umi_smallk_fwd_bnred(const void* x, int ldx, const void* wp, void* y, int ldy, const void* ybn, int ldybn, const void* txbn,
                          const float* rstd, float* part, long P, int Ci, int Co, hipStream_t s, float* dW, long s_co, long s_ci,
                          float out_scale, void* ws, size_t ws_bytes) {
@@ -600,7 +596,7 @@ int umi_smallk_fwd_bnred(const void* x, int ldx, const void* wp, void* y, int ld
     int grid = grid_for(P * (Co / 8));
     float* wpart = nullptr;
     if (dW) {
-        if (!ws || ws_bytes < (size_t)grid * Co * Ci * sizeof(float) || Co > 256) return UMI_ERR_WORKSPACE;
+        if (!ws || ws_bytes < (size_t)grid * Co * Ci * sizeof(float)) return UMI_ERR_WORKSPACE;
         wpart = (float*)ws;
     }
 #define GO(NC) hipLaunchKernelGGL(smallk1x1_bnred_kernel<NC>, dim3(grid), dim3(256), 0, s, (const half_t*)x, ldx, (const half_t*)wp, (half_t*)y, ldy, (const half_t*)ybn, ldybn, (const float4*)txbn, rstd, part, P, Co, wpart)
@@ -616,10 +612,10 @@ int umi_smallk_fwd_bnred(const void* x, int ldx, const void* wp, void* y, int ld
     return UMI_OK;
 }
 
-bool umi_head_wgrad_ok(int Ci, int Co, int R, int S, int stride, int pad, int ldx, int dtype, int flags, const void* txb) {
-    if (flags & UMI_CONV_FORCE_GENERIC) return false;
-    return dtype == UMI_F16 && !txb && R == 1 && S == 1 && stride == 1 && pad == 0 && Co >= 1 && Co <= 8 && groups_ok(Ci) &&
-           Ci <= 256 && ldx % 8 == 0;
+bool umi_head_wgrad_ok(const WgradProblem& p) {
+    if (p.flags & UMI_CONV_FORCE_GENERIC) return false;
+    return p.dtype == UMI_F16 && !p.has_txb && p.R == 1 && p.S == 1 && p.stride == 1 && p.pad == 0 && p.Co >= 1 && p.Co <= 8 &&
+           groups_ok(p.Ci) && p.Ci <= 256 && p.ldx % 8 == 0;
 }
 // pixels per workgroup of the head weight gradient: ~2048 workgroups where the tensor allows it (a fixed 4096 left the 64x64
 // maps of the attention gates with 16 workgroups: 249 us for 34 MB), whole multiples of 256 pixels
@@ -629,22 +625,27 @@ static int head_wgrad_ppb(long P) {
     if (ppb > WG_PPB) ppb = WG_PPB;
     return (int)ppb;
 }
-size_t umi_head_wgrad_ws_bytes(long P, int Ci, int Co) {
+static size_t head_wgrad_ws_bytes(long P, int Ci, int Co) {
     const int ppb = head_wgrad_ppb(P);
     return (size_t)((P + ppb - 1) / ppb) * Ci * Co * sizeof(float);
 }
-int umi_head_wgrad(const void* x, int ldx, const void* txa, const void* dy, int lddy, float* dW, long s_co, long s_ci,
-                   long s_t, float out_scale, long P, int Ci, int Co, void* ws, size_t ws_bytes, hipStream_t s) {
-    if (ws_bytes < umi_head_wgrad_ws_bytes(P, Ci, Co)) return UMI_ERR_WORKSPACE;
+size_t umi_head_wgrad_ws_bound(const WgradProblem& facts) {
+    WgradProblem p = facts;
+    p.stride = 1; p.pad = 0; p.ldx = p.lddy = 8;
+    return umi_head_wgrad_ok(p) ? head_wgrad_ws_bytes((long)p.N * p.Ho * p.Wo, p.Ci, p.Co) : 0;
+}
+int umi_head_wgrad(const WgradProblem& p, const void* x, const void* txa, const void* dy, const WgradOut& o, hipStream_t s) {
+    if (o.ws_bytes < head_wgrad_ws_bytes((long)p.N * p.H * p.W, p.Ci, p.Co)) return UMI_ERR_WORKSPACE;
     if (!al16(x)) return UMI_ERR_BADARG;
-    const int ppb = head_wgrad_ppb(P);
+    const long P = (long)p.N * p.H * p.W;
+    const int Ci = p.Ci, ppb = head_wgrad_ppb(P);
     int blocks = (int)((P + ppb - 1) / ppb);
-#define GO(NC) hipLaunchKernelGGL(head1x1_wgrad_kernel<NC>, dim3(blocks), dim3(256), 0, s, (const half_t*)x, ldx, (const float4*)txa, (const half_t*)dy, lddy, (float*)ws, P, Ci, ppb)
-    switch (Co) { case 1: GO(1); break; case 2: GO(2); break; case 3: GO(3); break; case 4: GO(4); break;
-                  case 5: GO(5); break; case 6: GO(6); break; case 7: GO(7); break; default: GO(8); }
+#define GO(NC) hipLaunchKernelGGL(head1x1_wgrad_kernel<NC>, dim3(blocks), dim3(256), 0, s, (const half_t*)x, p.ldx, (const float4*)txa, (const half_t*)dy, p.lddy, (float*)o.ws, P, Ci, ppb)
+    switch (p.Co) { case 1: GO(1); break; case 2: GO(2); break; case 3: GO(3); break; case 4: GO(4); break;
+                    case 5: GO(5); break; case 6: GO(6); break; case 7: GO(7); break; default: GO(8); }
 #undef GO
     UMI_LAUNCH_CHECK();
-    umi_launch_wgrad_reduce((const float*)ws, blocks, 1, Ci, Co, dW, s_co, s_ci, s_t, out_scale, s);
+    umi_launch_wgrad_reduce(blocks, 1, Ci, p.Co, o, s);
     UMI_LAUNCH_CHECK();
     return UMI_OK;
 }

@@ -3,7 +3,7 @@
 // attention, bilinear x2 (align_corners) upsampling, broadcast adds -- forward and backward, fp32 math on
 // fp32/fp16 NHWC storage ([B,1,N,C] for token tensors).  Correctness-first generic kernels: every reduction is
 // fixed-order (no atomics); they are HBM- or latency-bound and small next to the convolutions / GEMMs.
-#include "common.h"
+#include "kernels.h"
 
 namespace {
 
@@ -68,18 +68,7 @@ __global__ __launch_bounds__(256) void wstd_bwd_kernel(const float* __restrict__
 
 // All StdConv2d weights of a model in ONE launch each way (a R50 hybrid has 52 of them; one launch per conv costs more in
 // launch gaps than in work): workgroup = one output channel of one conv, found by binary search over the descriptor table.
-struct WstdDesc {          // mirrors umi_wstd_desc
-    const float* w;
-    float* ws;
-    float* rstd;
-    long off;              // element offset of this conv in the flat gradient buffers of the backward launch
-    int Co, K;
-    float eps;
-    int blk0;              // first workgroup (= output-channel row) of this conv
-    float* dw;             // backward: where this conv's parameter gradient goes (NULL: dw_base + off)
-};
-
-__device__ inline int wstd_find(const WstdDesc* d, int n, int blk) {
+__device__ inline int wstd_find(const umi_wstd_desc* d, int n, int blk) {
     int lo = 0, hi = n - 1;
     while (lo < hi) {
         const int mid = (lo + hi + 1) >> 1;
@@ -88,9 +77,9 @@ __device__ inline int wstd_find(const WstdDesc* d, int n, int blk) {
     return lo;
 }
 
-__global__ __launch_bounds__(256) void wstd_fwd_multi_kernel(const WstdDesc* __restrict__ descs, int n_desc) {
+__global__ __launch_bounds__(256) void wstd_fwd_multi_kernel(const umi_wstd_desc* __restrict__ descs, int n_desc) {
     __shared__ float sh[16];
-    const WstdDesc d = descs[wstd_find(descs, n_desc, blockIdx.x)];
+    const umi_wstd_desc d = descs[wstd_find(descs, n_desc, blockIdx.x)];
     const int co = blockIdx.x - d.blk0, K = d.K;
     const float* p = d.w + (long)co * K;                    // same arithmetic, in the same order, as wstd_fwd_kernel
     float s = 0.f, q = 0.f;
@@ -104,10 +93,10 @@ __global__ __launch_bounds__(256) void wstd_fwd_multi_kernel(const WstdDesc* __r
     if (threadIdx.x == 0) d.rstd[co] = r;
 }
 
-__global__ __launch_bounds__(256) void wstd_bwd_multi_kernel(const WstdDesc* __restrict__ descs, int n_desc,
+__global__ __launch_bounds__(256) void wstd_bwd_multi_kernel(const umi_wstd_desc* __restrict__ descs, int n_desc,
                                                              const float* __restrict__ g_base, float* __restrict__ dw_base) {
     __shared__ float sh[16];
-    const WstdDesc d = descs[wstd_find(descs, n_desc, blockIdx.x)];
+    const umi_wstd_desc d = descs[wstd_find(descs, n_desc, blockIdx.x)];
     const int co = blockIdx.x - d.blk0, K = d.K;
     const float* wh = d.ws + (long)co * K;
     const float* gp = g_base + d.off + (long)co * K;
@@ -597,38 +586,6 @@ __global__ void bilinear2x_bwd_kernel(const T* __restrict__ dy, int lddy, T* __r
 
 }  // namespace
 
-void umi_launch_reduce_rows2(const float* ws, int rows, int C, float* out0, float* out1, float scale, hipStream_t s);
-// groupnorm_f16.hip
-int umi_gn_splits(int N, long HW);
-bool umi_gn_fwd_f16v(const void* x, int ldx, const float* gamma, const float* beta, const void* res, int ldr, void* y, int ldy,
-                     float* mean, float* rstd, int relu, int N, long HW, int C, int G, float eps, float* ws, hipStream_t s);
-bool umi_gn_bwd_f16v(const void* dy, int lddy, const void* y, int ldy, const void* x, int ldx, const float* mean,
-                     const float* rstd, const float* gamma, int relu, void* dx, int lddx, void* dres, int lddr, int N, long HW,
-                     int C, int G, float* part, float* ws, hipStream_t s);
-void umi_gn_param_grads_launch(int n, const float* const* parts, const int* Cs, int N, float* const* dgammas, float* const* dbetas,
-                               float scale, hipStream_t s);
-// elementwise_tu_f16.hip
-bool umi_ew_f16v(int mode, const void* x, int ldx, const void* g, int ldg, void* y, int ldy, long M, int C, long bcast_rows,
-                 hipStream_t s);
-bool umi_pool3s2_fwd_f16v(const void* x, int ldx, void* y, int ldy, void* idx, int N, int H, int W, int C, hipStream_t s);
-bool umi_pool3s2_bwd_f16v(const void* dy, int lddy, const void* idx, void* dx, int lddx, int N, int H, int W, int C, hipStream_t s);
-bool umi_dropout_f16v(const void* x, int ldx, void* y, int ldy, void* mask, int backward, float p, unsigned seed, long M, int C,
-                      const void* tx, const unsigned* seed_dev, hipStream_t s);
-bool umi_dropout_fused_f16v(const void* x, int ldx, void* y, int ldy, void* mask, int backward, float p, unsigned seed, long M,
-                            int C, const unsigned* seed_dev, const void* aux, int ldaux, int gelu, hipStream_t s);
-int umi_ln_bwd_rows_f16v();
-bool umi_ln_bwd_f16v(const void* dy, int lddy, const void* x, int ldx, const float* gamma, const float* mean, const float* rstd,
-                     void* dx, int lddx, float* part, long M, int C, hipStream_t s);
-bool umi_bilinear2x_f16v(const void* x, int ldx, const void* tx, void* y, int ldy, int backward, int N, int H, int W, int C,
-                         hipStream_t s);
-// attention_mfma.hip
-bool umi_attn_mfma_ok(int D, int ld, int ldo, int dtype, const void* a, const void* b, const void* c);
-int umi_attn_fwd_mfma(const void* q, const void* k, const void* v, int ld, void* o, int ldo, float* lse, int B, int N, int Hh,
-                      hipStream_t s);
-int umi_attn_bwd_mfma(const void* q, const void* k, const void* v, int ld, const void* o, const void* dO, int ldo,
-                      const float* lse, void* dq, void* dk, void* dv, int ldd, float* delta, int B, int N, int Hh,
-                      hipStream_t s);
-
 #define DT_SWITCH(dtype, CALL_F32, CALL_F16)             \
     if ((dtype) == UMI_F32) { CALL_F32; }                \
     else if ((dtype) == UMI_F16) { CALL_F16; }           \
@@ -649,14 +606,14 @@ extern "C" int umi_wstd_bwd(const float* wstd, const float* rstd, const float* g
 
 extern "C" int umi_wstd_fwd_multi(const void* descs, int n_desc, int total_rows, umi_stream_t st) {
     if (!descs || n_desc <= 0 || total_rows <= 0) return UMI_ERR_BADARG;
-    hipLaunchKernelGGL(wstd_fwd_multi_kernel, dim3(total_rows), dim3(256), 0, (hipStream_t)st, (const WstdDesc*)descs, n_desc);
+    hipLaunchKernelGGL(wstd_fwd_multi_kernel, dim3(total_rows), dim3(256), 0, (hipStream_t)st, (const umi_wstd_desc*)descs, n_desc);
     UMI_LAUNCH_CHECK();
     return UMI_OK;
 }
 extern "C" int umi_wstd_bwd_multi(const void* descs, int n_desc, int total_rows, const float* g_base, float* dw_base,
                                   umi_stream_t st) {
     if (!descs || !g_base || n_desc <= 0 || total_rows <= 0) return UMI_ERR_BADARG;      // dw_base may be NULL if every entry has .dw
-    hipLaunchKernelGGL(wstd_bwd_multi_kernel, dim3(total_rows), dim3(256), 0, (hipStream_t)st, (const WstdDesc*)descs, n_desc,
+    hipLaunchKernelGGL(wstd_bwd_multi_kernel, dim3(total_rows), dim3(256), 0, (hipStream_t)st, (const umi_wstd_desc*)descs, n_desc,
                        g_base, dw_base);
     UMI_LAUNCH_CHECK();
     return UMI_OK;

@@ -15,7 +15,7 @@
 // the way), then per 16-pixel k-step and tap column the wave reuses 6 input-row fragments for the
 // 3 taps x 4 rows.  Split-K over pixel tiles; partial slabs [split][tap][ci][co] fp32 are reduced in
 // fixed order (deterministic) by wgrad_reduce_kernel into the parameter's own layout.
-#include "common.h"
+#include "kernels.h"
 #include <type_traits>
 #include <stdlib.h>
 
@@ -23,9 +23,6 @@ typedef _Float16 half8 __attribute__((ext_vector_type(8)));
 typedef _Float16 half4 __attribute__((ext_vector_type(4)));
 typedef short short4v __attribute__((ext_vector_type(4)));
 typedef float floatx16 __attribute__((ext_vector_type(16)));
-
-void umi_launch_wgrad_reduce(const float* part, int splits, int RS, int Ci, int Co, float* dW, long s_co, long s_ci,
-                             long s_t, float scale, hipStream_t st);
 
 #ifdef UMI_STAMP
 // diagnostic build only (tools/exp_stamp_wgrad.py): per-wave cycle sums of the tile-loop segments
@@ -1004,13 +1001,14 @@ void plan1(long M, int Ci, int Co, int TM, int* tiles_total, int* splits, int* t
 
 }  // namespace
 
-bool umi_wgrad1x1_mfma_ok(long M, int Ci, int Co, int R, int S, int stride, int pad, int ldx, int lddy, int dtype, int flags,
-                          const void* txb) {
-    if (flags & UMI_CONV_FORCE_GENERIC) return false;
-    if (dtype != UMI_F16 || txb) return false;
-    if (R != 1 || S != 1 || stride != 1 || pad != 0) return false;
-    if (Ci % 8 || Co % 8 || Ci < 16 || Co < 16 || ldx % 8 || lddy % 8) return false;   // partial 64-channel tiles are masked
-    if (M * (long)(ldx > lddy ? ldx : lddy) * 2 >= 0x7FFFFFF0L) return false;     // 32-bit buffer offsets
+// Workspace bounds (kernels.h): each fills in the geometry its kernel takes and the smallest row strides the predicate
+// accepts (its 32-bit offset tests only get stricter with wider rows); the slab count does not depend on the strides.
+bool umi_wgrad1x1_mfma_ok(const WgradProblem& p) {
+    if (p.flags & UMI_CONV_FORCE_GENERIC) return false;
+    if (p.dtype != UMI_F16 || p.has_txb) return false;
+    if (p.R != 1 || p.S != 1 || p.stride != 1 || p.pad != 0) return false;
+    if (p.Ci % 8 || p.Co % 8 || p.Ci < 16 || p.Co < 16 || p.ldx % 8 || p.lddy % 8) return false;   // partial 64-channel tiles are masked
+    if ((long)p.N * p.H * p.W * (long)(p.ldx > p.lddy ? p.ldx : p.lddy) * 2 >= 0x7FFFFFF0L) return false;     // 32-bit buffer offsets
     return true;
 }
 // 128 x 128 channel tiles only when there are enough of them to fill the chip without a deep split-K: every split is a
@@ -1019,29 +1017,34 @@ bool umi_wgrad1x1_mfma_ok(long M, int Ci, int Co, int R, int S, int stride, int 
 static int wgrad1x1_tm(int Ci, int Co) {
     return (Ci % 128 == 0 && Co % 128 == 0 && (long)(Ci / 128) * (Co / 128) >= 96) ? 128 : 64;
 }
-
-size_t umi_wgrad1x1_mfma_ws_bytes(long M, int Ci, int Co) {
+// slabs of the pointwise (taps = 1) / tap-gather kernel over M output pixels
+static size_t wgrad1x1_ws_bytes(long M, int Ci, int Co, int taps) {
     int tt, splits, tps;
-    plan1(M, Ci, Co, wgrad1x1_tm(Ci, Co), &tt, &splits, &tps);
-    return (size_t)splits * Ci * Co * sizeof(float);
+    plan1(M, Ci, Co, wgrad1x1_tm(Ci, Co), &tt, &splits, &tps, taps);
+    return (size_t)splits * taps * Ci * Co * sizeof(float);
+}
+size_t umi_wgrad1x1_mfma_ws_bound(const WgradProblem& facts) {
+    WgradProblem p = facts;
+    p.H = p.Ho; p.W = p.Wo; p.stride = 1; p.pad = 0; p.ldx = p.lddy = 8;
+    return umi_wgrad1x1_mfma_ok(p) ? wgrad1x1_ws_bytes((long)p.N * p.Ho * p.Wo, p.Ci, p.Co, 1) : 0;
 }
 
-int umi_wgrad1x1_mfma(const void* x, int ldx, const void* txa, const void* dy, int lddy, float* dW, long s_co, long s_ci,
-                      long s_t, float out_scale, long M, int Ci, int Co, void* ws, size_t ws_bytes, hipStream_t s) {
-    const int TM = wgrad1x1_tm(Ci, Co);
+int umi_wgrad1x1_mfma(const WgradProblem& p, const void* x, const void* txa, const void* dy, const WgradOut& o, hipStream_t s) {
+    const long M = (long)p.N * p.H * p.W;
+    const int Ci = p.Ci, Co = p.Co, TM = wgrad1x1_tm(Ci, Co);
     int tt, splits, tps;
     plan1(M, Ci, Co, TM, &tt, &splits, &tps);
-    if (ws_bytes < (size_t)splits * Ci * Co * sizeof(float)) return UMI_ERR_WORKSPACE;
+    if (o.ws_bytes < (size_t)splits * Ci * Co * sizeof(float)) return UMI_ERR_WORKSPACE;
     if (((uintptr_t)x | (uintptr_t)dy) & 15) return UMI_ERR_BADARG;
     const int n_co_t = (Co + TM - 1) / TM;
     dim3 grid(((Ci + TM - 1) / TM) * n_co_t, splits), block(256);
     const WGeo geo{1, 1, 1, 1, 1, 1, 0};
-#define GO(T_, H_) hipLaunchKernelGGL((wgrad1x1_mfma_kernel<T_, H_, false>), grid, block, 0, s, (const half_t*)x, ldx, (const float4*)txa, (const half_t*)dy, lddy, (float*)ws, M, Ci, Co, tt, tps, n_co_t, geo, WNoGroup{})
+#define GO(T_, H_) hipLaunchKernelGGL((wgrad1x1_mfma_kernel<T_, H_, false>), grid, block, 0, s, (const half_t*)x, p.ldx, (const float4*)txa, (const half_t*)dy, p.lddy, (float*)o.ws, M, Ci, Co, tt, tps, n_co_t, geo, WNoGroup{})
     if (TM == 128) { if (txa) GO(128, true); else GO(128, false); }
     else { if (txa) GO(64, true); else GO(64, false); }
 #undef GO
     UMI_LAUNCH_CHECK();
-    umi_launch_wgrad_reduce((const float*)ws, splits, 1, Ci, Co, dW, s_co, s_ci, s_t, out_scale, s);
+    umi_launch_wgrad_reduce(splits, 1, Ci, Co, o, s);
     UMI_LAUNCH_CHECK();
     return UMI_OK;
 }
@@ -1075,137 +1078,113 @@ int umi_wgrad1x1_mfma_group(int n, const void* const* x, int ldx, const void* co
 }
 
 // ---- tap-gather weight gradient (strided / padded R x S convs) ----------------------------------------------------------
-bool umi_wgrad_gather_mfma_ok(int N, int H, int W, int Ci, int Co, int R, int S, int stride, int pad, int Ho, int Wo, int ldx,
-                              int lddy, int dtype, int flags, const void* txb) {
-    if (flags & UMI_CONV_FORCE_GENERIC) return false;
-    if (dtype != UMI_F16 || txb) return false;
-    if (R * S > 49 || stride < 1 || pad < 0) return false;
-    if (Ho != (H + 2 * pad - R) / stride + 1 || Wo != (W + 2 * pad - S) / stride + 1) return false;
-    if (Ci % 64 || Co % 64 || ldx % 8 || lddy % 8) return false;
-    if ((long)N * Ho * Wo * lddy * 2 >= 0x7FFFFFF0L || (long)N * H * W * ldx * 2 >= 0x7FFFFFF0L) return false;
+static bool wgrad_gather_shape_ok(const WgradProblem& p) {          // everything but the geometry and the row strides
+    if (p.flags & UMI_CONV_FORCE_GENERIC) return false;
+    if (p.dtype != UMI_F16 || p.has_txb) return false;
+    return p.R * p.S <= 49 && p.Ci % 64 == 0 && p.Co % 64 == 0;
+}
+bool umi_wgrad_gather_mfma_ok(const WgradProblem& p) {
+    if (!wgrad_gather_shape_ok(p) || p.stride < 1 || p.pad < 0) return false;
+    if (p.Ho != (p.H + 2 * p.pad - p.R) / p.stride + 1 || p.Wo != (p.W + 2 * p.pad - p.S) / p.stride + 1) return false;
+    if (p.ldx % 8 || p.lddy % 8) return false;
+    if ((long)p.N * p.Ho * p.Wo * p.lddy * 2 >= 0x7FFFFFF0L || (long)p.N * p.H * p.W * p.ldx * 2 >= 0x7FFFFFF0L) return false;
     return true;
 }
-
-size_t umi_wgrad_gather_mfma_ws_bytes(int N, int Ho, int Wo, int Ci, int Co, int R, int S) {
-    int tt, splits, tps;
-    plan1((long)N * Ho * Wo, Ci, Co, wgrad1x1_tm(Ci, Co), &tt, &splits, &tps, R * S);
-    return (size_t)splits * R * S * Ci * Co * sizeof(float);
+size_t umi_wgrad_gather_mfma_ws_bound(const WgradProblem& p) {      // any stride and padding: the slabs depend on neither
+    return wgrad_gather_shape_ok(p) ? wgrad1x1_ws_bytes((long)p.N * p.Ho * p.Wo, p.Ci, p.Co, p.R * p.S) : 0;
 }
 
-int umi_wgrad_gather_mfma(const void* x, int ldx, const void* txa, const void* dy, int lddy, float* dW, long s_co, long s_ci,
-                          long s_t, float out_scale, int N, int H, int W, int Ci, int Co, int R, int S, int stride, int pad,
-                          int Ho, int Wo, void* ws, size_t ws_bytes, hipStream_t s) {
-    const int TM = wgrad1x1_tm(Ci, Co), taps = R * S;
-    const long M = (long)N * Ho * Wo;
+int umi_wgrad_gather_mfma(const WgradProblem& p, const void* x, const void* txa, const void* dy, const WgradOut& o, hipStream_t s) {
+    const int Ci = p.Ci, Co = p.Co, TM = wgrad1x1_tm(Ci, Co), taps = p.R * p.S;
+    const long M = (long)p.N * p.Ho * p.Wo;
     int tt, splits, tps;
     plan1(M, Ci, Co, TM, &tt, &splits, &tps, taps);
-    if (ws_bytes < (size_t)splits * taps * Ci * Co * sizeof(float)) return UMI_ERR_WORKSPACE;
+    if (o.ws_bytes < (size_t)splits * taps * Ci * Co * sizeof(float)) return UMI_ERR_WORKSPACE;
     if (((uintptr_t)x | (uintptr_t)dy) & 15) return UMI_ERR_BADARG;
     const int n_co_t = Co / TM;
     dim3 grid((Ci / TM) * n_co_t, splits, taps), block(256);
-    const WGeo geo{Ho, Wo, H, W, S, stride, pad};
-#define GO(T_, H_) hipLaunchKernelGGL((wgrad1x1_mfma_kernel<T_, H_, true>), grid, block, 0, s, (const half_t*)x, ldx, (const float4*)txa, (const half_t*)dy, lddy, (float*)ws, M, Ci, Co, tt, tps, n_co_t, geo, WNoGroup{})
+    const WGeo geo{p.Ho, p.Wo, p.H, p.W, p.S, p.stride, p.pad};
+#define GO(T_, H_) hipLaunchKernelGGL((wgrad1x1_mfma_kernel<T_, H_, true>), grid, block, 0, s, (const half_t*)x, p.ldx, (const float4*)txa, (const half_t*)dy, p.lddy, (float*)o.ws, M, Ci, Co, tt, tps, n_co_t, geo, WNoGroup{})
     if (TM == 128) { if (txa) GO(128, true); else GO(128, false); }
     else { if (txa) GO(64, true); else GO(64, false); }
 #undef GO
     UMI_LAUNCH_CHECK();
-    umi_launch_wgrad_reduce((const float*)ws, splits, taps, Ci, Co, dW, s_co, s_ci, s_t, out_scale, s);
+    umi_launch_wgrad_reduce(splits, taps, Ci, Co, o, s);
     UMI_LAUNCH_CHECK();
     return UMI_OK;
 }
 
-bool umi_wgradT_mfma_ok(int H, int W, int Ci, int Co, int R, int S, int stride, int pad, int Ho, int Wo, int ldx,
-                        int lddy, int dtype, int flags, const void* txa) {
-    if (flags & UMI_CONV_FORCE_GENERIC) return false;
-    if (dtype != UMI_F16 || txa) return false;
-    if (R != 2 || S != 2 || stride != 2 || pad != 0 || H != 2 * Ho || W != 2 * Wo) return false;
-    if (Ci % 64 || Co % 64 || ldx % 8 || lddy % 8) return false;
+// ---- ConvTranspose2d(2,2) weight gradient: x = d(up) [N, 2Ho, 2Wo, Ci], dy = the ConvT's input [N, Ho, Wo, Co] -----------------
+bool umi_wgradT_mfma_ok(const WgradProblem& p) {
+    if (p.flags & UMI_CONV_FORCE_GENERIC) return false;
+    if (p.dtype != UMI_F16 || p.has_txa) return false;
+    if (p.R != 2 || p.S != 2 || p.stride != 2 || p.pad != 0 || p.H != 2 * p.Ho || p.W != 2 * p.Wo) return false;
+    if (p.Ci % 64 || p.Co % 64 || p.ldx % 8 || p.lddy % 8) return false;
     return true;
 }
-
-size_t umi_wgradT_mfma_ws_bytes(int N, int Ho, int Wo, int Ci, int Co) {
+size_t umi_wgradT_mfma_ws_bound(const WgradProblem& facts) {
+    WgradProblem p = facts;
+    p.H = 2 * p.Ho; p.W = 2 * p.Wo; p.stride = 2; p.pad = 0; p.ldx = p.lddy = 8;
+    if (!umi_wgradT_mfma_ok(p)) return 0;
     int tx_, ty_, tt, splits, tps;
-    planT(N, Ho, Wo, Ci, Co, &tx_, &ty_, &tt, &splits, &tps);
-    return (size_t)splits * 4 * Ci * Co * sizeof(float) + (size_t)splits * 2 * Ci * sizeof(float);    // slabs + bias-gradient rows
+    planT(p.N, p.Ho, p.Wo, p.Ci, p.Co, &tx_, &ty_, &tt, &splits, &tps);
+    return (size_t)splits * 4 * p.Ci * p.Co * sizeof(float) + (size_t)splits * 2 * p.Ci * sizeof(float);    // slabs + bias-gradient rows
 }
 
-// one-shot request (set by umi_conv_wgrad_bias, consumed by the next umi_wgradT_mfma on this thread): also produce the hi-res
-// operand's column sums, scaled like dW
-static thread_local float* g_wgT_bias = nullptr;
-void umi_wgradT_bias_set(float* bias_out) { g_wgT_bias = bias_out; }
-void umi_launch_reduce_rows2(const float* ws, int rows, int C, float* out0, float* out1, float scale, hipStream_t s);
-
-int umi_wgradT_mfma(const void* x, int ldx, const void* dy, int lddy, const void* txb, float* dW, long s_co, long s_ci,
-                    long s_t, float out_scale, int N, int Ho, int Wo, int Ci, int Co, void* ws, size_t ws_bytes,
-                    hipStream_t s) {
+// o.convT_bias: also the hi-res operand's column sums, scaled like dW
+int umi_wgradT_mfma(const WgradProblem& p, const void* x, const void* dy, const void* txb, const WgradOut& o, hipStream_t s) {
+    const int N = p.N, Ho = p.Ho, Wo = p.Wo, Ci = p.Ci, Co = p.Co;
     int tiles_x, tiles_y, tiles_total, splits, tps;
     planT(N, Ho, Wo, Ci, Co, &tiles_x, &tiles_y, &tiles_total, &splits, &tps);
-    float* const bias_out = g_wgT_bias;
-    g_wgT_bias = nullptr;
-    if (ws_bytes < (size_t)splits * 4 * Ci * Co * sizeof(float) + (bias_out ? (size_t)splits * 2 * Ci * sizeof(float) : 0)) return UMI_ERR_WORKSPACE;
+    float* const bias_out = o.convT_bias;
+    if (o.ws_bytes < (size_t)splits * 4 * Ci * Co * sizeof(float) + (bias_out ? (size_t)splits * 2 * Ci * sizeof(float) : 0)) return UMI_ERR_WORKSPACE;
     if (((uintptr_t)x | (uintptr_t)dy) & 15) return UMI_ERR_BADARG;
-    float* const cpart = bias_out ? (float*)ws + (size_t)splits * 4 * Ci * Co : nullptr;
+    float* const cpart = bias_out ? (float*)o.ws + (size_t)splits * 4 * Ci * Co : nullptr;
     const bool wide = Co % 128 == 0;
     const int n_cy_t = wide ? Co / 128 : Co / 64;
     dim3 grid((Ci / 64) * n_cy_t, splits), block(256);
 #define UMI_GO_T(HT, YH_)                                                                                        \
-    hipLaunchKernelGGL((wgradT2x2_mfma_kernel<HT, YH_>), grid, block, 0, s, (const half_t*)x, ldx, (const half_t*)dy, lddy, \
-                       (const float4*)txb, (float*)ws, N, Ho, Wo, Ci, Co, tiles_x, tiles_y, tiles_total, tps, n_cy_t, cpart)
+    hipLaunchKernelGGL((wgradT2x2_mfma_kernel<HT, YH_>), grid, block, 0, s, (const half_t*)x, p.ldx, (const half_t*)dy, p.lddy, \
+                       (const float4*)txb, (float*)o.ws, N, Ho, Wo, Ci, Co, tiles_x, tiles_y, tiles_total, tps, n_cy_t, cpart)
     if (txb) { if (wide) UMI_GO_T(true, 2); else UMI_GO_T(true, 1); }
     else { if (wide) UMI_GO_T(false, 2); else UMI_GO_T(false, 1); }
 #undef UMI_GO_T
     if (bias_out) {
         UMI_LAUNCH_CHECK();
-        umi_launch_reduce_rows2(cpart, splits, Ci, bias_out, nullptr, out_scale, s);
+        umi_launch_reduce_rows2(cpart, splits, Ci, bias_out, nullptr, o.out_scale, s);
     }
     UMI_LAUNCH_CHECK();
-    umi_launch_wgrad_reduce((const float*)ws, splits, 4, Ci, Co, dW, s_co, s_ci, s_t, out_scale, s);
+    umi_launch_wgrad_reduce(splits, 4, Ci, Co, o, s);
     UMI_LAUNCH_CHECK();
     return UMI_OK;
 }
 
-bool umi_wgrad3x3_mfma_ok(int N, int H, int W, int Ci, int Co, int R, int S, int stride, int pad, int Ho, int Wo,
-                          int ldx, int lddy, int dtype, int flags, const void* txb) {
-    if (flags & UMI_CONV_FORCE_GENERIC) return false;
-    if (dtype != UMI_F16 || txb) return false;
-    if (R != 3 || S != 3 || stride != 1 || pad != 1 || Ho != H || Wo != W) return false;
-    if (Ci % 8 || Co % 8 || ldx % 8 || lddy % 8) return false;      // partial 64-channel tiles are masked in the kernel
-    if ((long)H * W * (ldx > lddy ? ldx : lddy) * 2 >= 0x7FFFFFF0L) return false;   // 32-bit offsets inside one image
+// ---- 3x3 / stride 1 / pad 1 ------------------------------------------------------------------------------------------------------
+bool umi_wgrad3x3_mfma_ok(const WgradProblem& p) {
+    if (p.flags & UMI_CONV_FORCE_GENERIC) return false;
+    if (p.dtype != UMI_F16 || p.has_txb) return false;
+    if (p.R != 3 || p.S != 3 || p.stride != 1 || p.pad != 1 || p.Ho != p.H || p.Wo != p.W) return false;
+    if (p.Ci % 8 || p.Co % 8 || p.ldx % 8 || p.lddy % 8) return false;      // partial 64-channel tiles are masked in the kernel
+    if ((long)p.H * p.W * (p.ldx > p.lddy ? p.ldx : p.lddy) * 2 >= 0x7FFFFFF0L) return false;   // 32-bit offsets inside one image
     return true;
 }
-
-size_t umi_wgrad3x3_mfma_ws_bytes(int N, int H, int W, int Ci, int Co) {
+size_t umi_wgrad3x3_mfma_ws_bound(const WgradProblem& facts) {
+    WgradProblem p = facts;
+    p.H = p.Ho; p.W = p.Wo; p.stride = p.pad = 1; p.ldx = p.lddy = 8;
+    if (!umi_wgrad3x3_mfma_ok(p)) return 0;
     int tx_, ty_, tt, splits, tps;
-    plan(N, H, W, Ci, Co, &tx_, &ty_, &tt, &splits, &tps);
-    return (size_t)splits * 9 * Ci * Co * sizeof(float);
+    plan(p.N, p.H, p.W, p.Ci, p.Co, &tx_, &ty_, &tt, &splits, &tps);
+    return (size_t)splits * 9 * p.Ci * p.Co * sizeof(float);
 }
 
-static int wgrad3x3_launch(const void* x, int ldx, const void* txa, const void* dy, int lddy, float* dW, long s_co,
-                           long s_ci, long s_t, float out_scale, int N, int H, int W, int Ci, int Co, void* ws,
-                           size_t ws_bytes, hipStream_t s, const BnApply* bna);
-
-int umi_wgrad3x3_mfma(const void* x, int ldx, const void* txa, const void* dy, int lddy, float* dW, long s_co,
-                      long s_ci, long s_t, float out_scale, int N, int H, int W, int Ci, int Co, void* ws,
-                      size_t ws_bytes, hipStream_t s) {
-    return wgrad3x3_launch(x, ldx, txa, dy, lddy, dW, s_co, s_ci, s_t, out_scale, N, H, W, Ci, Co, ws, ws_bytes, s, nullptr);
-}
-
-// weight gradient fused with stage 3 of the BatchNorm + ReLU backward of the conv's own output (see BnApply above)
-int umi_wgrad3x3_mfma_bnapply(const void* x, int ldx, const void* txa, const void* da, int ldda, const void* ybn, int ldybn,
-                              const void* txbn, const float* rstd, const float* sum_dz, const float* sum_dzx, void* dz,
-                              int lddz, float* dW, long s_co, long s_ci, long s_t, float out_scale, int N, int H, int W, int Ci,
-                              int Co, void* ws, size_t ws_bytes, hipStream_t s) {
-    const BnApply b{(const half_t*)ybn, ldybn, (const float4*)txbn, rstd, sum_dz, sum_dzx, (long)N * H * W,
-                    (half_t*)dz, lddz};
-    return wgrad3x3_launch(x, ldx, txa, da, ldda, dW, s_co, s_ci, s_t, out_scale, N, H, W, Ci, Co, ws, ws_bytes, s, &b);
-}
-
-static int wgrad3x3_launch(const void* x, int ldx, const void* txa, const void* dy, int lddy, float* dW, long s_co,
-                           long s_ci, long s_t, float out_scale, int N, int H, int W, int Ci, int Co, void* ws,
-                           size_t ws_bytes, hipStream_t s, const BnApply* bna) {
+// bna: fused with stage 3 of the BatchNorm + ReLU backward of the conv's own output (see BnApply above)
+int umi_wgrad3x3_mfma(const WgradProblem& p, const void* x, const void* txa, const void* dy, const WgradOut& o, hipStream_t s,
+                      const WgradBnApply* bna) {
+    const int N = p.N, H = p.H, W = p.W, Ci = p.Ci, Co = p.Co, ldx = p.ldx, lddy = p.lddy;
+    void* const ws = o.ws;
     int tiles_x, tiles_y, tiles_total, splits, tps;
     plan(N, H, W, Ci, Co, &tiles_x, &tiles_y, &tiles_total, &splits, &tps);
-    if (ws_bytes < (size_t)splits * 9 * Ci * Co * sizeof(float)) return UMI_ERR_WORKSPACE;
+    if (o.ws_bytes < (size_t)splits * 9 * Ci * Co * sizeof(float)) return UMI_ERR_WORKSPACE;
     if (((uintptr_t)x | (uintptr_t)dy) & 15) return UMI_ERR_BADARG;
     const int n_co_t = (Co + 63) / 64;
     dim3 grid(((Ci + 63) / 64) * n_co_t, splits), block(256);
@@ -1226,7 +1205,9 @@ static int wgrad3x3_launch(const void* x, int ldx, const void* txa, const void* 
         }();
         if (attr_rc) return attr_rc;
         dim3 block_ws(512);
-        const BnApply ba = bna ? *bna : BnApply{nullptr, 0, nullptr, nullptr, nullptr, nullptr, 1, nullptr, 0};
+        const BnApply ba = bna ? BnApply{(const half_t*)bna->y, bna->ldy, (const float4*)bna->tx_bn, bna->rstd, bna->sum_dz, bna->sum_dzx,
+                                         (long)N * H * W, (half_t*)bna->dz, bna->lddz}
+                               : BnApply{nullptr, 0, nullptr, nullptr, nullptr, nullptr, 1, nullptr, 0};
 #define GO_WS(HT, BN_)                                                                                              \
         hipLaunchKernelGGL((wgrad3x3_ws_kernel<HT, BN_>), grid, block_ws, dyn, s, (const half_t*)x, ldx, (const float4*)txa,   \
                            (const half_t*)dy, lddy, (float*)ws, N, H, W, Ci, Co, tiles_x, tiles_y, tiles_total, tps, n_co_t, fast_ci, ba)
@@ -1242,7 +1223,7 @@ static int wgrad3x3_launch(const void* x, int ldx, const void* txa, const void* 
                            (const half_t*)dy, lddy, (float*)ws, N, H, W, Ci, Co, tiles_x, tiles_y, tiles_total, tps,
                            n_co_t, fast_ci);
     UMI_LAUNCH_CHECK();
-    umi_launch_wgrad_reduce((const float*)ws, splits, 9, Ci, Co, dW, s_co, s_ci, s_t, out_scale, s);
+    umi_launch_wgrad_reduce(splits, 9, Ci, Co, o, s);
     UMI_LAUNCH_CHECK();
     return UMI_OK;
 }
