@@ -324,7 +324,11 @@ int umi_elementwise(int mode, const void* x, int ldx, const void* g, int ldg, vo
 
 /* Dropout (vit_seg_modeling.py:103,151; U-Net Down / Up, Model.py:37,80-81): forward writes a byte mask (own counter-based
  * RNG stream) and y = keep ? tx(x) / (1-p) : 0 (tx: nullable consumer transform of x, forward only); backward (x = dy)
- * reuses the mask.  seed_dev (nullable): device counter added into the stream seed inside the kernel, so a step replayed
+ * reuses the mask.  0 <= p <= 1 (UMI_ERR_BADARG otherwise, NaN included), here and in umi_dropout_fused / umi_linear_fused;
+ * p == 1 keeps nothing, as nn.Dropout(1.0): y = 0 (the residual alone in the fused forms), a zero gradient, nothing non-finite.
+ * Stream: keep = u >= p with u = (hash32(e, seed') >> 8) * 2^-24, e = row * C + col (dense index: no ld enters; its high word
+ * is xor-ed into seed'), seed' = seed + seed_dev[0] * 0x9E3779B9; tests/dropout_stream.py states it in full.
+ * seed_dev (nullable): device counter added into the stream seed inside the kernel, so a step replayed
  * from a captured HIP graph still draws a fresh mask every replay. */
 int umi_dropout(const void* x, int ldx, void* y, int ldy, void* mask, int backward, float p, unsigned seed, long M, int C,
                 int dtype, const void* tx, const unsigned* seed_dev, umi_stream_t stream);

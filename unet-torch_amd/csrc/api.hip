@@ -25,7 +25,7 @@ extern "C" const char* umi_arch(void) { return "gfx950"; }
 extern "C" int umi_linear_fused(const void* x, int ldx, const void* wp8, const float* bias, void* y, int ldy, long M, int Ci,
                                 int Co, int epi, float p, unsigned seed, const unsigned* seed_dev, void* mask, const void* aux,
                                 int ldaux, void* y2, int ldy2, int dtype, umi_stream_t stream) {
-    if (!x || !wp8 || !y || !mask || M <= 0 || M >= (1L << 31) || Ci <= 0 || Co <= 0 || p < 0.f || p >= 1.f) return UMI_ERR_BADARG;
+    if (!x || !wp8 || !y || !mask || M <= 0 || M >= (1L << 31) || Ci <= 0 || Co <= 0 || !(p >= 0.f && p <= 1.f)) return UMI_ERR_BADARG;
     if (epi != 1 && epi != 2) return UMI_ERR_BADARG;
     if ((epi == 1 && (!y2 || ldy2 % 8)) || (epi == 2 && (!aux || ldaux % 8))) return UMI_ERR_BADARG;
     const ConvFwdProblem pr = fwd_problem(1, 1, (int)M, Ci, Co, 1, 1, 1, 0, 1, (int)M, ldx, ldy, dtype, dtype, 0, false, bias != nullptr, false);

@@ -353,6 +353,8 @@ __device__ __forceinline__ unsigned hash32(unsigned a, unsigned b) {           /
     return x;
 }
 // fwd (g == nullptr): keep = u >= p ; y = keep ? x/(1-p) : 0 ; mask byte written.   bwd: y = g * mask/(1-p)
+// p == 1 (nn.Dropout(1.0)): u < 1 always, so nothing is kept and the infinite scale is never multiplied in (a select, not
+// a product with the mask): zeros forward and backward
 template <typename T>
 __global__ void dropout_kernel(const T* __restrict__ x, int ldx, T* __restrict__ y, int ldy, unsigned char* __restrict__ mask,
                                int bwd, float p, unsigned seed, long M, int C, const float4* __restrict__ tx,
@@ -789,7 +791,7 @@ extern "C" int umi_elementwise(int mode, const void* x, int ldx, const void* g, 
 extern "C" int umi_dropout_fused(const void* x, int ldx, void* y, int ldy, void* mask, int backward, float p, unsigned seed, long M,
                                  int C, int dtype, const unsigned* seed_dev, const void* aux, int ldaux, int gelu,
                                  umi_stream_t st) {
-    if (!x || !y || !mask || M <= 0 || C <= 0 || p < 0.f || p >= 1.f) return UMI_ERR_BADARG;
+    if (!x || !y || !mask || M <= 0 || C <= 0 || !(p >= 0.f && p <= 1.f)) return UMI_ERR_BADARG;
     if (dtype != UMI_F16 ||
         !umi_dropout_fused_f16v(x, ldx, y, ldy, mask, backward, p, seed, M, C, seed_dev, aux, ldaux, gelu, (hipStream_t)st))
         return UMI_ERR_UNSUPPORTED;
@@ -799,7 +801,7 @@ extern "C" int umi_dropout_fused(const void* x, int ldx, void* y, int ldy, void*
 
 extern "C" int umi_dropout(const void* x, int ldx, void* y, int ldy, void* mask, int backward, float p, unsigned seed, long M,
                            int C, int dtype, const void* tx, const unsigned* seed_dev, umi_stream_t st) {
-    if (!x || !y || !mask || p < 0.f || p >= 1.f) return UMI_ERR_BADARG;
+    if (!x || !y || !mask || !(p >= 0.f && p <= 1.f)) return UMI_ERR_BADARG;
     if (dtype == UMI_F16 && umi_dropout_f16v(x, ldx, y, ldy, mask, backward, p, seed, M, C, tx, seed_dev, (hipStream_t)st)) {
         UMI_LAUNCH_CHECK();
         return UMI_OK;
