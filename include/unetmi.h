@@ -628,6 +628,27 @@ int umi_split_classes(const unsigned char* map, unsigned char* planes, int N, in
 int umi_class_center_lists(const int* counts, const unsigned char* label_class, const int* area, const long long* sum_y,
                            const long long* sum_x, int* centers, int* c_count, int N, int cap, int n_classes, umi_stream_t stream);
 
+/* Training-batch transform (csrc/augment.hip; statement and rule: umi/augment.py): the reference's Dataset.transform for a batch.
+ * Per sample params[n] = {mode, k, axis, angle} (int32) and geom[n] = {M00, M01, M10, M11, off0, off1} (float64, formed on the
+ * host as scipy.ndimage.rotate forms them), both on the device and read there: mode 1 = np.flip(np.rot90(x, k), axis) (an odd k
+ * needs H == W, else the sample comes out 0), mode 2 = SciPy's order-0 rotation (y = (off0 + r * M00) + q * M01 and
+ * x = (off1 + r * M10) + q * M11 in float64 without contraction; 0 unless 0 <= y <= H - 1 and 0 <= x <= W - 1, else
+ * src[floor(y + 0.5)][floor(x + 0.5)]), any other mode = identity.  dtype 0 = uint8, 1 = float32.  C <= 4, N <= 65535,
+ * H * W < 2^30.  Nothing synchronises with the host, and no value of params / geom can form an address outside its sample.
+ *   umi_augment_geometry: src[N][H][W][C] -> dst, same shape and type.
+ *   umi_augment_labels: src[N][H][W] -> dst[N][out_h][out_w] (dst_dtype 0 = float32, 1 = int64) = the order-0 zoom
+ *     (umi_zoom_nearest's rule) of the augmented map as one gather; value = (float)v * scale, truncated for int64.
+ *   umi_augment_znorm: src[N][H][W][C] -> out[N][C][H][W] float32 = (augmented - mean) / std per (sample, channel), float64
+ *     statistics in a fixed summation order (exact integer sums for uint8, which limits H * W to 2^23; two passes for float32),
+ *     channels reversed when reverse_channels.  The augmented image is not written.  ws: umi_augment_znorm_ws_bytes(N) bytes. */
+int umi_augment_geometry(const void* src, int dtype, void* dst, const int* params, const double* geom, int N, int H, int W, int C,
+                         umi_stream_t stream);
+int umi_augment_labels(const void* src, int src_dtype, void* dst, int dst_dtype, float scale, const int* params, const double* geom,
+                       int N, int H, int W, int out_h, int out_w, umi_stream_t stream);
+size_t umi_augment_znorm_ws_bytes(int N);
+int umi_augment_znorm(const void* src, int dtype, float* out_nchw, const int* params, const double* geom, int N, int H, int W, int C,
+                      int reverse_channels, void* ws, size_t ws_bytes, umi_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -27,6 +27,11 @@ per-task epoch losses divided by the step count twice, no validation record, che
 mode the epoch gate is a device flag the loss kernel reads (rewritten in place at the start of each epoch, so the graphs of
 the full and the ragged batch serve both gate values), and an LR change made by a scheduler object is written into the device
 LR block in place (umi.optim push_lr), so the captured step sees it.
+`Trainer(..., batch_transform=tf)` (keyword-only; `umi.augment.TrainTransform` or any callable of its signature): the loaders
+then yield RAW batches -- uint8 / float32 HWC (or HW) images and a label map or a tuple of them, as the reference's
+`Dataset.__getitem__` reads them before `transform` -- which are moved to the device as they are and transformed there, with
+freshly drawn augmentation parameters in the train phase and none in the validation phase, before the step and outside any
+captured graph.
 `lr_scheduler=True` (what the reference's train.py passes) crashes the reference in its first validation after epoch 5
 (`True.step`); here train() raises NotImplementedError before the first step whenever the run would reach that point.
 The remaining epoch loops of the reference (uncertainty-weighted multi-task, CLTR, Topo losses) are out of scope and raise.
@@ -51,7 +56,8 @@ _OTHER = ('CLTR',)
 
 class Trainer():
     def __init__(self, model, model_type, dtype, device, output_save_dir, dataloaders, batch_size, optimizer,
-                 patience, num_epochs, loss_function, accuracy_metric, lr_scheduler=None, start_epoch=1, *, graph=None):
+                 patience, num_epochs, loss_function, accuracy_metric, lr_scheduler=None, start_epoch=1, *, graph=None,
+                 batch_transform=None):
         self.model = model
         self.model_type = model_type
         self.dtype = dtype
@@ -80,6 +86,7 @@ class Trainer():
         self.grad_sync = None         # optional callable run between backward and optimizer.step (DDP)
         self.graph = (os.environ.get("UMI_TRAINER_GRAPH") == "1") if graph is None else bool(graph)
         self._graphs, self._seen_shapes, self._dev_sched, self._side = {}, set(), False, None
+        self.batch_transform = batch_transform
         # multi_task_trainRatio: epoch > 5 (host, and in graph mode a device flag), ratioAccuracy of the last step
         self._ratio_gate, self._gate_dev, self._ratio = False, None, None
         self.alpha, self.alpha_list = None, []
@@ -104,7 +111,19 @@ class Trainer():
         raise ValueError('Invalid model_type "%s"' % self.model_type)
 
     # ------------------------------------------------------------------------------------
-    def _to_device(self, inputs, labels):
+    def _transform_batch(self, inputs, labels, train):
+        """Raw batch -> network batch with self.batch_transform, on self.device."""
+        from umi.augment import no_augmentation
+        multi = isinstance(labels, (list, tuple))
+        inputs = inputs.to(self.device)
+        maps = [l.to(self.device) for l in labels] if multi else labels.to(self.device)
+        params = None if train else no_augmentation(inputs.shape[0])       # None: the transform draws them
+        inputs, out = self.batch_transform(inputs, maps, params)
+        return inputs, (tuple(out) if multi else out)
+
+    def _to_device(self, inputs, labels, train=True):
+        if self.batch_transform is not None:
+            inputs, labels = self._transform_batch(inputs, labels, train)
         if isinstance(labels, (list, tuple)):                    # multi-task batches: labels = (label1, label2)
             return inputs.to(self.device).type(self.dtype), tuple(l.to(self.device).type(self.dtype) for l in labels)
         return inputs.to(self.device).type(self.dtype), labels.to(self.device).type(self.dtype)
@@ -193,7 +212,7 @@ class Trainer():
         return outs[0].clone()            # the static output buffer is overwritten by the next replay
 
     def eval_step(self, inputs, labels):
-        inputs, labels = self._to_device(inputs, labels)
+        inputs, labels = self._to_device(inputs, labels, train=False)
         with torch.no_grad():
             out, loss = self._forward_loss(inputs, labels)
             if self.model_type in _MULTI:                        # the reference reports no validation score there (:853)

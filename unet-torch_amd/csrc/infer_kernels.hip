@@ -6,6 +6,7 @@
 //   umi_argmax_mask   NCHW fp32 logits -> uint8 class mask; the first maximum wins (torch.argmax).  softmax is monotone,
 //                     so the reference's softmax before the argmax is skipped.
 #include "common.h"
+#include "zoom_nearest_rule.h"
 
 namespace {
 
@@ -299,13 +300,6 @@ __global__ __launch_bounds__(256) void binary_mask_kernel(const float* __restric
     }
 }
 
-// source index of output i, or -1 where SciPy's mode 'constant' gives 0
-__device__ inline int zn_src(int i, int n_in, int n_out) {
-    const double x = (double)i * (n_out > 1 ? (double)(n_in - 1) / (double)(n_out - 1) : 0.0);
-    if (x < 0.0 || x > (double)(n_in - 1)) return -1;
-    const int s = (int)floor(x + 0.5);
-    return s > n_in - 1 ? n_in - 1 : s;
-}
 
 // one thread = 16 bytes of one output row (blockIdx.y = row, blockIdx.z = image); `al`: every row of `out` starts 16-byte aligned
 template <typename T>

@@ -205,6 +205,12 @@ SIGNATURES = {
     "umi_split_classes": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
     "umi_class_center_lists": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
                                        c_void_p]),
+    "umi_augment_geometry": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
+    "umi_augment_labels": (c_int, [c_void_p, c_int, c_void_p, c_int, c_float, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int,
+                                   c_void_p]),
+    "umi_augment_znorm_ws_bytes": (c_size_t, [c_int]),
+    "umi_augment_znorm": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p,
+                                  c_size_t, c_void_p]),
 }
 
 for _name, (_res, _args) in SIGNATURES.items():
