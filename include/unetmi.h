@@ -41,10 +41,16 @@ enum { UMI_CONV_UPSAMPLE2 = 1,   /* ConvTranspose2d(k=2,s=2): tap t=(dy,dx) scat
        UMI_CONV_FORCE_GENERIC = 2, /* never take the MFMA fast path (used by tests to cross-check it) */
        UMI_CONV_DGRAD_STRIDED = 4, /* data gradient of a stride>1 conv: x = dy [N,H,W,Ci:=Co_fwd], y = dx [N,Ho,Wo,Co:=Ci_fwd]
                                       with (R,S,stride,pad) of the FORWARD conv; weights packed [R*S][Co_fwd][Ci_fwd] unflipped */
-       UMI_CONV_ACCUMULATE = 8     /* y += conv(...) instead of y = conv(...): the second gradient contribution of a tensor with two
+       UMI_CONV_ACCUMULATE = 8,    /* y += conv(...) instead of y = conv(...): the second gradient contribution of a tensor with two
                                       consumers (attention gate, reference Model.py:268-289: g and x each feed two branches).  Only
                                       the pointwise / tap-gather MFMA kernel implements it: umi_conv_fwd_plan and umi_conv_fwd return
-                                      UMI_ERR_UNSUPPORTED for any other problem, nothing is written */ };
+                                      UMI_ERR_UNSUPPORTED for any other problem, nothing is written */
+       UMI_CONV_F32_MFMA = 16      /* opt-in: an fp32 3x3 / stride 1 / pad 1 conv (forward, data gradient, weight gradient) runs on the
+                                      fp32-input matrix-core instruction (v_mfma_f32_32x32x2_f32: one fp32 rounding per product, an
+                                      fmaf chain like the generic kernel's in another order).  Taken when in and out are UMI_F32, no
+                                      bias, none of the flags above, Ci % 8 == Co % 8 == 0 and ldx % 4 == ldy % 4 == 0 (weight
+                                      gradient: no transform on dy either); IGNORED otherwise: the call, umi_conv_fwd_plan and
+                                      umi_conv_wgrad_ws_bytes then answer exactly as without it */ };
 
 int umi_version(void);
 const char* umi_arch(void);          /* "gfx950" */
@@ -101,6 +107,9 @@ int umi_linear_fused(const void* x, int ldx, const void* wp8, const float* bias,
  *         and R * S <= 49: stride >= 2, UMI_CONV_DGRAD_STRIDED, or UMI_CONV_UPSAMPLE2 with R = S = 2 -- as long as two source
  *         images stay within 31-bit byte offsets (2 * H * W * ldx * 2 < 0x7FFFFFF0).  (It writes no statistics: umi_conv_fwd
  *         with `stat_part` is UMI_ERR_UNSUPPORTED there.)
+ * With UMI_CONV_F32_MFMA, where that flag's conditions hold, the fp32 matrix-core 3x3 kernel is named instead: *layout = 0 (it
+ * reads umi_pack_kn's [tap][k][n], the flipped / transposed pack for a data gradient) and *stat_rows = one row per 8 x 32 pixel
+ * tile, N * ceil(H / 8) * ceil(W / 32); a plan that names it is never followed by UMI_ERR_UNSUPPORTED from umi_conv_fwd.
  * *stat_rows = rows of `stat_part` the call will write.  UMI_ERR_UNSUPPORTED: UMI_CONV_ACCUMULATE off the pointwise kernel. */
 int umi_conv_fwd_plan(int N, int H, int W, int Ci, int Co, int R, int S, int stride, int pad,
                       int ldx, int ldy, int in_dtype, int out_dtype, int flags, int has_bias,
@@ -195,7 +204,8 @@ int umi_bn_bwd_from_partials(const float* part, int rows, int C, float* sum_dz, 
 /* Weight gradient of umi_conv_fwd (autograd of the reference convs):
  *   dW[co*s_co + ci*s_ci + t*s_t] = out_scale * sum_{n,ho,wo} txa(x[...,ci]) * txb(dy[n,ho,wo,co])
  * fp32 output in the parameter's own layout (OIHW: s_co=Ci*R*S, s_ci=R*S, s_t=1).
- * Deterministic: split-K partial slabs in `ws`, reduced in fixed order. */
+ * Deterministic: split-K partial slabs in `ws`, reduced in fixed order.  `flags`: UMI_CONV_FORCE_GENERIC, UMI_CONV_F32_MFMA
+ * (pass the same flags to umi_conv_wgrad_ws_bytes: the fp32 matrix-core kernel splits the pixels its own way). */
 size_t umi_conv_wgrad_ws_bytes(int N, int Ho, int Wo, int Ci, int Co, int R, int S, int dtype, int flags);
 int umi_conv_wgrad(const void* x, int ldx, const void* txa, const void* dy, int lddy, const void* txb,
                    float* dW, long s_co, long s_ci, long s_t, float out_scale,

@@ -11,7 +11,8 @@ only own parameters and buffers.
 
 Build-specific, keyword-only extras (never positional, so reference call sites are
 unaffected): `compute_dtype` = "fp16" (fp16 storage + fp32 accumulate, loss-scaled
-gradients; default, env UMI_COMPUTE_DTYPE) or "fp32" (parity mode).
+gradients; default, env UMI_COMPUTE_DTYPE), "fp32" (parity mode) or "fp32_mfma" ("fp32" in storage,
+state and every kernel but the 3x3 convolutions, which run on the fp32-input matrix-core kernels).
 
 There is no CPU path here: inputs must live on the MI355X ("cuda" in PyTorch-ROCm naming).
 """
@@ -28,10 +29,16 @@ def _resolve_dtype(compute_dtype):
     if isinstance(name, torch.dtype):
         return name
     table = {"fp16": torch.float16, "float16": torch.float16, "half": torch.float16,
-             "fp32": torch.float32, "float32": torch.float32}
+             "fp32": torch.float32, "float32": torch.float32, "fp32_mfma": torch.float32}
     if name not in table:
-        raise ValueError(f"compute_dtype must be fp16 or fp32, got {name!r}")
+        raise ValueError(f"compute_dtype must be fp16, fp32 or fp32_mfma, got {name!r}")
     return table[name]
+
+
+def _resolve_conv3x3_flags(compute_dtype):
+    """Kernel flags the tape adds to its 3x3 convolutions: "fp32_mfma" opts into libunetmi's fp32 matrix-core kernels."""
+    name = compute_dtype or os.environ.get("UMI_COMPUTE_DTYPE", "fp16")
+    return G.L.CONV_F32_MFMA if name == "fp32_mfma" else 0
 
 
 class _TapeFunction(torch.autograd.Function):
@@ -95,6 +102,7 @@ def _run_tape(module, inputs, build, tape_cls=None, dtype=None):
                         loss_scale=G.default_loss_scale(dtype, N * H * W),
                         grad_sink=getattr(module, "_umi_grad_sink", None) if record else None,
                         pack_cache=G.pack_cache_of(module), seed=seed, seed_dev=seed_dev)
+        tape.conv3x3_flags = _resolve_conv3x3_flags(getattr(module, "_compute_dtype", None))
         acts = [tape.input_nchw(x, needs_grad=need) for x, need in zip(inputs, in_needs)]
         out_act = build(tape, *acts)
         tape.finish_forward()

@@ -70,9 +70,10 @@ extern "C" int umi_conv_fwd_plan(int N, int H, int W, int Ci, int Co, int R, int
     const ConvFwdPath path = umi_conv_fwd_path(fwd_problem(N, H, W, Ci, Co, R, S, stride, pad, Ho, Wo, ldx, ldy, in_dtype, out_dtype,
                                                            flags, false, has_bias != 0, true));
     if ((flags & UMI_CONV_ACCUMULATE) && path != FWD_MFMA1X1) return UMI_ERR_UNSUPPORTED;
-    if (layout) *layout = (path == FWD_MFMA3X3 || path == FWD_MFMA1X1) ? 1 : 0;
+    if (layout) *layout = (path == FWD_MFMA3X3 || path == FWD_MFMA1X1) ? 1 : 0;      // (the fp32 matrix-core kernel reads layout 0)
     if (stat_rows)
-        *stat_rows = path == FWD_MFMA3X3 ? umi_conv3x3_mfma_stat_rows(N, H, W, Co)
+        *stat_rows = path == FWD_MFMA3X3_F32 ? umi_conv3x3_f32_mfma_stat_rows(N, H, W)
+                     : path == FWD_MFMA3X3 ? umi_conv3x3_mfma_stat_rows(N, H, W, Co)
                      : path == FWD_STEM  ? umi_stem_stat_rows(N, H, W)
                      : path == FWD_HEAD  ? umi_head_stat_rows((long)N * H * W, Ci)
                                          : umi_cdiv((long)N * Ho * Wo, 64);
@@ -185,9 +186,10 @@ extern "C" int umi_conv_fwd(const void* x, int ldx, const void* tx, const void* 
     if (!x || !wp || !y || N <= 0 || H <= 0 || W <= 0 || Ci <= 0 || Co <= 0 || R <= 0 || S <= 0 || stride <= 0 ||
         Ho <= 0 || Wo <= 0 || ldx < Ci || ldy < Co || out_H <= 0 || out_W <= 0)
         return UMI_ERR_BADARG;
-    const ConvFwdProblem p = fwd_problem(N, H, W, Ci, Co, R, S, stride, pad, Ho, Wo, ldx, ldy, in_dtype, out_dtype, flags,
-                                         tx != nullptr, bias != nullptr, stat_part != nullptr);
+    ConvFwdProblem p = fwd_problem(N, H, W, Ci, Co, R, S, stride, pad, Ho, Wo, ldx, ldy, in_dtype, out_dtype, flags,
+                                   tx != nullptr, bias != nullptr, stat_part != nullptr);
     const ConvFwdPath path = umi_conv_fwd_path(p);
+    if (path != FWD_MFMA3X3_F32) p.flags = flags &= ~UMI_CONV_F32_MFMA;      // refused there: the call runs without the flag
     // only the pointwise / tap-gather MFMA kernel adds into y
     if ((flags & UMI_CONV_ACCUMULATE) && (stat_part || path != FWD_MFMA1X1)) return UMI_ERR_UNSUPPORTED;
     if (flags & UMI_CONV_DGRAD_STRIDED) {
@@ -203,6 +205,7 @@ extern "C" int umi_conv_fwd(const void* x, int ldx, const void* tx, const void* 
     }
     const hipStream_t s = (hipStream_t)stream;
     switch (path) {
+    case FWD_MFMA3X3_F32: return umi_conv3x3_f32_mfma(p, x, tx, wp, y, stat_part, s);
     case FWD_MFMA3X3:
         // the caller packed the weights for this path (umi_conv_fwd_plan said layout 1): misalignment is an error,
         // not a reason to silently reinterpret them
@@ -230,8 +233,10 @@ static WgradProblem wgrad_problem(int N, int H, int W, int Ci, int Co, int R, in
 
 extern "C" size_t umi_conv_wgrad_ws_bytes(int N, int Ho, int Wo, int Ci, int Co, int R, int S, int dtype, int flags) {
     // the call picks its path from more arguments than this query has: size for whichever path could need most
-    const WgradProblem p = wgrad_problem(N, 0, 0, Ci, Co, R, S, 0, 0, Ho, Wo, 0, 0, dtype, flags, false, false);
-    const size_t bounds[] = {umi_wgrad3x3_mfma_ws_bound(p), umi_wgrad1x1_mfma_ws_bound(p), umi_wgradT_mfma_ws_bound(p),
+    WgradProblem p = wgrad_problem(N, 0, 0, Ci, Co, R, S, 0, 0, Ho, Wo, 0, 0, dtype, flags, false, false);
+    const size_t f32_mfma = umi_wgrad3x3_f32_mfma_ws_bound(p);
+    p.flags &= ~UMI_CONV_F32_MFMA;                       // the call may still find the flag refused (strides, a transform on dy)
+    const size_t bounds[] = {f32_mfma, umi_wgrad3x3_mfma_ws_bound(p), umi_wgrad1x1_mfma_ws_bound(p), umi_wgradT_mfma_ws_bound(p),
                              umi_wgrad_gather_mfma_ws_bound(p), umi_stem_wgrad_ws_bound(p), umi_head_wgrad_ws_bound(p),
                              umi_root_wgrad_ws_bound(p), umi_head3_wgrad_ws_bound(p), umi_conv_wgrad_generic_ws_bound(p)};
     size_t most = 0;
@@ -240,11 +245,14 @@ extern "C" size_t umi_conv_wgrad_ws_bytes(int N, int Ho, int Wo, int Ci, int Co,
 }
 
 // The weight gradient of problem `p` on `path` (= umi_conv_wgrad_path(p)), with the sinks of `o`.
-static int conv_wgrad(const WgradProblem& p, WgradPath path, const void* x, const void* txa, const void* dy, const void* txb,
+static int conv_wgrad(const WgradProblem& asked, WgradPath path, const void* x, const void* txa, const void* dy, const void* txb,
                       const WgradOut& o, hipStream_t s) {
+    WgradProblem p = asked;
+    if (path != WGRAD_MFMA3X3_F32) p.flags &= ~UMI_CONV_F32_MFMA;      // refused there: the call runs without the flag
     if (!x || !dy || !o.dW || !o.ws || p.N <= 0 || p.H <= 0 || p.W <= 0 || p.Ci <= 0 || p.Co <= 0 || p.ldx < p.Ci || p.lddy < p.Co)
         return UMI_ERR_BADARG;
     switch (path) {
+    case WGRAD_MFMA3X3_F32: return umi_wgrad3x3_f32_mfma(p, x, txa, dy, o, s);
     case WGRAD_MFMA3X3: return umi_wgrad3x3_mfma(p, x, txa, dy, o, s);
     case WGRAD_MFMA1X1: return umi_wgrad1x1_mfma(p, x, txa, dy, o, s);
     case WGRAD_T: return umi_wgradT_mfma(p, x, dy, txb, o, s);

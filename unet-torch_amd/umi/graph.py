@@ -88,6 +88,7 @@ class Tape:
         self._late_adds = []              # (destination, addend) pairs applied after every deferred fill has run
         self._late_ready = []             # parameters whose bucket slot (gradient sink) is a deferred fill: mark_ready after it
         self._inputs = []
+        self.conv3x3_flags = 0            # compute_dtype "fp32_mfma": lib.CONV_F32_MFMA, OR-ed into the 3x3 convolutions' calls
 
     # ---- helpers -----------------------------------------------------------------------
     def alloc(self, N, H, W, C, dtype=None, zero=False, device=None):
@@ -100,6 +101,11 @@ class Tape:
         if c is not None and isinstance(weight, torch.nn.Parameter) and weight.dtype == torch.float32:
             return c.get(kind, weight, self.dtype, k8)
         return ops.PACKERS[kind](wf, self.dtype, k8=k8)
+
+    def _f3(self, R, S, stride, pad, cin):
+        """Flags for one call of a 3x3 / stride 1 / pad 1 convolution that reads `cin` channels: the tape's opt-in kernel flag where
+        the channel count allows it at all (the library ignores it for any other reason it cannot take the problem)."""
+        return self.conv3x3_flags if (R, S, stride, pad) == (3, 3, 1, 1) and cin % 8 == 0 else 0
 
     def _defer_list(self, weight, gw):
         """The list a weight gradient's split-K reduction is deferred to (and `gw` marked as filled at the flush), or None."""
@@ -239,7 +245,7 @@ class Tape:
         # the pointwise matrix-core kernel has no statistics epilogue: a 1x1 conv that feeds a BatchNorm (attention gates) runs
         # it without statistics and takes them in a separate HBM-bound pass over its (small: C_hidden channels) output; where
         # neither applies (odd channel counts) the generic kernel produces both
-        part, flags, two_pass = None, 0, False
+        part, flags, two_pass = None, self._f3(R, S, stride, pad, Ci), False
         if self.training and (R, S) == (1, 1):
             two_pass = (self.dtype == torch.float16 and Co % 8 == 0 and
                         ops.conv_plan(a.raw, out, R, S, stride, pad, 0, False)[0] == 1)
@@ -312,7 +318,7 @@ class Tape:
                         ops.bn_bwd_apply(o.grad, out, tx, rstd, dbeta, dgamma)
                 if not fuse and not stem_fuse:
                     ops.conv_wgrad(a.raw, a.tx, o.grad, None, gw, Ci * R * S, R * S, 1, inv, R, S, stride, pad,
-                                   defer=self._defer_list(weight, gw))
+                                   flags=self._f3(R, S, stride, pad, Ci), defer=self._defer_list(weight, gw))
                 self._set_pgrad(weight, gw)
                 if bias is not None:
                     gb = self._new_pgrad(bias)
@@ -344,7 +350,7 @@ class Tape:
                         a.bn_part, a.bn_part_at = part, a.gives + 1      # valid after the _give below and until the next one
                     else:
                         ops.conv_fwd(o.grad, None, lambda lay: self._pack("conv_dgrad", weight, wf, bool(lay)), None, dx,
-                                     R, S, 1, R - 1 - pad)
+                                     R, S, 1, R - 1 - pad, flags=self._f3(R, S, stride, R - 1 - pad, Co))
                     self._give(a, dx)
             self.steps.append(bwd)
         return o

@@ -11,6 +11,7 @@ from . import build as _build
 
 UMI_F32, UMI_F16 = 0, 1
 CONV_UPSAMPLE2, CONV_FORCE_GENERIC, CONV_DGRAD_STRIDED, CONV_ACCUMULATE = 1, 2, 4, 8
+CONV_F32_MFMA = 16         # opt-in fp32 matrix-core 3x3 kernels; ignored by the library where they do not apply
 
 _ERR = {-1: "UMI_ERR_BADARG", -2: "UMI_ERR_UNSUPPORTED", -3: "UMI_ERR_WORKSPACE"}
 
