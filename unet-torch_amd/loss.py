@@ -86,8 +86,8 @@ class _FusedDiceCE(torch.autograd.Function):
         HW = pred[0, 0].numel()
         stats = torch.empty(3 * C + 2, dtype=torch.float32, device=pred.device)
         ws = ops.workspace(L.fn("umi_dice_ce_ws_bytes")(N, C, HW), pred.device)
-        L.check(L.fn("umi_dice_ce_fwd")(pred.data_ptr(), target.data_ptr(), _TARGET_DTYPES[target.dtype], N, C, HW,
-                                        stats.data_ptr(), ws.data_ptr(), ws.numel(), ops._stream()), "umi_dice_ce_fwd")
+        L.call("umi_dice_ce_fwd", pred.data_ptr(), target.data_ptr(), _TARGET_DTYPES[target.dtype], N, C, HW,
+               stats.data_ptr(), ws.data_ptr(), ws.numel(), ops._stream())
         ctx.save_for_backward(pred, target, stats)
         return stats[3 * C + 1].clone()
 
@@ -99,8 +99,8 @@ class _FusedDiceCE(torch.autograd.Function):
         HW = pred[0, 0].numel()
         g = gout.detach().to(torch.float32).contiguous()
         dl = torch.empty_like(pred)
-        L.check(L.fn("umi_dice_ce_bwd")(pred.data_ptr(), target.data_ptr(), _TARGET_DTYPES[target.dtype], stats.data_ptr(),
-                                        g.data_ptr(), N, C, HW, dl.data_ptr(), ops._stream()), "umi_dice_ce_bwd")
+        L.call("umi_dice_ce_bwd", pred.data_ptr(), target.data_ptr(), _TARGET_DTYPES[target.dtype], stats.data_ptr(),
+               g.data_ptr(), N, C, HW, dl.data_ptr(), ops._stream())
         return dl, None
 
 
@@ -177,9 +177,9 @@ class _HausdorffDT(torch.autograd.Function):
         D = torch.empty_like(pred)
         loss = torch.empty((), dtype=torch.float32, device=pred.device)
         ws = ops.workspace(L.fn("umi_hdt_ws_bytes")(B, H, W), pred.device)
-        L.check(L.fn("umi_hdt_fwd")(pred.data_ptr(), target.data_ptr(), B, C, H, W, alpha, D.data_ptr(),
-                                    None if fields is None else fields.data_ptr(), loss.data_ptr(), ws.data_ptr(),
-                                    ws.numel(), ops._stream()), "umi_hdt_fwd")
+        L.call("umi_hdt_fwd", pred.data_ptr(), target.data_ptr(), B, C, H, W, alpha, D.data_ptr(),
+               None if fields is None else fields.data_ptr(), loss.data_ptr(), ws.data_ptr(),
+               ws.numel(), ops._stream())
         ctx.save_for_backward(pred, target, D)
         ctx.mark_non_differentiable(D)
         return loss, D
@@ -191,8 +191,8 @@ class _HausdorffDT(torch.autograd.Function):
         B, C, H, W = pred.shape
         g = gout.detach().to(torch.float32).contiguous()
         dpred = torch.empty_like(pred)
-        L.check(L.fn("umi_hdt_bwd")(pred.data_ptr(), target.data_ptr(), D.data_ptr(), g.data_ptr(), B, C, H, W,
-                                    dpred.data_ptr(), ops._stream()), "umi_hdt_bwd")
+        L.call("umi_hdt_bwd", pred.data_ptr(), target.data_ptr(), D.data_ptr(), g.data_ptr(), B, C, H, W,
+               dpred.data_ptr(), ops._stream())
         return dpred, None, None, None
 
 
@@ -316,8 +316,8 @@ class _DiceBCE(torch.autograd.Function):
         stats = torch.empty(5 * B, dtype=torch.float64, device=pred.device)
         loss = torch.empty((), dtype=torch.float32, device=pred.device)
         ws = ops.workspace(L.fn("umi_binloss_ws_bytes")(B, 1, HW), pred.device)
-        L.check(L.fn("umi_dice_bce_fwd")(pred.data_ptr(), target.data_ptr(), B, HW, stats.data_ptr(), loss.data_ptr(),
-                                         ws.data_ptr(), ws.numel(), ops._stream()), "umi_dice_bce_fwd")
+        L.call("umi_dice_bce_fwd", pred.data_ptr(), target.data_ptr(), B, HW, stats.data_ptr(), loss.data_ptr(),
+               ws.data_ptr(), ws.numel(), ops._stream())
         ctx.save_for_backward(pred, target, stats)
         return loss
 
@@ -327,8 +327,8 @@ class _DiceBCE(torch.autograd.Function):
         pred, target, stats = ctx.saved_tensors
         g = gout.detach().to(torch.float32).contiguous()
         dpred = torch.empty_like(pred)
-        L.check(L.fn("umi_dice_bce_bwd")(pred.data_ptr(), target.data_ptr(), stats.data_ptr(), g.data_ptr(), pred.shape[0],
-                                         pred[0, 0].numel(), dpred.data_ptr(), ops._stream()), "umi_dice_bce_bwd")
+        L.call("umi_dice_bce_bwd", pred.data_ptr(), target.data_ptr(), stats.data_ptr(), g.data_ptr(), pred.shape[0],
+               pred[0, 0].numel(), dpred.data_ptr(), ops._stream())
         return dpred, None
 
 
@@ -342,9 +342,8 @@ class _Tversky(torch.autograd.Function):
         stats = torch.empty(5 * B if C == 1 else 3 * C, dtype=torch.float64, device=pred.device)
         loss = torch.empty((), dtype=torch.float32, device=pred.device)
         ws = ops.workspace(L.fn("umi_binloss_ws_bytes")(B, C, HW), pred.device)
-        L.check(L.fn("umi_tversky_fwd")(pred.data_ptr(), target.data_ptr(), _TARGET_DTYPES[target.dtype], B, C, HW, alpha,
-                                        beta, stats.data_ptr(), loss.data_ptr(), ws.data_ptr(), ws.numel(), ops._stream()),
-                "umi_tversky_fwd")
+        L.call("umi_tversky_fwd", pred.data_ptr(), target.data_ptr(), _TARGET_DTYPES[target.dtype], B, C, HW, alpha,
+               beta, stats.data_ptr(), loss.data_ptr(), ws.data_ptr(), ws.numel(), ops._stream())
         ctx.save_for_backward(pred, target, stats)
         ctx.ab = (alpha, beta)
         return loss
@@ -356,9 +355,8 @@ class _Tversky(torch.autograd.Function):
         B, C, HW = pred.shape[0], pred.shape[1], pred[0, 0].numel()
         g = gout.detach().to(torch.float32).contiguous()
         dpred = torch.empty_like(pred)
-        L.check(L.fn("umi_tversky_bwd")(pred.data_ptr(), target.data_ptr(), _TARGET_DTYPES[target.dtype], stats.data_ptr(),
-                                        g.data_ptr(), B, C, HW, ctx.ab[0], ctx.ab[1], dpred.data_ptr(), ops._stream()),
-                "umi_tversky_bwd")
+        L.call("umi_tversky_bwd", pred.data_ptr(), target.data_ptr(), _TARGET_DTYPES[target.dtype], stats.data_ptr(),
+               g.data_ptr(), B, C, HW, ctx.ab[0], ctx.ab[1], dpred.data_ptr(), ops._stream())
         return dpred, None, None, None
 
 
@@ -373,8 +371,8 @@ class _TopKBCE(torch.autograd.Function):
         mask = torch.empty(N, dtype=torch.uint8, device=pred.device)
         loss = torch.empty((), dtype=torch.float32, device=pred.device)
         ws = ops.workspace(L.fn("umi_topk_loss_ws_bytes")(N), pred.device)
-        L.check(L.fn("umi_topk_loss_fwd")(pred.data_ptr(), target.data_ptr(), N, k, mode, mask.data_ptr(), loss.data_ptr(),
-                                          ws.data_ptr(), ws.numel(), ops._stream()), "umi_topk_loss_fwd")
+        L.call("umi_topk_loss_fwd", pred.data_ptr(), target.data_ptr(), N, k, mode, mask.data_ptr(), loss.data_ptr(),
+               ws.data_ptr(), ws.numel(), ops._stream())
         ctx.save_for_backward(pred, target, mask)
         ctx.k = k
         return loss
@@ -385,8 +383,8 @@ class _TopKBCE(torch.autograd.Function):
         pred, target, mask = ctx.saved_tensors
         g = gout.detach().to(torch.float32).contiguous()
         dpred = torch.empty_like(pred)
-        L.check(L.fn("umi_topk_loss_bwd")(pred.data_ptr(), target.data_ptr(), mask.data_ptr(), g.data_ptr(), pred.numel(),
-                                          ctx.k, dpred.data_ptr(), ops._stream()), "umi_topk_loss_bwd")
+        L.call("umi_topk_loss_bwd", pred.data_ptr(), target.data_ptr(), mask.data_ptr(), g.data_ptr(), pred.numel(),
+               ctx.k, dpred.data_ptr(), ops._stream())
         return dpred, None, None, None
 
 
@@ -555,9 +553,9 @@ class _MultiTaskRatio(torch.autograd.Function):
         outs = [torch.empty((), dtype=torch.float32, device=dev) for _ in range(4)]
         ws = ops.workspace(L.fn("umi_mt_ratio_ws_bytes")(B, HW), dev)
         flag = torch.is_tensor(gate)
-        L.check(L.fn("umi_mt_ratio_fwd")(o1.data_ptr(), o2.data_ptr(), l1.data_ptr(), l2.data_ptr(), B, HW,
-                                         0 if flag else int(bool(gate)), gate.data_ptr() if flag else None, stats.data_ptr(), *[t.data_ptr() for t in outs], ws.data_ptr(), ws.numel(),
-                                         ops._stream()), "umi_mt_ratio_fwd")
+        L.call("umi_mt_ratio_fwd", o1.data_ptr(), o2.data_ptr(), l1.data_ptr(), l2.data_ptr(), B, HW,
+               0 if flag else int(bool(gate)), gate.data_ptr() if flag else None, stats.data_ptr(), *[t.data_ptr() for t in outs], ws.data_ptr(), ws.numel(),
+               ops._stream())
         ctx.save_for_backward(o1, o2, l1, l2, stats)
         return tuple(outs)
 
@@ -568,9 +566,9 @@ class _MultiTaskRatio(torch.autograd.Function):
         zero = torch.zeros((), dtype=torch.float32, device=o1.device)
         g = torch.stack([zero if v is None else v.detach().to(torch.float32) for v in (gL, g1, g2, gr)])
         d1, d2 = torch.empty_like(o1), torch.empty_like(o2)
-        L.check(L.fn("umi_mt_ratio_bwd")(o1.data_ptr(), o2.data_ptr(), l1.data_ptr(), l2.data_ptr(), stats.data_ptr(),
-                                         g.data_ptr(), o1.shape[0], o1[0, 0].numel(), d1.data_ptr(), d2.data_ptr(),
-                                         ops._stream()), "umi_mt_ratio_bwd")
+        L.call("umi_mt_ratio_bwd", o1.data_ptr(), o2.data_ptr(), l1.data_ptr(), l2.data_ptr(), stats.data_ptr(),
+               g.data_ptr(), o1.shape[0], o1[0, 0].numel(), d1.data_ptr(), d2.data_ptr(),
+               ops._stream())
         return d1, d2, None, None, None
 
 

@@ -234,7 +234,7 @@ def _batch_dims(x, what):
 
 def _status(st, what, shape):
     from . import lib as L
-    if st == -2:
+    if st == L.UMI_ERR_UNSUPPORTED:
         raise ValueError(f"{what}: unsupported size {tuple(shape)}")
     L.check(st, what)
 

@@ -13,6 +13,7 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(os.path.dirname(HERE), "csrc")
 LIB = os.path.join(HERE, "libunetmi.so")
+HEADER = os.path.join(os.path.dirname(os.path.dirname(HERE)), "include", "unetmi.h")
 OBJ = os.path.join(HERE, "_obj")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 CFLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fno-gpu-rdc",
@@ -25,8 +26,7 @@ def sources():
 
 
 def _headers():
-    return glob.glob(os.path.join(CSRC, "*.h")) + \
-        [os.path.join(os.path.dirname(os.path.dirname(HERE)), "include", "unetmi.h")]
+    return glob.glob(os.path.join(CSRC, "*.h")) + [HEADER]
 
 
 def _obj(src):

@@ -192,15 +192,15 @@ class TUTape(Tape):
         N, Hd, Wd, Cd, lddy = ops._nhwc(dy)
         _, Hx, Wx, Cx, lddx = ops._nhwc(dx)
         lay = ctypes.c_int(0)
-        L.check(L.fn("umi_conv_fwd_plan")(N, Hd, Wd, Cd, Cx, R, S, stride, pad, lddy, lddx, ops._dt(dy), ops._dt(dx),
-                                          L.CONV_DGRAD_STRIDED, 0, ctypes.addressof(lay), None), "umi_conv_fwd_plan")
+        L.call("umi_conv_fwd_plan", N, Hd, Wd, Cd, Cx, R, S, stride, pad, lddy, lddx, ops._dt(dy), ops._dt(dx),
+               L.CONV_DGRAD_STRIDED, 0, ctypes.addressof(lay), None)
         if callable(wpd):
             wpd = wpd(lay.value)
         elif lay.value != 0:
             raise ValueError("this data gradient takes the MFMA path: pass a callable so the weights get the k8 packing")
-        L.check(L.fn("umi_conv_fwd")(dy.data_ptr(), lddy, None, wpd.data_ptr(), None, dx.data_ptr(), lddx, None,
-                                     N, Hd, Wd, Cd, Cx, R, S, stride, pad, Hx, Wx, 0, 0, Hx, Wx, ops._dt(dy), ops._dt(dx),
-                                     L.CONV_DGRAD_STRIDED | L.CONV_UPSAMPLE2 * 0, ops._stream()), "umi_conv_fwd(dgrad strided)")
+        L.call("umi_conv_fwd", dy.data_ptr(), lddy, None, wpd.data_ptr(), None, dx.data_ptr(), lddx, None,
+               N, Hd, Wd, Cd, Cx, R, S, stride, pad, Hx, Wx, 0, 0, Hx, Wx, ops._dt(dy), ops._dt(dx),
+               L.CONV_DGRAD_STRIDED | L.CONV_UPSAMPLE2 * 0, ops._stream())
 
     # ---- GroupNorm (+ residual) (+ ReLU) ---------------------------------------------------------------------------
     def group_norm(self, a: Act, gn, relu, residual: Act = None):

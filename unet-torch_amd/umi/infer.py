@@ -54,8 +54,8 @@ def zoom_cubic(img, input_size):
     out = torch.empty((oh, ow, C), dtype=img.dtype, device=img.device)
     nbytes = L.fn("umi_zoom_cubic_ws_bytes")(H, W, C)
     ws = torch.empty(nbytes, dtype=torch.uint8, device=img.device)
-    L.check(L.fn("umi_zoom_cubic_hwc")(img.data_ptr(), 0 if img.dtype == torch.uint8 else 1, out.data_ptr(), H, W, C, oh, ow,
-                                       ws.data_ptr(), nbytes, ops._stream()), "umi_zoom_cubic_hwc")
+    L.call("umi_zoom_cubic_hwc", img.data_ptr(), 0 if img.dtype == torch.uint8 else 1, out.data_ptr(), H, W, C, oh, ow,
+           ws.data_ptr(), nbytes, ops._stream())
     return out[..., 0] if hw else out
 
 
@@ -90,8 +90,8 @@ def preprocess(img, reverse_channels=None, input_size=None):
     out = torch.empty((1, C, H, W), dtype=torch.float32, device=img.device)
     nbytes = L.fn("umi_znorm_ws_bytes")()
     ws = ops.workspace(nbytes, img.device)
-    L.check(L.fn("umi_znorm_hwc")(img.data_ptr(), 0 if img.dtype == torch.uint8 else 1, out.data_ptr(), H * W, C,
-                                  int(bool(reverse_channels)), ws.data_ptr(), nbytes, ops._stream()), "umi_znorm_hwc")
+    L.call("umi_znorm_hwc", img.data_ptr(), 0 if img.dtype == torch.uint8 else 1, out.data_ptr(), H * W, C,
+           int(bool(reverse_channels)), ws.data_ptr(), nbytes, ops._stream())
     return out
 
 
@@ -103,7 +103,7 @@ def argmax_mask(logits):
     logits = logits.contiguous()
     N, C, H, W = logits.shape
     mask = torch.empty((N, H, W), dtype=torch.uint8, device=logits.device)
-    L.check(L.fn("umi_argmax_mask")(logits.data_ptr(), mask.data_ptr(), N, C, H * W, ops._stream()), "umi_argmax_mask")
+    L.call("umi_argmax_mask", logits.data_ptr(), mask.data_ptr(), N, C, H * W, ops._stream())
     return mask
 
 
@@ -140,7 +140,7 @@ def binary_mask(logits):
     N, _, H, W = logits.shape
     mask = torch.empty((N, H, W), dtype=torch.uint8, device=logits.device)
     if mask.numel():
-        L.check(L.fn("umi_binary_mask")(logits.data_ptr(), mask.data_ptr(), mask.numel(), ops._stream()), "umi_binary_mask")
+        L.call("umi_binary_mask", logits.data_ptr(), mask.data_ptr(), mask.numel(), ops._stream())
     return mask
 
 
@@ -161,10 +161,9 @@ def zoom_nearest(mask, out_hw):
     if oh < 1 or ow < 1:
         raise ValueError(f"output size {(oh, ow)}")
     out = torch.empty((N, oh, ow), dtype=m.dtype, device=m.device)
-    st = L.fn("umi_zoom_nearest")(m.data_ptr(), 0 if m.dtype == torch.uint8 else 1, out.data_ptr(), N, H, W, oh, ow, ops._stream())
-    if st == -2:
+    if not L.supported("umi_zoom_nearest", m.data_ptr(), 0 if m.dtype == torch.uint8 else 1, out.data_ptr(), N, H, W, oh, ow,
+                       ops._stream()):
         raise ValueError(f"zoom_nearest: unsupported size {tuple(m.shape)} -> {(oh, ow)}")
-    L.check(st, "umi_zoom_nearest")
     return out[0] if single else out
 
 
@@ -206,8 +205,8 @@ def label_components(mask, check=False):
     sum_y = torch.empty((N, cap), dtype=torch.int64, device=dev)
     sum_x = torch.empty((N, cap), dtype=torch.int64, device=dev)
     ws = ops.workspace(nbytes, dev)
-    L.check(L.fn("umi_label_components")(m.data_ptr(), labels.data_ptr(), counts.data_ptr(), area.data_ptr(), sum_y.data_ptr(),
-                                         sum_x.data_ptr(), N, H, W, ws.data_ptr(), nbytes, ops._stream()), "umi_label_components")
+    L.call("umi_label_components", m.data_ptr(), labels.data_ptr(), counts.data_ptr(), area.data_ptr(), sum_y.data_ptr(),
+           sum_x.data_ptr(), N, H, W, ws.data_ptr(), nbytes, ops._stream())
     if check:
         _raise_on_fault(ws, "label_components")
     return (labels[0] if mask.dim() == 2 else labels), counts, area, sum_y, sum_x
@@ -219,8 +218,7 @@ def count_objects(mask, check=False, _fault=False):
     m, N, H, W, nbytes = _component_mask(mask)
     counts = torch.empty(N, dtype=torch.int32, device=m.device)
     ws = ops.workspace(nbytes, m.device)
-    L.check(L.fn("umi_count_components")(m.data_ptr(), counts.data_ptr(), N, H, W, ws.data_ptr(), nbytes, ops._stream()),
-            "umi_count_components")
+    L.call("umi_count_components", m.data_ptr(), counts.data_ptr(), N, H, W, ws.data_ptr(), nbytes, ops._stream())
     if check:
         _raise_on_fault(ws, "count_objects")
     return (counts, ws[:4].view(torch.int32)) if _fault else counts
@@ -236,8 +234,7 @@ def sum_trunc(x):
     out = torch.empty(x.shape[0], dtype=torch.int32, device=x.device)
     nbytes = L.fn("umi_sum_trunc_ws_bytes")(x.shape[0])
     ws = ops.workspace(nbytes, x.device)
-    L.check(L.fn("umi_sum_trunc")(x.data_ptr(), out.data_ptr(), x.shape[0], x[0].numel(), ws.data_ptr(), nbytes, ops._stream()),
-            "umi_sum_trunc")
+    L.call("umi_sum_trunc", x.data_ptr(), out.data_ptr(), x.shape[0], x[0].numel(), ws.data_ptr(), nbytes, ops._stream())
     return out
 
 
@@ -391,9 +388,9 @@ def _label_class_components(mask, n_classes, max_components):
     sum_y = torch.empty((N, cap), dtype=torch.int64, device=dev)
     sum_x = torch.empty((N, cap), dtype=torch.int64, device=dev)
     ws = ops.workspace(nbytes, dev)
-    L.check(L.fn("umi_label_class_components")(m.data_ptr(), labels.data_ptr(), counts.data_ptr(), class_counts.data_ptr(),
-                                               label_class.data_ptr(), area.data_ptr(), sum_y.data_ptr(), sum_x.data_ptr(), N, H, W, K,
-                                               cap, ws.data_ptr(), nbytes, ops._stream()), "umi_label_class_components")
+    L.call("umi_label_class_components", m.data_ptr(), labels.data_ptr(), counts.data_ptr(), class_counts.data_ptr(),
+           label_class.data_ptr(), area.data_ptr(), sum_y.data_ptr(), sum_x.data_ptr(), N, H, W, K,
+           cap, ws.data_ptr(), nbytes, ops._stream())
     return ((labels[0] if mask.dim() == 2 else labels), counts, class_counts, label_class, area, sum_y, sum_x), \
         ws[:4].view(torch.int32)
 
@@ -425,8 +422,8 @@ def count_class_objects(mask, n_classes, check=False):
     m, N, H, W, K, nbytes = _class_component_mask(mask, n_classes)
     class_counts = torch.empty((N, K), dtype=torch.int32, device=m.device)
     ws = ops.workspace(nbytes, m.device)
-    L.check(L.fn("umi_count_class_components")(m.data_ptr(), class_counts.data_ptr(), N, H, W, K, ws.data_ptr(), nbytes,
-                                               ops._stream()), "umi_count_class_components")
+    L.call("umi_count_class_components", m.data_ptr(), class_counts.data_ptr(), N, H, W, K, ws.data_ptr(), nbytes,
+           ops._stream())
     if check:
         _raise_on_class_fault(ws[:4].view(torch.int32).item(), "count_class_objects")
     return class_counts

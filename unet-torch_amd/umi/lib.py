@@ -5,15 +5,95 @@ missing and cannot be built, importing this module raises.
 """
 import ctypes
 import os
-from ctypes import c_char_p, c_double, c_float, c_int, c_long, c_size_t, c_uint, c_void_p
+import re
 
 from . import build as _build
 
-UMI_F32, UMI_F16 = 0, 1
-CONV_UPSAMPLE2, CONV_FORCE_GENERIC, CONV_DGRAD_STRIDED, CONV_ACCUMULATE = 1, 2, 4, 8
-CONV_F32_MFMA = 16         # opt-in fp32 matrix-core 3x3 kernels; ignored by the library where they do not apply
+# the closed type map of include/unetmi.h; a parameter or field with a `*` is an address
+_SCALAR = {"int": ctypes.c_int, "long": ctypes.c_long, "long long": ctypes.c_longlong, "unsigned": ctypes.c_uint,
+           "size_t": ctypes.c_size_t, "float": ctypes.c_float, "double": ctypes.c_double, "umi_stream_t": ctypes.c_void_p}
+_TYPE_WORDS = {w for t in _SCALAR for w in t.split()} | {"const", "void", "char", "short", "signed", "struct", "enum"}
 
-_ERR = {-1: "UMI_ERR_BADARG", -2: "UMI_ERR_UNSUPPORTED", -3: "UMI_ERR_WORKSPACE"}
+
+def _refuse(decl, why="cannot parse"):
+    raise ValueError(f"unetmi.h: {why}: {decl!r}")
+
+
+def _ctype(text, decl):
+    """ctypes type of the type part of a parameter / field declaration."""
+    if "*" in text:
+        return ctypes.c_void_p if re.fullmatch(r"[\w\s*]+", text) else _refuse(decl)
+    t = " ".join(w for w in text.split() if w != "const")
+    return _SCALAR[t] if t in _SCALAR else _refuse(decl, f"unknown type {t!r} in")
+
+
+def _declarator(text, decl):
+    """'const float* part' -> ('const float*', 'part', None);  'pad2_[2]' -> ('', 'pad2_', 2)."""
+    m = re.fullmatch(r"(.*?)(\w+) ?(?:\[ ?(\d+) ?\])?", text.strip())
+    if not m or m.group(2) in _TYPE_WORDS:             # e.g. a bit-field, a parameter without a name
+        _refuse(decl, f"cannot parse {text.strip()!r} in")
+    return m.group(1).strip(), m.group(2), m.group(3) and int(m.group(3))
+
+
+def _fields(body, decl):
+    out = []
+    for stmt in filter(None, (s.strip() for s in body.split(";"))):
+        first, *more = stmt.split(",")                 # `long st, sk, sn;`: the later declarators share the first one's base type
+        base, name, n = _declarator(first, decl)
+        for ptr, name, n in [("*" in base, name, n)] + [("*" in t, *_declarator(t, decl)[1:]) for t in more]:
+            t = _ctype(base.replace("*", " ") + "*" * ptr, decl)
+            out.append((name, t * n if n else t))
+    return out
+
+
+def _param(text, decl):
+    base, _, n = _declarator(text, decl)
+    return _ctype(base, decl) if n is None else _refuse(decl, f"array parameter {text.strip()!r} in")
+
+
+def parse_header(text):
+    """(enums, structs, signatures) of a header written like include/unetmi.h: {name: int}, {name: ctypes.Structure subclass},
+    {name: (restype, [argtypes])}.  Strict: a declaration that is not fully understood raises and is quoted, nothing is guessed."""
+    text = re.sub(r"/\*.*?\*/|//[^\n]*", " ", text, flags=re.S)
+    text = re.sub(r"^[ \t]*#.*$", "", text, flags=re.M)          # include guard, #include, #ifdef __cplusplus
+    text, wrapped = re.subn(r'extern\s+"C"\s*\{', "", text)
+    enums, structs, sigs = {}, {}, {}
+    *pieces, rest = text.split(";")
+    decl = ""
+    for piece in pieces:                                        # declarations end at a `;` outside braces
+        decl += piece
+        if decl.count("{") > decl.count("}"):
+            decl += ";"
+            continue
+        decl, d = "", " ".join(decl.split())
+        if re.fullmatch(r"typedef void ?\* ?umi_stream_t", d):
+            continue
+        m = re.fullmatch(r"enum (?:\w+ )?\{(.*)\}", d)
+        if m:
+            for item in filter(None, (i.strip() for i in m.group(1).split(","))):
+                e = re.fullmatch(r"(\w+) = (-?\d+)", item) or _refuse(d, f"cannot parse enumerator {item!r} in")
+                enums[e.group(1)] = int(e.group(2))
+            continue
+        m = re.fullmatch(r"typedef struct (\w+) \{([^{}]*)\} \1", d)
+        if m:
+            structs[m.group(1)] = type(m.group(1), (ctypes.Structure,), {"_fields_": _fields(m.group(2), d)})
+            continue
+        m = re.fullmatch(r"([\w *]+?) ?\b(umi_\w+) ?\(([^()]*)\)", d) or _refuse(d)
+        ret = m.group(1).replace(" ", "")
+        res = ctypes.c_char_p if ret == "constchar*" else _refuse(d, "unsupported return type in") if "*" in ret \
+            else _ctype(m.group(1), d)
+        params = [] if m.group(3).strip() == "void" else m.group(3).split(",")
+        sigs[m.group(2)] = (res, [_param(p, d) for p in params])
+    if (decl + rest).strip() != "}" * wrapped:
+        _refuse(" ".join((decl + rest).split()))
+    return enums, structs, sigs
+
+
+with open(_build.HEADER) as _f:
+    ENUMS, STRUCTS, SIGNATURES = parse_header(_f.read())          # the header is the only statement of the C ABI
+# UMI_F32, UMI_F16, UMI_OK, UMI_ERR_*, and the conv flags under their short names CONV_*
+globals().update({k.replace("UMI_CONV_", "CONV_"): v for k, v in ENUMS.items()})
+_ERR = {v: k for k, v in ENUMS.items() if k.startswith("UMI_ERR_")}
 
 
 def _load():
@@ -34,186 +114,6 @@ def _load():
 
 _lib = _load()
 
-# name -> (restype, argtypes); mirrors include/unetmi.h one to one
-SIGNATURES = {
-    "umi_version": (c_int, []),
-    "umi_arch": (c_char_p, []),
-    "umi_tune_conv3x3_impl": (c_int, [c_int]),
-    "umi_zoom_cubic_ws_bytes": (c_size_t, [c_int, c_int, c_int]),
-    "umi_zoom_cubic_hwc": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p]),
-    "umi_linear_fused": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_long, c_int, c_int, c_int, c_float,
-                                 c_uint, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_void_p]),
-    "umi_pack_kn": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_long, c_long, c_long, c_int, c_int, c_int,
-                            c_int, c_void_p]),
-    "umi_pack_kn8": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_long, c_long, c_long, c_int, c_int, c_int,
-                             c_int, c_void_p]),
-    "umi_conv_fwd": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p,
-                             c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
-                             c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]),
-    "umi_conv_fwd_plan": (c_int, [c_int] * 15 + [c_void_p, c_void_p]),
-    "umi_bn_finalize": (c_int, [c_void_p, c_int, c_int, c_double, c_void_p, c_void_p, c_float, c_float,
-                                c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
-    "umi_pool2_fwd": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int,
-                              c_void_p]),
-    "umi_pool2_bwd": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int,
-                              c_int, c_int, c_int, c_int, c_int, c_void_p]),
-    "umi_bn_bwd_ws_bytes": (c_size_t, [c_long, c_int]),
-    "umi_bn_bwd_reduce": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
-                                  c_long, c_int, c_int, c_void_p, c_size_t, c_void_p]),
-    "umi_bn_bwd_apply": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
-                                 c_long, c_int, c_int, c_void_p]),
-    "umi_conv_wgrad_ws_bytes": (c_size_t, [c_int] * 9),
-    "umi_conv_wgrad": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p,
-                               c_long, c_long, c_long, c_float,
-                               c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
-                               c_int, c_int, c_void_p, c_size_t, c_void_p]),
-    "umi_conv_wgrad_deferred": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p,
-                                        c_long, c_long, c_long, c_float,
-                                        c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
-                                        c_int, c_int, c_void_p, c_size_t, c_void_p, c_void_p]),
-    "umi_wgrad_reduce_group": (c_int, [c_int, c_void_p, c_void_p]),
-    "umi_conv_wgrad_group": (c_int, [c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_long, c_long, c_float, c_long,
-                                     c_int, c_int, c_int, c_void_p]),
-    "umi_conv_wgrad_bnapply": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p,
-                                       c_void_p, c_void_p, c_int, c_void_p, c_long, c_long, c_long, c_float,
-                                       c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
-                                       c_void_p, c_size_t, c_void_p]),
-    "umi_colsum_ws_bytes": (c_size_t, [c_long, c_int]),
-    "umi_colsum_group": (c_int, [c_int, c_void_p, c_int, c_void_p, c_float, c_long, c_int, c_int, c_void_p, c_size_t, c_void_p]),
-    "umi_materialize_nchw": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p]),
-    "umi_wstd_fwd": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_float, c_void_p]),
-    "umi_wstd_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p]),
-    "umi_wstd_fwd_multi": (c_int, [c_void_p, c_int, c_int, c_void_p]),
-    "umi_wstd_bwd_multi": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]),
-    "umi_gn_fwd": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_int,
-                           c_int, c_long, c_int, c_int, c_float, c_int, c_void_p, c_size_t, c_void_p]),
-    "umi_gn_fwd_ws_bytes": (c_size_t, [c_int, c_long, c_int]),
-    "umi_gn_bwd_ws_bytes": (c_size_t, [c_int, c_long, c_int, c_int]),
-    "umi_gn_bwd": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int,
-                           c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_float, c_int, c_long, c_int, c_int, c_int,
-                           c_void_p, c_size_t, c_void_p, c_void_p]),
-    "umi_gn_param_grads_group": (c_int, [c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_float, c_void_p]),
-    "umi_pool3s2_fwd": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p]),
-    "umi_pool3s2_bwd": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int,
-                                c_void_p]),
-    "umi_ln_fwd": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_long, c_int, c_float,
-                           c_int, c_void_p]),
-    "umi_ln_bwd_ws_bytes": (c_size_t, [c_long, c_int]),
-    "umi_ln_bwd": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p,
-                           c_float, c_long, c_int, c_int, c_void_p, c_size_t, c_void_p, c_void_p]),
-    "umi_elementwise": (c_int, [c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_long, c_int, c_long, c_int, c_void_p]),
-    "umi_dropout": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_float, ctypes.c_uint, c_long, c_int, c_int,
-                            c_void_p, c_void_p, c_void_p]),
-    "umi_dropout_fused": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_float, ctypes.c_uint, c_long, c_int, c_int,
-                                  c_void_p, c_void_p, c_int, c_int, c_void_p]),
-    "umi_attn_fwd": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int,
-                             c_void_p]),
-    "umi_attn_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p,
-                             c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p]),
-    "umi_bilinear2x": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]),
-    "umi_colsum": (c_int, [c_void_p, c_int, c_void_p, c_float, c_long, c_int, c_int, c_void_p, c_size_t, c_void_p]),
-    "umi_conv3x3_fwd_act": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int,
-                                    c_int, c_int, c_void_p]),
-    "umi_conv_dgrad_bnred": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p,
-                                     c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]),
-    "umi_conv_wgrad_bias": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_long, c_long, c_long, c_void_p, c_float]
-                            + [c_int] * 9 + [c_void_p, c_size_t, c_void_p, c_void_p]),
-    "umi_conv_gather_bnred_rows": (c_int, [c_int] * 15),
-    "umi_conv_gather_bnred": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p]
-                              + [c_int] * 13 + [c_void_p]),
-    "umi_head_bwd_fused_ws_bytes": (c_size_t, [c_long, c_int, c_int]),
-    "umi_head_bwd_fused": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p,
-                                   c_void_p, c_long, c_long, c_float, c_void_p, c_size_t, c_long, c_int, c_int, c_int, c_void_p]),
-    "umi_head_dgrad_bnred_rows": (c_int, [c_long, c_int, c_int, c_int, c_int]),
-    "umi_head_dgrad_bnred": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p,
-                                     c_long, c_int, c_int, c_int, c_void_p]),
-    "umi_bn_bwd_from_partials": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]),
-    "umi_bn_stats_rows": (c_int, [c_long, c_int]),
-    "umi_bn_stats": (c_int, [c_void_p, c_int, c_void_p, c_long, c_int, c_int, c_void_p]),
-    "umi_pool2_bwd_bnred_stat_rows": (c_int, [c_int, c_int, c_int, c_int]),
-    "umi_pool2_bwd_bnred": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p,
-                                    c_int, c_int, c_int, c_int, c_int, c_void_p]),
-    "umi_dice_ce_ws_bytes": (c_size_t, [c_int, c_int, c_long]),
-    "umi_dice_ce_fwd": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_long, c_void_p, c_void_p, c_size_t, c_void_p]),
-    "umi_dice_ce_bwd": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_long, c_void_p, c_void_p]),
-    "umi_hdt_ws_bytes": (c_size_t, [c_int, c_int, c_int]),
-    "umi_hdt_fwd": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_float, c_void_p, c_void_p, c_void_p, c_void_p,
-                            c_size_t, c_void_p]),
-    "umi_hdt_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
-    "umi_binloss_ws_bytes": (c_size_t, [c_int, c_int, c_long]),
-    "umi_dice_bce_fwd": (c_int, [c_void_p, c_void_p, c_int, c_long, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
-    "umi_dice_bce_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_long, c_void_p, c_void_p]),
-    "umi_tversky_fwd": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_long, c_float, c_float, c_void_p, c_void_p,
-                                c_void_p, c_size_t, c_void_p]),
-    "umi_tversky_bwd": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_long, c_float, c_float,
-                                c_void_p, c_void_p]),
-    "umi_topk_loss_ws_bytes": (c_size_t, [c_long]),
-    "umi_topk_loss_fwd": (c_int, [c_void_p, c_void_p, c_long, c_long, c_int, c_void_p, c_void_p, c_void_p, c_size_t,
-                                  c_void_p]),
-    "umi_topk_loss_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_long, c_long, c_void_p, c_void_p]),
-    "umi_mt_ratio_ws_bytes": (c_size_t, [c_int, c_long]),
-    "umi_mt_ratio_stats_len": (c_size_t, [c_int]),
-    "umi_mt_ratio_fwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_long, c_int, c_void_p, c_void_p, c_void_p,
-                                 c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
-    "umi_mt_ratio_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_long, c_void_p,
-                                 c_void_p, c_void_p]),
-    "umi_optim_block_elems": (c_int, []),
-    "umi_table_upload": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p]),
-    "umi_optim_sgd_multi": (c_int, [c_void_p, c_int, c_int, c_double, c_double, c_double, c_double, c_int, c_int, c_void_p]),
-    "umi_optim_adam_multi": (c_int, [c_void_p, c_int, c_int, c_double, c_double, c_double, c_double, c_double, c_double,
-                                     c_void_p]),
-    "umi_optim_hyper_bytes": (c_size_t, []),
-    "umi_optim_hyper_pre": (c_int, [c_void_p, c_int, c_void_p]),
-    "umi_optim_hyper_poly": (c_int, [c_void_p, c_void_p]),
-    "umi_optim_sgd_multi_dev": (c_int, [c_void_p, c_int, c_int, c_void_p, c_double, c_double, c_double, c_int, c_int, c_void_p]),
-    "umi_optim_adam_multi_dev": (c_int, [c_void_p, c_int, c_int, c_void_p, c_double, c_double, c_double, c_double, c_void_p]),
-    "umi_pack_block_elems": (c_int, []),
-    "umi_pack_kn_multi": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p]),
-    "umi_add2_relu_fwd": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_long, c_int, c_int,
-                                  c_void_p]),
-    "umi_add2_relu_bwd": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_long, c_int, c_int,
-                                  c_void_p]),
-    "umi_gate_fwd": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_long, c_int, c_int, c_void_p]),
-    "umi_gate_bwd": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p,
-                             c_long, c_int, c_int, c_void_p]),
-    "umi_znorm_ws_bytes": (c_size_t, []),
-    "umi_znorm_hwc": (c_int, [c_void_p, c_int, c_void_p, c_long, c_int, c_int, c_void_p, c_size_t, c_void_p]),
-    "umi_argmax_mask": (c_int, [c_void_p, c_void_p, c_int, c_int, c_long, c_void_p]),
-    "umi_binary_mask": (c_int, [c_void_p, c_void_p, c_long, c_void_p]),
-    "umi_zoom_nearest": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p]),
-    "umi_sum_trunc_ws_bytes": (c_size_t, [c_int]),
-    "umi_sum_trunc": (c_int, [c_void_p, c_void_p, c_int, c_long, c_void_p, c_size_t, c_void_p]),
-    "umi_components_ws_bytes": (c_size_t, [c_int, c_int, c_int]),
-    "umi_components_cap": (c_int, [c_int, c_int]),
-    "umi_count_components": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p]),
-    "umi_label_components": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p,
-                                     c_size_t, c_void_p]),
-    "umi_match_max_dots": (c_int, []),
-    "umi_dot_lists_ws_bytes": (c_size_t, [c_int, c_int, c_int]),
-    "umi_dot_lists": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p]),
-    "umi_component_centers": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p]),
-    "umi_crowd_match": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_size_t, c_void_p, c_int,
-                                c_void_p, c_int, c_void_p, c_int, c_void_p]),
-    "umi_distance_match_ws_bytes": (c_size_t, [c_int, c_int]),
-    "umi_distance_match": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, ctypes.c_longlong, c_void_p, c_int,
-                                   c_void_p, c_size_t, c_void_p]),
-    "umi_grid_sums": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
-    "umi_scatter_centers": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_void_p]),
-    "umi_class_components_ws_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
-    "umi_count_class_components": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p]),
-    "umi_label_class_components": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
-                                           c_int, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p]),
-    "umi_split_classes": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
-    "umi_class_center_lists": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
-                                       c_void_p]),
-    "umi_augment_geometry": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
-    "umi_augment_labels": (c_int, [c_void_p, c_int, c_void_p, c_int, c_float, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int,
-                                   c_void_p]),
-    "umi_augment_znorm_ws_bytes": (c_size_t, [c_int]),
-    "umi_augment_znorm": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p,
-                                  c_size_t, c_void_p]),
-}
-
 for _name, (_res, _args) in SIGNATURES.items():
     _fn = getattr(_lib, _name)          # AttributeError here == header/library mismatch: fail loudly
     _fn.restype = _res
@@ -224,6 +124,23 @@ def check(status: int, what: str):
     if status != 0:
         raise RuntimeError(f"libunetmi: {what} failed with "
                            f"{_ERR.get(status, 'hipError_t ' + str(status))}")
+
+
+def call(name, *args):
+    """Run a status-returning entry point; raises on any non-zero status.  (One Python frame around the ctypes call: an eager
+    step makes about 350 of these.)"""
+    st = getattr(_lib, name)(*args)
+    if st:
+        check(st, name)
+
+
+def supported(name, *args):
+    """The same for an entry point that may answer UMI_ERR_UNSUPPORTED ("nothing was launched, run the separate passes"):
+    False then, True when it ran."""
+    st = getattr(_lib, name)(*args)
+    if st and st != UMI_ERR_UNSUPPORTED:
+        check(st, name)
+    return not st
 
 
 def fn(name):

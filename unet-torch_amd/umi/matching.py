@@ -366,8 +366,8 @@ def dot_lists(dot_map, max_dots=MAX_DOTS, check=False, _fault=False):
     dots = torch.zeros((N, max_dots, 2), dtype=torch.int32, device=m.device)
     g_count = torch.empty(N, dtype=torch.int32, device=m.device)
     ws = ops.workspace(nbytes, m.device)
-    L.check(L.fn("umi_dot_lists")(m.data_ptr(), 0 if m.dtype == torch.uint8 else 1, dots.data_ptr(), g_count.data_ptr(), N, H, W,
-                                  max_dots, ws.data_ptr(), nbytes, ops._stream()), "umi_dot_lists")
+    L.call("umi_dot_lists", m.data_ptr(), 0 if m.dtype == torch.uint8 else 1, dots.data_ptr(), g_count.data_ptr(), N, H, W,
+           max_dots, ws.data_ptr(), nbytes, ops._stream())
     if check:
         raise_on_dot_overflow(ws[:4].view(torch.int32).item(), max_dots)
     return (dots, g_count, _fault_word(ws)) if _fault else (dots, g_count)
@@ -386,9 +386,8 @@ def component_centers(counts, area, sum_y, sum_x):
         raise ValueError("component_centers expects label_components' counts (N,), area (N,cap) int32 and sum_y, sum_x int64")
     N, cap = area.shape
     centers = torch.empty((N, cap, 2), dtype=torch.int32, device=area.device)
-    L.check(L.fn("umi_component_centers")(counts.contiguous().data_ptr(), area.contiguous().data_ptr(), sum_y.contiguous().data_ptr(),
-                                          sum_x.contiguous().data_ptr(), centers.data_ptr(), N, cap, ops._stream()),
-            "umi_component_centers")
+    L.call("umi_component_centers", counts.contiguous().data_ptr(), area.contiguous().data_ptr(), sum_y.contiguous().data_ptr(),
+           sum_x.contiguous().data_ptr(), centers.data_ptr(), N, cap, ops._stream())
     return centers
 
 
@@ -436,9 +435,9 @@ def crowd_match(dots, g_count, centers, c_count, sigma_list, thresh_list):
     N, max_dots, cap = _lists_on_device(dots, g_count, centers, c_count)
     radii, tables, thr = match_tables(sigma_list, thresh_list, dots.device)
     out = torch.empty((N, len(radii), thr.numel(), 2), dtype=torch.int32, device=dots.device)
-    L.check(L.fn("umi_crowd_match")(dots.data_ptr(), g_count.data_ptr(), max_dots, centers.data_ptr(), c_count.data_ptr(), cap,
-                                    tables.data_ptr(), tables.numel(), radii, len(radii), thr.data_ptr(), thr.numel(),
-                                    out.data_ptr(), N, ops._stream()), "umi_crowd_match")
+    L.call("umi_crowd_match", dots.data_ptr(), g_count.data_ptr(), max_dots, centers.data_ptr(), c_count.data_ptr(), cap,
+           tables.data_ptr(), tables.numel(), radii, len(radii), thr.data_ptr(), thr.numel(),
+           out.data_ptr(), N, ops._stream())
     return out
 
 
@@ -452,9 +451,8 @@ def distance_match(dots, g_count, centers, c_count, thresh):
     out = torch.empty((N, 3), dtype=torch.int32, device=dots.device)
     nbytes = L.fn("umi_distance_match_ws_bytes")(N, cap)
     ws = ops.workspace(nbytes, dots.device)
-    L.check(L.fn("umi_distance_match")(dots.data_ptr(), g_count.data_ptr(), max_dots, centers.data_ptr(), c_count.data_ptr(), cap,
-                                       d2_limit(thresh), out.data_ptr(), N, ws.data_ptr(), nbytes, ops._stream()),
-            "umi_distance_match")
+    L.call("umi_distance_match", dots.data_ptr(), g_count.data_ptr(), max_dots, centers.data_ptr(), c_count.data_ptr(), cap,
+           d2_limit(thresh), out.data_ptr(), N, ws.data_ptr(), nbytes, ops._stream())
     return out
 
 
@@ -474,8 +472,8 @@ def grid_sums(maps, size=512):
     if min(N, H, W) < 1 or N * H * W >= 2 ** 31 or N > 65535:
         raise ValueError(f"grid_sums: unsupported map shape {tuple(maps.shape)}")
     out = torch.empty((N, 8, 8), dtype=torch.int64 if m.dtype == torch.uint8 else torch.float64, device=m.device)
-    L.check(L.fn("umi_grid_sums")(m.data_ptr(), 0 if m.dtype == torch.uint8 else 1, out.data_ptr(), N, H, W, int(size),
-                                  ops._stream()), "umi_grid_sums")
+    L.call("umi_grid_sums", m.data_ptr(), 0 if m.dtype == torch.uint8 else 1, out.data_ptr(), N, H, W, int(size),
+           ops._stream())
     return out
 
 
@@ -491,8 +489,8 @@ def scatter_centers(centers, c_count, H, W):
         raise ValueError("scatter_centers expects centers int32 (N,cap,2) and c_count int32 (N,)")
     N, cap = centers.shape[:2]
     out = torch.empty((N, H, W), dtype=torch.uint8, device=centers.device)
-    L.check(L.fn("umi_scatter_centers")(centers.data_ptr(), c_count.contiguous().data_ptr(), cap, out.data_ptr(), N, H, W,
-                                        ops._stream()), "umi_scatter_centers")
+    L.call("umi_scatter_centers", centers.data_ptr(), c_count.contiguous().data_ptr(), cap, out.data_ptr(), N, H, W,
+           ops._stream())
     return out
 
 
@@ -512,7 +510,7 @@ def split_classes(class_map, n_classes):
     if not 2 <= K <= 256 or min(N, H, W) < 1 or N * (K - 1) * H * W >= 2 ** 31 or N > 65535:
         raise ValueError(f"split_classes: unsupported shape {tuple(class_map.shape)} for {K} classes")
     planes = torch.empty((N, K - 1, H, W), dtype=torch.uint8, device=m.device)
-    L.check(L.fn("umi_split_classes")(m.data_ptr(), planes.data_ptr(), N, H, W, K, ops._stream()), "umi_split_classes")
+    L.call("umi_split_classes", m.data_ptr(), planes.data_ptr(), N, H, W, K, ops._stream())
     return planes
 
 
@@ -536,7 +534,7 @@ def class_center_lists(counts, label_class, area, sum_y, sum_x, n_classes):
         raise ValueError(f"class_center_lists: unsupported size N = {N}, cap = {cap}, {K} classes")
     centers = torch.empty((N * (K - 1), cap, 2), dtype=torch.int32, device=area.device)
     c_count = torch.empty(N * (K - 1), dtype=torch.int32, device=area.device)
-    L.check(L.fn("umi_class_center_lists")(counts.contiguous().data_ptr(), label_class.contiguous().data_ptr(),
-                                           area.contiguous().data_ptr(), sum_y.contiguous().data_ptr(), sum_x.contiguous().data_ptr(),
-                                           centers.data_ptr(), c_count.data_ptr(), N, cap, K, ops._stream()), "umi_class_center_lists")
+    L.call("umi_class_center_lists", counts.contiguous().data_ptr(), label_class.contiguous().data_ptr(),
+           area.contiguous().data_ptr(), sum_y.contiguous().data_ptr(), sum_x.contiguous().data_ptr(),
+           centers.data_ptr(), c_count.data_ptr(), N, cap, K, ops._stream())
     return centers, c_count

@@ -6,6 +6,7 @@ contiguous and whose pixel stride (`stride(2)`) may exceed C (channel slice of a
 concat buffer).
 """
 
+import numpy as np
 import torch
 
 from . import lib as L
@@ -89,9 +90,8 @@ def pack_kn(src: torch.Tensor, T, K, N, st, sk, sn, flip_t, dtype, Kpad=None, Np
     assert src.dtype == torch.float32 and src.is_contiguous()
     Kpad, Npad = Kpad or K, Npad or N
     out = torch.empty(T * Kpad * Npad, dtype=dtype, device=src.device)
-    f = L.fn("umi_pack_kn8" if k8 else "umi_pack_kn")
-    L.check(f(src.data_ptr(), out.data_ptr(), T, K, N, st, sk, sn, int(flip_t), Kpad, Npad, _dt(out), _stream()),
-            "umi_pack_kn")
+    L.call("umi_pack_kn8" if k8 else "umi_pack_kn",
+           src.data_ptr(), out.data_ptr(), T, K, N, st, sk, sn, int(flip_t), Kpad, Npad, _dt(out), _stream())
     return out
 
 
@@ -196,7 +196,6 @@ class PackCache:
         return self._host, self._dev
 
     def _upload(self, arr):
-        import numpy as np
         raw = np.ascontiguousarray(arr).view(np.uint8).reshape(-1)
         nbytes = (raw.size + 15) // 16 * 16
         host, dev = self._buffers()
@@ -208,7 +207,7 @@ class PackCache:
             self._used = 0
         off = self._used
         host.numpy()[off:off + raw.size] = raw
-        L.check(L.fn("umi_table_upload")(host.data_ptr() + off, dev.data_ptr() + off, nbytes, _stream()), "umi_table_upload")
+        L.call("umi_table_upload", host.data_ptr() + off, dev.data_ptr() + off, nbytes, _stream())
         self._used = off + nbytes
         return dev.data_ptr() + off
 
@@ -244,9 +243,8 @@ class PackCache:
         ver = self._ver(w)
         if e.ver != ver:
             T, K, N, st, sk, sn, flip = e.args
-            f = L.fn("umi_pack_kn8" if e.k8 else "umi_pack_kn")
-            L.check(f(w.data_ptr(), e.dst.data_ptr(), T, K, N, st, sk, sn, flip, K, N, _dt(e.dst), _stream()),
-                    "umi_pack_kn")
+            L.call("umi_pack_kn8" if e.k8 else "umi_pack_kn",
+                   w.data_ptr(), e.dst.data_ptr(), T, K, N, st, sk, sn, flip, K, N, _dt(e.dst), _stream())
             e.ver = ver
         return e.dst
 
@@ -303,14 +301,13 @@ class PackCache:
             e.rstd = torch.empty(w.shape[0], dtype=torch.float32, device=w.device)
             self.wstd_total += (w.numel() + 63) // 64 * 64         # 256-byte aligned slots
         if e.ver != ver:
-            L.check(L.fn("umi_wstd_fwd")(w.data_ptr(), e.ws.data_ptr(), e.rstd.data_ptr(), w.shape[0], w[0].numel(), e.eps,
-                                         _stream()), "umi_wstd_fwd")
+            L.call("umi_wstd_fwd", w.data_ptr(), e.ws.data_ptr(), e.rstd.data_ptr(), w.shape[0], w[0].numel(), e.eps,
+                   _stream())
             torch.autograd.graph.increment_version(e.ws)           # its packed copies are stale now
             e.ver = ver
         return e
 
     def _wstd_table(self, ents, dws=None):
-        import numpy as np
         tkey = ("wstd",) + tuple((id(e), e.w().data_ptr()) for e in ents) + (tuple(t.data_ptr() for t in dws) if dws else ())
         tab = self._tables.get(tkey)
         if tab is None:
@@ -329,12 +326,11 @@ class PackCache:
         e.off), in one launch: into dw_flat[e.off:...], or -- `dws`: one fp32 tensor per entry, e.g. the slots of a gradient
         sink's buckets -- straight into those."""
         dev_ptr, rows, n = self._wstd_table(ents, dws)
-        L.check(L.fn("umi_wstd_bwd_multi")(dev_ptr, n, rows, g_flat.data_ptr(), dw_flat.data_ptr() if dw_flat is not None else None,
-                                           _stream()), "umi_wstd_bwd_multi")
+        L.call("umi_wstd_bwd_multi", dev_ptr, n, rows, g_flat.data_ptr(), dw_flat.data_ptr() if dw_flat is not None else None,
+               _stream())
 
     def _repack(self, items):
         """items: [(key, entry, source tensor)] -> one umi_pack_kn_multi launch per storage dtype."""
-        import numpy as np
         by_dtype = {}
         for it in items:
             by_dtype.setdefault(it[1].dst.dtype, []).append(it)
@@ -352,8 +348,8 @@ class PackCache:
                     b0 += (T * K * N + blk - 1) // blk
                 tab = self._tables[tkey] = (self._upload(arr), b0, len(its))
             dev_ptr, total, n = tab
-            L.check(L.fn("umi_pack_kn_multi")(dev_ptr, n, total, L.UMI_F32 if dtype == torch.float32 else L.UMI_F16,
-                                              _stream()), "umi_pack_kn_multi")
+            L.call("umi_pack_kn_multi", dev_ptr, n, total, L.UMI_F32 if dtype == torch.float32 else L.UMI_F16,
+                   _stream())
             for _, e, w in its:
                 e.ver = self._ver(w)
 
@@ -373,7 +369,7 @@ class PackCache:
                 wst.append(e)
         if wst:
             dev_ptr, rows, n = self._wstd_table(wst)
-            L.check(L.fn("umi_wstd_fwd_multi")(dev_ptr, n, rows, _stream()), "umi_wstd_fwd_multi")
+            L.call("umi_wstd_fwd_multi", dev_ptr, n, rows, _stream())
             torch.autograd.graph.increment_version([e.ws for e in wst])
             for e in wst:
                 e.ver = self._ver(e.w())
@@ -389,20 +385,8 @@ class PackCache:
             self._repack(stale)
 
 
-def _np_dtypes():
-    import numpy as np
-    pack = np.dtype([("src", "u8"), ("dst", "u8"), ("st", "i8"), ("sk", "i8"), ("sn", "i8"), ("T", "i4"), ("K", "i4"),
-                     ("N", "i4"), ("flip", "i4"), ("Kpad", "i4"), ("Npad", "i4"), ("k8", "i4"), ("blk0", "i4"),
-                     ("ldn", "i4"), ("pad", "i4")])
-    opt = np.dtype([("p", "u8"), ("g", "u8"), ("s0", "u8"), ("s1", "u8"), ("n", "i8"), ("blk0", "i4"), ("pad", "i4")])
-    wstd = np.dtype([("w", "u8"), ("ws", "u8"), ("rstd", "u8"), ("off", "i8"), ("Co", "i4"), ("K", "i4"), ("eps", "f4"),
-                     ("blk0", "i4"), ("dw", "u8")])
-    # sizeof(umi_pack_desc) / sizeof(umi_optim_desc) / sizeof(umi_wstd_desc)
-    assert pack.itemsize == 80 and opt.itemsize == 48 and wstd.itemsize == 56
-    return pack, opt, wstd
-
-
-_PACK_DESC, OPTIM_DESC, _WSTD_DESC = _np_dtypes()
+# device descriptor tables are filled as numpy records laid out as the header's structs
+_PACK_DESC, OPTIM_DESC, _WSTD_DESC = (np.dtype(L.STRUCTS[n]) for n in ("umi_pack_desc", "umi_optim_desc", "umi_wstd_desc"))
 
 
 # ------------------------------------------------------------------------------------------
@@ -412,9 +396,8 @@ def conv_plan(x, y, R, S, stride, pad, flags=0, has_bias=False):
     N, H, W, Ci, ldx = _nhwc(x)
     _, _, _, Co, ldy = _nhwc(y)
     lay, rows = ctypes.c_int(0), ctypes.c_int(0)
-    L.check(L.fn("umi_conv_fwd_plan")(N, H, W, Ci, Co, R, S, stride, pad, ldx, ldy, _dt(x), _dt(y), flags,
-                                      int(has_bias), ctypes.addressof(lay), ctypes.addressof(rows)),
-            "umi_conv_fwd_plan")
+    L.call("umi_conv_fwd_plan", N, H, W, Ci, Co, R, S, stride, pad, ldx, ldy, _dt(x), _dt(y), flags,
+           int(has_bias), ctypes.addressof(lay), ctypes.addressof(rows))
     return lay.value, rows.value
 
 
@@ -426,7 +409,7 @@ def conv_accumulate_ok(x, y, R, S, stride, pad, flags=0):
     if (x.data_ptr() | y.data_ptr()) & 15:
         return False
     return L.fn("umi_conv_fwd_plan")(N, H, W, Ci, Co, R, S, stride, pad, ldx, ldy, _dt(x), _dt(y),
-                                     flags | L.CONV_ACCUMULATE, 0, None, None) == 0
+                                     flags | L.CONV_ACCUMULATE, 0, None, None) == L.UMI_OK
 
 
 def conv_fwd(x, tx, wp, bias, y, R, S, stride, pad, want_stats=False, flags=0, up_offset=(0, 0)):
@@ -451,10 +434,9 @@ def conv_fwd(x, tx, wp, bias, y, R, S, stride, pad, want_stats=False, flags=0, u
         part = torch.empty(rows * 2 * Co, dtype=torch.float32, device=x.device)
     if tx is not None:
         assert tx.shape == (Ci, 4) and tx.dtype == torch.float32 and tx.is_contiguous()
-    L.check(L.fn("umi_conv_fwd")(x.data_ptr(), ldx, _ptr(tx), wp.data_ptr(), _ptr(bias), y.data_ptr(), ldy,
-                                 _ptr(part), N, H, W, Ci, Co, R, S, stride, pad, Ho, Wo,
-                                 up_offset[0], up_offset[1], oH, oW, _dt(x), _dt(y), flags, _stream()),
-            "umi_conv_fwd")
+    L.call("umi_conv_fwd", x.data_ptr(), ldx, _ptr(tx), wp.data_ptr(), _ptr(bias), y.data_ptr(), ldy,
+           _ptr(part), N, H, W, Ci, Co, R, S, stride, pad, Ho, Wo,
+           up_offset[0], up_offset[1], oH, oW, _dt(x), _dt(y), flags, _stream())
     return part
 
 
@@ -463,21 +445,17 @@ def conv3x3_fwd_act(x, tx, wp8, out_tx, y):
     matrix-core path (nothing was launched)."""
     N, H, W, Ci, ldx = _nhwc(x)
     _, _, _, Co, ldy = _nhwc(y)
-    st = L.fn("umi_conv3x3_fwd_act")(x.data_ptr(), ldx, _ptr(tx), wp8.data_ptr(), out_tx.data_ptr(), y.data_ptr(), ldy,
-                                     N, H, W, Ci, Co, _dt(x), _stream())
-    if st == -2:
-        return False
-    L.check(st, "umi_conv3x3_fwd_act")
-    return True
+    return L.supported("umi_conv3x3_fwd_act", x.data_ptr(), ldx, _ptr(tx), wp8.data_ptr(), out_tx.data_ptr(), y.data_ptr(), ldy,
+                       N, H, W, Ci, Co, _dt(x), _stream())
 
 
 def bn_finalize(part, C, count, gamma, beta, eps, momentum, running_mean, running_var):
     rows = part.numel() // (2 * C)
     tx = torch.empty(C, 4, dtype=torch.float32, device=part.device)
     rstd = torch.empty(C, dtype=torch.float32, device=part.device)
-    L.check(L.fn("umi_bn_finalize")(part.data_ptr(), rows, C, float(count), _ptr(gamma), _ptr(beta), eps, momentum,
-                                    _ptr(running_mean), _ptr(running_var), tx.data_ptr(), rstd.data_ptr(),
-                                    _stream()), "umi_bn_finalize")
+    L.call("umi_bn_finalize", part.data_ptr(), rows, C, float(count), _ptr(gamma), _ptr(beta), eps, momentum,
+           _ptr(running_mean), _ptr(running_var), tx.data_ptr(), rstd.data_ptr(),
+           _stream())
     return tx, rstd
 
 
@@ -485,16 +463,15 @@ def pool2_fwd(x, tx, y):
     N, H, W, C, ldx = _nhwc(x)
     _, Ho, Wo, _, ldy = _nhwc(y)
     assert (Ho, Wo) == (H // 2, W // 2)
-    L.check(L.fn("umi_pool2_fwd")(x.data_ptr(), ldx, _ptr(tx), y.data_ptr(), ldy, N, H, W, C, _dt(x), _stream()),
-            "umi_pool2_fwd")
+    L.call("umi_pool2_fwd", x.data_ptr(), ldx, _ptr(tx), y.data_ptr(), ldy, N, H, W, C, _dt(x), _stream())
 
 
 def pool2_bwd(dpool, x, tx, da, accumulate):
     N, H, W, C, ldx = _nhwc(x)
     _, _, _, _, lddp = _nhwc(dpool)
     _, _, _, _, ldda = _nhwc(da)
-    L.check(L.fn("umi_pool2_bwd")(dpool.data_ptr(), lddp, x.data_ptr(), ldx, _ptr(tx), da.data_ptr(), ldda,
-                                  int(accumulate), N, H, W, C, _dt(x), _stream()), "umi_pool2_bwd")
+    L.call("umi_pool2_bwd", dpool.data_ptr(), lddp, x.data_ptr(), ldx, _ptr(tx), da.data_ptr(), ldda,
+           int(accumulate), N, H, W, C, _dt(x), _stream())
 
 
 def bn_stats(y):
@@ -505,10 +482,8 @@ def bn_stats(y):
     if rows <= 0:
         return None
     part = torch.empty(rows * 2 * C, dtype=torch.float32, device=y.device)
-    st = L.fn("umi_bn_stats")(y.data_ptr(), ldy, part.data_ptr(), M, C, _dt(y), _stream())
-    if st == -2:
+    if not L.supported("umi_bn_stats", y.data_ptr(), ldy, part.data_ptr(), M, C, _dt(y), _stream()):
         return None
-    L.check(st, "umi_bn_stats")
     return part
 
 
@@ -520,12 +495,10 @@ def pool2_bwd_bnred(dpool, x, tx, rstd, da, accumulate):
     if rows <= 0 or x.dtype != torch.float16 or tx is None or rstd is None:
         return None
     part = torch.empty(rows * 2 * C, dtype=torch.float32, device=x.device)
-    st = L.fn("umi_pool2_bwd_bnred")(dpool.data_ptr(), _nhwc(dpool)[4], x.data_ptr(), ldx, tx.data_ptr(), rstd.data_ptr(),
-                                     da.data_ptr(), _nhwc(da)[4], int(accumulate), part.data_ptr(), N, H, W, C, _dt(x),
-                                     _stream())
-    if st == -2:                                   # UMI_ERR_UNSUPPORTED (alignment / strides): not an error
-        return None
-    L.check(st, "umi_pool2_bwd_bnred")
+    if not L.supported("umi_pool2_bwd_bnred", dpool.data_ptr(), _nhwc(dpool)[4], x.data_ptr(), ldx, tx.data_ptr(),
+                       rstd.data_ptr(), da.data_ptr(), _nhwc(da)[4], int(accumulate), part.data_ptr(), N, H, W, C, _dt(x),
+                       _stream()):
+        return None                                # UMI_ERR_UNSUPPORTED (alignment / strides): not an error
     return part
 
 
@@ -559,11 +532,9 @@ def conv_dgrad_bnred(dy, wp8, da, ybn, txbn, rstd):
     if lay != 1:
         return None
     part = torch.empty(rows * 2 * Co, dtype=torch.float32, device=dy.device)
-    st = L.fn("umi_conv_dgrad_bnred")(dy.data_ptr(), lddy, wp8.data_ptr(), da.data_ptr(), ldda, ybn.data_ptr(), ldybn,
-                                      txbn.data_ptr(), rstd.data_ptr(), part.data_ptr(), N, H, W, Ci, Co, _dt(dy), _stream())
-    if st == -2:
+    if not L.supported("umi_conv_dgrad_bnred", dy.data_ptr(), lddy, wp8.data_ptr(), da.data_ptr(), ldda, ybn.data_ptr(), ldybn,
+                       txbn.data_ptr(), rstd.data_ptr(), part.data_ptr(), N, H, W, Ci, Co, _dt(dy), _stream()):
         return None
-    L.check(st, "umi_conv_dgrad_bnred")
     return part
 
 
@@ -582,12 +553,10 @@ def conv_gather_bnred(x, wp8, y, ybn, txbn, rstd, R, S, stride, pad, flags=0):
     if rows <= 0:
         return None
     part = torch.empty(rows * 2 * Co, dtype=torch.float32, device=x.device)
-    st = L.fn("umi_conv_gather_bnred")(x.data_ptr(), ldx, wp8.data_ptr(), y.data_ptr(), ldy, ybn.data_ptr(), ldybn,
-                                       txbn.data_ptr(), rstd.data_ptr(), part.data_ptr(), N, H, W, Ci, Co, R, S, stride, pad,
-                                       Ho, Wo, _dt(x), flags, _stream())
-    if st == -2:
+    if not L.supported("umi_conv_gather_bnred", x.data_ptr(), ldx, wp8.data_ptr(), y.data_ptr(), ldy, ybn.data_ptr(), ldybn,
+                       txbn.data_ptr(), rstd.data_ptr(), part.data_ptr(), N, H, W, Ci, Co, R, S, stride, pad,
+                       Ho, Wo, _dt(x), flags, _stream()):
         return None
-    L.check(st, "umi_conv_gather_bnred")
     return part
 
 
@@ -609,18 +578,14 @@ def head_dgrad_bnred(dl, wp, da, ybn, txbn, rstd, dW=None, out_scale=1.0):
     if dW is not None:
         assert dW.dtype == torch.float32 and dW.is_contiguous() and dW.numel() == Ci * Co
         ws = workspace(L.fn("umi_head_bwd_fused_ws_bytes")(P, Ci, Co), dl.device)
-        st = L.fn("umi_head_bwd_fused")(dl.data_ptr(), lddl, wp.data_ptr(), da.data_ptr(), ldda, ybn.data_ptr(), ldybn,
-                                        txbn.data_ptr(), rstd.data_ptr(), part.data_ptr(), dW.data_ptr(), Co, 1, out_scale,
-                                        ws.data_ptr(), ws.numel(), P, Ci, Co, _dt(dl), _stream())
-        if st == -2:
+        if not L.supported("umi_head_bwd_fused", dl.data_ptr(), lddl, wp.data_ptr(), da.data_ptr(), ldda, ybn.data_ptr(), ldybn,
+                           txbn.data_ptr(), rstd.data_ptr(), part.data_ptr(), dW.data_ptr(), Co, 1, out_scale,
+                           ws.data_ptr(), ws.numel(), P, Ci, Co, _dt(dl), _stream()):
             return None
-        L.check(st, "umi_head_bwd_fused")
         return part
-    st = L.fn("umi_head_dgrad_bnred")(dl.data_ptr(), lddl, wp.data_ptr(), da.data_ptr(), ldda, ybn.data_ptr(), ldybn,
-                                      txbn.data_ptr(), rstd.data_ptr(), part.data_ptr(), P, Ci, Co, _dt(dl), _stream())
-    if st == -2:
+    if not L.supported("umi_head_dgrad_bnred", dl.data_ptr(), lddl, wp.data_ptr(), da.data_ptr(), ldda, ybn.data_ptr(), ldybn,
+                       txbn.data_ptr(), rstd.data_ptr(), part.data_ptr(), P, Ci, Co, _dt(dl), _stream()):
         return None
-    L.check(st, "umi_head_dgrad_bnred")
     return part
 
 
@@ -635,12 +600,12 @@ def bn_bwd(da, y, tx, rstd, partials=None, apply=True):
     ws = workspace(nb, y.device)
     sums = torch.empty(2, C, dtype=torch.float32, device=y.device)
     if partials is not None:
-        L.check(L.fn("umi_bn_bwd_from_partials")(partials.data_ptr(), partials.numel() // (2 * C), C, sums[0].data_ptr(),
-                                                 sums[1].data_ptr(), _stream()), "umi_bn_bwd_from_partials")
+        L.call("umi_bn_bwd_from_partials", partials.data_ptr(), partials.numel() // (2 * C), C, sums[0].data_ptr(),
+               sums[1].data_ptr(), _stream())
     else:
-        L.check(L.fn("umi_bn_bwd_reduce")(da.data_ptr(), ldda, y.data_ptr(), ldy, tx.data_ptr(), rstd.data_ptr(),
-                                          sums[0].data_ptr(), sums[1].data_ptr(), M, C, _dt(y), ws.data_ptr(),
-                                          ws.numel(), _stream()), "umi_bn_bwd_reduce")
+        L.call("umi_bn_bwd_reduce", da.data_ptr(), ldda, y.data_ptr(), ldy, tx.data_ptr(), rstd.data_ptr(),
+               sums[0].data_ptr(), sums[1].data_ptr(), M, C, _dt(y), ws.data_ptr(),
+               ws.numel(), _stream())
     if apply:
         bn_bwd_apply(da, y, tx, rstd, sums[0], sums[1])
     return sums[0], sums[1]
@@ -648,9 +613,8 @@ def bn_bwd(da, y, tx, rstd, partials=None, apply=True):
 
 def bn_bwd_apply(da, y, tx, rstd, sum_dz, sum_dzx):
     N, H, W, C, ldy = _nhwc(y)
-    L.check(L.fn("umi_bn_bwd_apply")(da.data_ptr(), _nhwc(da)[4], y.data_ptr(), ldy, tx.data_ptr(), rstd.data_ptr(),
-                                     sum_dz.data_ptr(), sum_dzx.data_ptr(), N * H * W, C, _dt(y), _stream()),
-            "umi_bn_bwd_apply")
+    L.call("umi_bn_bwd_apply", da.data_ptr(), _nhwc(da)[4], y.data_ptr(), ldy, tx.data_ptr(), rstd.data_ptr(),
+           sum_dz.data_ptr(), sum_dzx.data_ptr(), N * H * W, C, _dt(y), _stream())
 
 
 def conv_wgrad_bnapply(x, txa, da, y, tx_bn, rstd, sum_dz, sum_dzx, dz, dW, s_co, s_ci, s_t, out_scale, R, S, stride, pad):
@@ -664,20 +628,14 @@ def conv_wgrad_bnapply(x, txa, da, y, tx_bn, rstd, sum_dz, sum_dzx, dz, dW, s_co
     nb = L.fn("umi_conv_wgrad_ws_bytes")(N, Ho, Wo, Ci, Co, R, S, _dt(x), 0)
     ws = workspace(nb, x.device)
     # dz None: the layer's input takes no gradient, nothing else reads dz (the network's first conv: formed on the fly, never stored)
-    st = L.fn("umi_conv_wgrad_bnapply")(x.data_ptr(), ldx, _ptr(txa), da.data_ptr(), ldda, y.data_ptr(), _nhwc(y)[4],
-                                        tx_bn.data_ptr(), rstd.data_ptr(), sum_dz.data_ptr(), sum_dzx.data_ptr(),
-                                        _ptr(dz), _nhwc(dz)[4] if dz is not None else 0, dW.data_ptr(), s_co, s_ci, s_t, out_scale,
-                                        N, H, W, Ci, Co, R, S, stride, pad, _dt(x), 0, ws.data_ptr(), ws.numel(), _stream())
-    if st == -2:                                   # UMI_ERR_UNSUPPORTED: not an error, the caller runs the two passes
-        return False
-    L.check(st, "umi_conv_wgrad_bnapply")
-    return True
+    # UMI_ERR_UNSUPPORTED: not an error, the caller runs the two passes
+    return L.supported("umi_conv_wgrad_bnapply", x.data_ptr(), ldx, _ptr(txa), da.data_ptr(), ldda, y.data_ptr(), _nhwc(y)[4],
+                       tx_bn.data_ptr(), rstd.data_ptr(), sum_dz.data_ptr(), sum_dzx.data_ptr(),
+                       _ptr(dz), _nhwc(dz)[4] if dz is not None else 0, dW.data_ptr(), s_co, s_ci, s_t, out_scale,
+                       N, H, W, Ci, Co, R, S, stride, pad, _dt(x), 0, ws.data_ptr(), ws.numel(), _stream())
 
 
-class _WgPending(__import__("ctypes").Structure):          # mirrors umi_wgrad_pending
-    import ctypes as _c
-    _fields_ = [("part", _c.c_void_p), ("dW", _c.c_void_p), ("s_co", _c.c_long), ("s_ci", _c.c_long), ("s_t", _c.c_long),
-                ("scale", _c.c_float), ("splits", _c.c_int), ("RS", _c.c_int), ("Ci", _c.c_int), ("Co", _c.c_int)]
+_WgPending = L.STRUCTS["umi_wgrad_pending"]
 
 
 def conv_wgrad(x, txa, dy, txb, dW, s_co, s_ci, s_t, out_scale, R, S, stride, pad, flags=0, defer=None):
@@ -690,16 +648,15 @@ def conv_wgrad(x, txa, dy, txb, dW, s_co, s_ci, s_t, out_scale, R, S, stride, pa
     nb = L.fn("umi_conv_wgrad_ws_bytes")(N, Ho, Wo, Ci, Co, R, S, _dt(x), flags)
     if defer is None:
         ws = workspace(nb, x.device)
-        L.check(L.fn("umi_conv_wgrad")(x.data_ptr(), ldx, _ptr(txa), dy.data_ptr(), lddy, _ptr(txb), dW.data_ptr(),
-                                       s_co, s_ci, s_t, out_scale, N, H, W, Ci, Co, R, S, stride, pad, Ho, Wo,
-                                       _dt(x), flags, ws.data_ptr(), ws.numel(), _stream()), "umi_conv_wgrad")
+        L.call("umi_conv_wgrad", x.data_ptr(), ldx, _ptr(txa), dy.data_ptr(), lddy, _ptr(txb), dW.data_ptr(),
+               s_co, s_ci, s_t, out_scale, N, H, W, Ci, Co, R, S, stride, pad, Ho, Wo,
+               _dt(x), flags, ws.data_ptr(), ws.numel(), _stream())
         return
     ws = torch.empty(max(nb, 16), dtype=torch.uint8, device=x.device)
     pend = _WgPending()
-    L.check(L.fn("umi_conv_wgrad_deferred")(x.data_ptr(), ldx, _ptr(txa), dy.data_ptr(), lddy, _ptr(txb), dW.data_ptr(),
-                                            s_co, s_ci, s_t, out_scale, N, H, W, Ci, Co, R, S, stride, pad, Ho, Wo,
-                                            _dt(x), flags, ws.data_ptr(), ws.numel(), ctypes.addressof(pend), _stream()),
-            "umi_conv_wgrad_deferred")
+    L.call("umi_conv_wgrad_deferred", x.data_ptr(), ldx, _ptr(txa), dy.data_ptr(), lddy, _ptr(txb), dW.data_ptr(),
+           s_co, s_ci, s_t, out_scale, N, H, W, Ci, Co, R, S, stride, pad, Ho, Wo,
+           _dt(x), flags, ws.data_ptr(), ws.numel(), ctypes.addressof(pend), _stream())
     if pend.part:
         defer.append((pend, ws, dW))
 
@@ -718,12 +675,10 @@ def convT_wgrad_bias(g, y, txy, dW, dbias, out_scale, defer=None):
     ws = torch.empty(max(nb, 16), dtype=torch.uint8, device=g.device) if defer is not None else workspace(nb, g.device)
     pend = _WgPending()
     assert dW.numel() == Ci * Co * 4                 # [Co][Ci][2][2] = ConvTranspose2d's [in][out][2][2]: in = y's channels, out = g's
-    st = L.fn("umi_conv_wgrad_bias")(g.data_ptr(), ldx, y.data_ptr(), lddy, _ptr(txy), dW.data_ptr(), Ci * 4, 4, 1, dbias.data_ptr(),
-                                     out_scale, N, H, W, Ci, Co, Ho, Wo, _dt(g), 0, ws.data_ptr(), ws.numel(),
-                                     ctypes.addressof(pend) if defer is not None else None, _stream())
-    if st == -2:
+    if not L.supported("umi_conv_wgrad_bias", g.data_ptr(), ldx, y.data_ptr(), lddy, _ptr(txy), dW.data_ptr(), Ci * 4, 4, 1,
+                       dbias.data_ptr(), out_scale, N, H, W, Ci, Co, Ho, Wo, _dt(g), 0, ws.data_ptr(), ws.numel(),
+                       ctypes.addressof(pend) if defer is not None else None, _stream()):
         return False
-    L.check(st, "umi_conv_wgrad_bias")
     if defer is not None and pend.part:
         defer.append((pend, ws, dW))
     return True
@@ -766,21 +721,17 @@ def conv_wgrad_group(xs, dys, dWs, s_co, s_ci, out_scale):
         assert dW.dtype == torch.float32
     arr = ctypes.c_void_p * n
     ptrs = [arr(*[t.data_ptr() for t in ts]) for ts in (xs, dys, dWs)]
-    st = L.fn("umi_conv_wgrad_group")(n, ctypes.cast(ptrs[0], ctypes.c_void_p), ldx, ctypes.cast(ptrs[1], ctypes.c_void_p), lddy,
-                                      ctypes.cast(ptrs[2], ctypes.c_void_p), s_co, s_ci, out_scale, N * H * W, Ci, Co,
-                                      _dt(xs[0]), _stream())
-    if st == -2:
-        return False
-    L.check(st, "umi_conv_wgrad_group")
-    return True
+    return L.supported("umi_conv_wgrad_group", n, ctypes.cast(ptrs[0], ctypes.c_void_p), ldx,
+                       ctypes.cast(ptrs[1], ctypes.c_void_p), lddy, ctypes.cast(ptrs[2], ctypes.c_void_p), s_co, s_ci, out_scale,
+                       N * H * W, Ci, Co, _dt(xs[0]), _stream())
 
 
 def colsum(x, out, out_scale):
     N, H, W, C, ldx = _nhwc(x)
     M = N * H * W
     ws = workspace(L.fn("umi_colsum_ws_bytes")(M, C), x.device)
-    L.check(L.fn("umi_colsum")(x.data_ptr(), ldx, out.data_ptr(), out_scale, M, C, _dt(x), ws.data_ptr(),
-                               ws.numel(), _stream()), "umi_colsum")
+    L.call("umi_colsum", x.data_ptr(), ldx, out.data_ptr(), out_scale, M, C, _dt(x), ws.data_ptr(),
+           ws.numel(), _stream())
 
 
 def colsum_group(xs, outs, out_scale):
@@ -797,12 +748,8 @@ def colsum_group(xs, outs, out_scale):
     ws = workspace(min(n, 16) * L.fn("umi_colsum_ws_bytes")(M, C), xs[0].device)
     arr = ctypes.c_void_p * n
     px, po = arr(*[t.data_ptr() for t in xs]), arr(*[t.data_ptr() for t in outs])
-    st = L.fn("umi_colsum_group")(n, ctypes.cast(px, ctypes.c_void_p), ldx, ctypes.cast(po, ctypes.c_void_p), out_scale, M, C,
-                                  _dt(xs[0]), ws.data_ptr(), ws.numel(), _stream())
-    if st == -2:
-        return False
-    L.check(st, "umi_colsum_group")
-    return True
+    return L.supported("umi_colsum_group", n, ctypes.cast(px, ctypes.c_void_p), ldx, ctypes.cast(po, ctypes.c_void_p), out_scale,
+                       M, C, _dt(xs[0]), ws.data_ptr(), ws.numel(), _stream())
 
 
 def add2_relu(a, txa, b, txb, y):
@@ -811,34 +758,33 @@ def add2_relu(a, txa, b, txb, y):
     _, _, _, _, ldb = _nhwc(b)
     _, _, _, _, ldy = _nhwc(y)
     assert a.shape == b.shape == y.shape
-    L.check(L.fn("umi_add2_relu_fwd")(a.data_ptr(), lda, _ptr(txa), b.data_ptr(), ldb, _ptr(txb), y.data_ptr(), ldy,
-                                      N * H * W, C, _dt(a), _stream()), "umi_add2_relu_fwd")
+    L.call("umi_add2_relu_fwd", a.data_ptr(), lda, _ptr(txa), b.data_ptr(), ldb, _ptr(txb), y.data_ptr(), ldy,
+           N * H * W, C, _dt(a), _stream())
 
 
 def add2_relu_bwd(dy, y, da, db):
     N, H, W, C, lddy = _nhwc(dy)
-    L.check(L.fn("umi_add2_relu_bwd")(dy.data_ptr(), lddy, y.data_ptr(), _nhwc(y)[4], da.data_ptr(), _nhwc(da)[4],
-                                      db.data_ptr(), _nhwc(db)[4], N * H * W, C, _dt(dy), _stream()), "umi_add2_relu_bwd")
+    L.call("umi_add2_relu_bwd", dy.data_ptr(), lddy, y.data_ptr(), _nhwc(y)[4], da.data_ptr(), _nhwc(da)[4],
+           db.data_ptr(), _nhwc(db)[4], N * H * W, C, _dt(dy), _stream())
 
 
 def gate(x, txx, p, txp, y):
     """y <- txx(x) * sigmoid(txp(p)), p: [N,H,W,1] (reference Model.py:303-304)."""
     N, H, W, C, ldx = _nhwc(x)
     assert tuple(p.shape) == (N, H, W, 1) and p.is_contiguous() and y.shape == x.shape
-    L.check(L.fn("umi_gate_fwd")(x.data_ptr(), ldx, _ptr(txx), p.data_ptr(), _ptr(txp), y.data_ptr(), _nhwc(y)[4],
-                                 N * H * W, C, _dt(x), _stream()), "umi_gate_fwd")
+    L.call("umi_gate_fwd", x.data_ptr(), ldx, _ptr(txx), p.data_ptr(), _ptr(txp), y.data_ptr(), _nhwc(y)[4],
+           N * H * W, C, _dt(x), _stream())
 
 
 def gate_bwd(dy, x, txx, p, txp, dx, dp):
     N, H, W, C, ldx = _nhwc(x)
     assert dp.is_contiguous() and tuple(dp.shape) == (N, H, W, 1)
-    L.check(L.fn("umi_gate_bwd")(dy.data_ptr(), _nhwc(dy)[4], x.data_ptr(), ldx, _ptr(txx), p.data_ptr(), _ptr(txp),
-                                 dx.data_ptr(), _nhwc(dx)[4], dp.data_ptr(), N * H * W, C, _dt(x), _stream()), "umi_gate_bwd")
+    L.call("umi_gate_bwd", dy.data_ptr(), _nhwc(dy)[4], x.data_ptr(), ldx, _ptr(txx), p.data_ptr(), _ptr(txp),
+           dx.data_ptr(), _nhwc(dx)[4], dp.data_ptr(), N * H * W, C, _dt(x), _stream())
 
 
 def materialize_nchw(x, tx):
     N, H, W, C, ldx = _nhwc(x)
     y = torch.empty(N, C, H, W, dtype=torch.float32, device=x.device)
-    L.check(L.fn("umi_materialize_nchw")(x.data_ptr(), ldx, _ptr(tx), y.data_ptr(), N, H, W, C, _dt(x), _stream()),
-            "umi_materialize_nchw")
+    L.call("umi_materialize_nchw", x.data_ptr(), ldx, _ptr(tx), y.data_ptr(), N, H, W, C, _dt(x), _stream())
     return y

@@ -72,8 +72,7 @@ class _Table:
             if ev is not None and not capturing:
                 ev.synchronize()
             self.host[self.turn].numpy()[:raw.size] = raw
-            L.check(L.fn("umi_table_upload")(self.host[self.turn].data_ptr(), self.dev.data_ptr(), raw.size, ops._stream()),
-                    "umi_table_upload")
+            L.call("umi_table_upload", self.host[self.turn].data_ptr(), self.dev.data_ptr(), raw.size, ops._stream())
             if not capturing:
                 self.events[self.turn] = torch.cuda.Event()
                 self.events[self.turn].record()
@@ -91,10 +90,7 @@ def _table(tabs, key, cap, rows, also=()):
     return tabs.setdefault(key + (cap,), _Table()).get(rows)
 
 
-_HYPER = np.dtype([("lr", "f8"), ("base_lr", "f8"), ("iter", "f8"), ("max_iter", "f8"), ("power", "f8"), ("adam_t", "f8"),
-                   ("beta1", "f8"), ("beta2", "f8"), ("lr_f", "f4"), ("step_size_f", "f4"), ("bc2_sqrt_f", "f4"), ("pad", "f4"),
-                   ("pad2", "f8", 2)])
-assert _HYPER.itemsize == 96           # sizeof(umi_optim_hyper)
+_HYPER = np.dtype(L.STRUCTS["umi_optim_hyper"])
 
 
 class _DeviceHyper:
@@ -126,10 +122,10 @@ class _DeviceHyper:
                 if len(steps) > 1:
                     raise RuntimeError("umi.optim: device_schedule() needs one common Adam step count per param group")
                 h["adam_t"] = steps.pop() if steps else 0.0
-            host = torch.empty(96, dtype=torch.uint8).pin_memory()
+            host = torch.empty(_HYPER.itemsize, dtype=torch.uint8).pin_memory()
             host.numpy()[:] = h.view(np.uint8).reshape(-1)
-            dev = torch.empty(96, dtype=torch.uint8, device="cuda")
-            L.check(L.fn("umi_table_upload")(host.data_ptr(), dev.data_ptr(), 96, ops._stream()), "umi_table_upload")
+            dev = torch.empty(_HYPER.itemsize, dtype=torch.uint8, device="cuda")
+            L.call("umi_table_upload", host.data_ptr(), dev.data_ptr(), _HYPER.itemsize, ops._stream())
             blocks.append((dev, host))
         torch.cuda.current_stream().synchronize()
         self._umi_hyper, self._umi_poly = blocks, poly is not None
@@ -227,21 +223,21 @@ class SGD(_DeviceHyper, torch.optim.SGD):
             cap = torch.cuda.is_current_stream_capturing()       # a captured table-upload node re-reads its own staging buffers
             hyper = self.device_hyper
             if hyper is not None:
-                L.check(L.fn("umi_optim_hyper_pre")(hyper[gi][0].data_ptr(), 0, ops._stream()), "umi_optim_hyper_pre")
+                L.call("umi_optim_hyper_pre", hyper[gi][0].data_ptr(), 0, ops._stream())
             for first, rr in rows.items():
                 if not rr:
                     continue
                 ptr, n, blocks = _table(tabs, (gi, first), cap, rr, also=((gi, False),))   # the step after a first step
                 if hyper is not None:
-                    L.check(L.fn("umi_optim_sgd_multi_dev")(ptr, n, blocks, hyper[gi][0].data_ptr(), mom, float(group["dampening"]),
-                                                            float(group["weight_decay"]), int(bool(group["nesterov"])),
-                                                            int(first), ops._stream()), "umi_optim_sgd_multi_dev")
+                    L.call("umi_optim_sgd_multi_dev", ptr, n, blocks, hyper[gi][0].data_ptr(), mom, float(group["dampening"]),
+                           float(group["weight_decay"]), int(bool(group["nesterov"])),
+                           int(first), ops._stream())
                 else:
-                    L.check(L.fn("umi_optim_sgd_multi")(ptr, n, blocks, float(group["lr"]), mom, float(group["dampening"]),
-                                                        float(group["weight_decay"]), int(bool(group["nesterov"])), int(first),
-                                                        ops._stream()), "umi_optim_sgd_multi")
+                    L.call("umi_optim_sgd_multi", ptr, n, blocks, float(group["lr"]), mom, float(group["dampening"]),
+                           float(group["weight_decay"]), int(bool(group["nesterov"])), int(first),
+                           ops._stream())
             if hyper is not None and self._umi_poly:
-                L.check(L.fn("umi_optim_hyper_poly")(hyper[gi][0].data_ptr(), ops._stream()), "umi_optim_hyper_poly")
+                L.call("umi_optim_hyper_poly", hyper[gi][0].data_ptr(), ops._stream())
             for p, _ in touched:
                 _bump(p)
         return loss
@@ -293,21 +289,19 @@ class Adam(_DeviceHyper, torch.optim.Adam):
                 touched.append((p, g))
             tabs = self.__dict__.setdefault("_umi_tables", {})
             if hyper is not None and touched:
-                L.check(L.fn("umi_optim_hyper_pre")(hyper[gi][0].data_ptr(), 1, ops._stream()), "umi_optim_hyper_pre")
+                L.call("umi_optim_hyper_pre", hyper[gi][0].data_ptr(), 1, ops._stream())
             for slot, (t, rr) in enumerate(sorted(by_step.items())):
                 ptr, n, blocks = _table(tabs, (gi, slot), cap, rr)
                 if hyper is not None:
-                    L.check(L.fn("umi_optim_adam_multi_dev")(ptr, n, blocks, hyper[gi][0].data_ptr(), b1, b2, float(group["eps"]),
-                                                             float(group["weight_decay"]), ops._stream()),
-                            "umi_optim_adam_multi_dev")
+                    L.call("umi_optim_adam_multi_dev", ptr, n, blocks, hyper[gi][0].data_ptr(), b1, b2, float(group["eps"]),
+                           float(group["weight_decay"]), ops._stream())
                     continue
                 bc1 = 1.0 - b1 ** t
                 bc2 = 1.0 - b2 ** t
-                L.check(L.fn("umi_optim_adam_multi")(ptr, n, blocks, float(group["lr"]) / bc1, b1, b2, math.sqrt(bc2),
-                                                     float(group["eps"]), float(group["weight_decay"]), ops._stream()),
-                        "umi_optim_adam_multi")
+                L.call("umi_optim_adam_multi", ptr, n, blocks, float(group["lr"]) / bc1, b1, b2, math.sqrt(bc2),
+                       float(group["eps"]), float(group["weight_decay"]), ops._stream())
             if hyper is not None and self._umi_poly and touched:
-                L.check(L.fn("umi_optim_hyper_poly")(hyper[gi][0].data_ptr(), ops._stream()), "umi_optim_hyper_poly")
+                L.call("umi_optim_hyper_poly", hyper[gi][0].data_ptr(), ops._stream())
             for p, _ in touched:
                 _bump(p)
         return loss
