@@ -45,12 +45,19 @@ enum { UMI_CONV_UPSAMPLE2 = 1,   /* ConvTranspose2d(k=2,s=2): tap t=(dy,dx) scat
                                       consumers (attention gate, reference Model.py:268-289: g and x each feed two branches).  Only
                                       the pointwise / tap-gather MFMA kernel implements it: umi_conv_fwd_plan and umi_conv_fwd return
                                       UMI_ERR_UNSUPPORTED for any other problem, nothing is written */
-       UMI_CONV_F32_MFMA = 16      /* opt-in: an fp32 3x3 / stride 1 / pad 1 conv (forward, data gradient, weight gradient) runs on the
+       UMI_CONV_F32_MFMA = 16,     /* opt-in: an fp32 3x3 / stride 1 / pad 1 conv (forward, data gradient, weight gradient) runs on the
                                       fp32-input matrix-core instruction (v_mfma_f32_32x32x2_f32: one fp32 rounding per product, an
                                       fmaf chain like the generic kernel's in another order).  Taken when in and out are UMI_F32, no
                                       bias, none of the flags above, Ci % 8 == Co % 8 == 0 and ldx % 4 == ldy % 4 == 0 (weight
                                       gradient: no transform on dy either); IGNORED otherwise: the call, umi_conv_fwd_plan and
-                                      umi_conv_wgrad_ws_bytes then answer exactly as without it */ };
+                                      umi_conv_wgrad_ws_bytes then answer exactly as without it */
+       UMI_CONV_F32_MFMA_1X1 = 32  /* opt-in, independent of the flag above: an fp32 pointwise conv / nn.Linear (R = S = 1, stride 1,
+                                      pad 0: Y[M, Co] = X[M, Ci] . W[Ci, Co], M = N * H * W; forward, data gradient, weight gradient)
+                                      runs on the same instruction (csrc/gemm_mfma_f32.hip).  Taken when in and out are UMI_F32, none
+                                      of the flags 1, 2, 4, 8 is set, Ci % 8 == Co % 8 == 0 and ldx % 4 == ldy % 4 == 0 (weight
+                                      gradient: lddy % 4 == 0 and no transform on dy); a bias, an input transform and statistics are
+                                      all allowed.  IGNORED otherwise, like the flag above: UMI_CONV_F32_MFMA on a 1x1 call and this
+                                      flag on a 3x3 call are ignored, both together name the kernel that fits the geometry */ };
 
 int umi_version(void);
 const char* umi_arch(void);          /* "gfx950" */
@@ -110,6 +117,9 @@ int umi_linear_fused(const void* x, int ldx, const void* wp8, const float* bias,
  * With UMI_CONV_F32_MFMA, where that flag's conditions hold, the fp32 matrix-core 3x3 kernel is named instead: *layout = 0 (it
  * reads umi_pack_kn's [tap][k][n], the flipped / transposed pack for a data gradient) and *stat_rows = one row per 8 x 32 pixel
  * tile, N * ceil(H / 8) * ceil(W / 32); a plan that names it is never followed by UMI_ERR_UNSUPPORTED from umi_conv_fwd.
+ * With UMI_CONV_F32_MFMA_1X1, where that flag's conditions hold, the fp32 matrix-core pointwise kernel is named: *layout = 0
+ * (umi_pack_kn's [1][Ci][Co]; the transposed pack for a data gradient) and *stat_rows = one row per 128 consecutive output rows,
+ * ceil(N * H * W / 128); a plan that names it is never followed by UMI_ERR_UNSUPPORTED from umi_conv_fwd either.
  * *stat_rows = rows of `stat_part` the call will write.  UMI_ERR_UNSUPPORTED: UMI_CONV_ACCUMULATE off the pointwise kernel. */
 int umi_conv_fwd_plan(int N, int H, int W, int Ci, int Co, int R, int S, int stride, int pad,
                       int ldx, int ldy, int in_dtype, int out_dtype, int flags, int has_bias,
@@ -205,7 +215,11 @@ int umi_bn_bwd_from_partials(const float* part, int rows, int C, float* sum_dz, 
  *   dW[co*s_co + ci*s_ci + t*s_t] = out_scale * sum_{n,ho,wo} txa(x[...,ci]) * txb(dy[n,ho,wo,co])
  * fp32 output in the parameter's own layout (OIHW: s_co=Ci*R*S, s_ci=R*S, s_t=1).
  * Deterministic: split-K partial slabs in `ws`, reduced in fixed order.  `flags`: UMI_CONV_FORCE_GENERIC, UMI_CONV_F32_MFMA
- * (pass the same flags to umi_conv_wgrad_ws_bytes: the fp32 matrix-core kernel splits the pixels its own way). */
+ * and UMI_CONV_F32_MFMA_1X1 (pass the same flags to umi_conv_wgrad_ws_bytes: the fp32 matrix-core kernels split the pixels their
+ * own way).  The split rule of the pointwise fp32 matrix-core kernel: the M = N * Ho * Wo rows are cut into chunks of 32; with
+ * tiles = ceil(Ci / TI) * ceil(Co / TJ), TI = 64 if Ci <= 64 else 128 and TJ likewise from Co, it wants ceil(512 / tiles) splits
+ * but at most ceil(chunks / 4), at least 1; a split is ceil(chunks / wanted) consecutive chunks, splits = ceil(chunks / that), and
+ * the workspace is splits slabs of Ci * Co fp32 values, [split][1][Ci][Co]. */
 size_t umi_conv_wgrad_ws_bytes(int N, int Ho, int Wo, int Ci, int Co, int R, int S, int dtype, int flags);
 int umi_conv_wgrad(const void* x, int ldx, const void* txa, const void* dy, int lddy, const void* txb,
                    float* dW, long s_co, long s_ci, long s_t, float out_scale,

@@ -11,8 +11,9 @@ only own parameters and buffers.
 
 Build-specific, keyword-only extras (never positional, so reference call sites are
 unaffected): `compute_dtype` = "fp16" (fp16 storage + fp32 accumulate, loss-scaled
-gradients; default, env UMI_COMPUTE_DTYPE), "fp32" (parity mode) or "fp32_mfma" ("fp32" in storage,
-state and every kernel but the 3x3 convolutions, which run on the fp32-input matrix-core kernels).
+gradients; default, env UMI_COMPUTE_DTYPE), "fp32" (parity mode), "fp32_mfma" ("fp32" in storage,
+state and every kernel but the 3x3 convolutions, which run on the fp32-input matrix-core kernels) or
+"fp32_mfma_gemm" ("fp32_mfma" plus the pointwise convolutions and linears on the fp32 matrix-core GEMM).
 
 There is no CPU path here: inputs must live on the MI355X ("cuda" in PyTorch-ROCm naming).
 """
@@ -29,9 +30,9 @@ def _resolve_dtype(compute_dtype):
     if isinstance(name, torch.dtype):
         return name
     table = {"fp16": torch.float16, "float16": torch.float16, "half": torch.float16,
-             "fp32": torch.float32, "float32": torch.float32, "fp32_mfma": torch.float32}
+             "fp32": torch.float32, "float32": torch.float32, "fp32_mfma": torch.float32, "fp32_mfma_gemm": torch.float32}
     if name not in table:
-        raise ValueError(f"compute_dtype must be fp16, fp32 or fp32_mfma, got {name!r}")
+        raise ValueError(f"compute_dtype must be fp16, fp32, fp32_mfma or fp32_mfma_gemm, got {name!r}")
     return table[name]
 
 
@@ -39,6 +40,19 @@ def _resolve_conv3x3_flags(compute_dtype):
     """Kernel flags the tape adds to its 3x3 convolutions: "fp32_mfma" opts into libunetmi's fp32 matrix-core kernels."""
     name = compute_dtype or os.environ.get("UMI_COMPUTE_DTYPE", "fp16")
     return G.L.CONV_F32_MFMA if name == "fp32_mfma" else 0
+
+
+def _resolve_conv_flags(compute_dtype):
+    """(3x3 flag, pointwise flag) the tape adds to its convolution calls: "fp32_mfma" opts the 3x3 convolutions into libunetmi's
+    fp32 matrix-core kernels, "fp32_mfma_gemm" the pointwise convolutions and linears as well."""
+    name = compute_dtype or os.environ.get("UMI_COMPUTE_DTYPE", "fp16")
+    if name == "fp32_mfma_gemm":
+        return G.L.CONV_F32_MFMA, G.L.CONV_F32_MFMA_1X1
+    return _resolve_conv3x3_flags(name), 0
+
+
+def _set_tape_flags(tape, compute_dtype):
+    tape.conv3x3_flags, tape.conv1x1_flags = _resolve_conv_flags(compute_dtype)
 
 
 class _TapeFunction(torch.autograd.Function):
@@ -102,7 +116,7 @@ def _run_tape(module, inputs, build, tape_cls=None, dtype=None):
                         loss_scale=G.default_loss_scale(dtype, N * H * W),
                         grad_sink=getattr(module, "_umi_grad_sink", None) if record else None,
                         pack_cache=G.pack_cache_of(module), seed=seed, seed_dev=seed_dev)
-        tape.conv3x3_flags = _resolve_conv3x3_flags(getattr(module, "_compute_dtype", None))
+        _set_tape_flags(tape, getattr(module, "_compute_dtype", None))
         acts = [tape.input_nchw(x, needs_grad=need) for x, need in zip(inputs, in_needs)]
         out_act = build(tape, *acts)
         tape.finish_forward()

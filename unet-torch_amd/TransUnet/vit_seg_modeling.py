@@ -7,7 +7,8 @@ embedding + position embedding, 12 pre-LN transformer blocks (softmax attention,
 (bilinear x2 align_corners, cat([x, skip]), conv+BN+ReLU x2) and the 3x3 segmentation head -- onto a libunetmi tape
 (umi/graph_tu.py) with a hand-written backward; nothing runs through torch.nn.
 
-Keyword-only extra: `compute_dtype` ("fp16" default / "fp32" parity mode, env UMI_COMPUTE_DTYPE).
+Keyword-only extra: `compute_dtype` ("fp16" default / "fp32" parity mode / "fp32_mfma_gemm": "fp32" with the linears, the 1x1 and
+the 3x3 / stride-1 convolutions on the fp32 matrix-core kernels; env UMI_COMPUTE_DTYPE).
 `VisionTransformerMultitask` / `VisionTransformerMultitaskEM` (reference :444-638): the same encoder with 2 / 6 CUP decoders
 and heads on one tape.
 Not supported: `vis=True` (attention maps are never materialised), the non-hybrid (pure ViT patch conv) variant.
@@ -21,7 +22,7 @@ import torch.nn as nn
 from torch.nn import Conv2d, Dropout, LayerNorm, Linear
 from torch.nn.modules.utils import _pair
 
-from Model import _TapeFunction, _resolve_dtype, _run_tape
+from Model import _TapeFunction, _resolve_conv_flags, _resolve_dtype, _run_tape, _set_tape_flags
 from umi import graph as G
 from umi.graph_tu import TUTape
 
@@ -353,6 +354,8 @@ class VisionTransformer(nn.Module):
                           loss_scale=G.default_loss_scale(dtype, N * H * W),
                           grad_sink=getattr(self, "_umi_grad_sink", None) if record else None,
                           pack_cache=G.pack_cache_of(self))
+            if _resolve_conv_flags(self._compute_dtype)[1]:      # "fp32_mfma_gemm" ("fp32_mfma" sets no flag on this tape)
+                _set_tape_flags(tape, self._compute_dtype)
             a = tape.input_nchw(x, needs_grad=False)
             emb = self.transformer.embeddings
             h, skips = _build_embeddings(tape, a, emb)

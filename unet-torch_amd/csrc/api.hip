@@ -70,9 +70,10 @@ extern "C" int umi_conv_fwd_plan(int N, int H, int W, int Ci, int Co, int R, int
     const ConvFwdPath path = umi_conv_fwd_path(fwd_problem(N, H, W, Ci, Co, R, S, stride, pad, Ho, Wo, ldx, ldy, in_dtype, out_dtype,
                                                            flags, false, has_bias != 0, true));
     if ((flags & UMI_CONV_ACCUMULATE) && path != FWD_MFMA1X1) return UMI_ERR_UNSUPPORTED;
-    if (layout) *layout = (path == FWD_MFMA3X3 || path == FWD_MFMA1X1) ? 1 : 0;      // (the fp32 matrix-core kernel reads layout 0)
+    if (layout) *layout = (path == FWD_MFMA3X3 || path == FWD_MFMA1X1) ? 1 : 0;      // (the fp32 matrix-core kernels read layout 0)
     if (stat_rows)
         *stat_rows = path == FWD_MFMA3X3_F32 ? umi_conv3x3_f32_mfma_stat_rows(N, H, W)
+                     : path == FWD_GEMM_F32 ? umi_gemm_f32_mfma_stat_rows((long)N * H * W)
                      : path == FWD_MFMA3X3 ? umi_conv3x3_mfma_stat_rows(N, H, W, Co)
                      : path == FWD_STEM  ? umi_stem_stat_rows(N, H, W)
                      : path == FWD_HEAD  ? umi_head_stat_rows((long)N * H * W, Ci)
@@ -189,7 +190,7 @@ extern "C" int umi_conv_fwd(const void* x, int ldx, const void* tx, const void* 
     ConvFwdProblem p = fwd_problem(N, H, W, Ci, Co, R, S, stride, pad, Ho, Wo, ldx, ldy, in_dtype, out_dtype, flags,
                                    tx != nullptr, bias != nullptr, stat_part != nullptr);
     const ConvFwdPath path = umi_conv_fwd_path(p);
-    if (path != FWD_MFMA3X3_F32) p.flags = flags &= ~UMI_CONV_F32_MFMA;      // refused there: the call runs without the flag
+    if (path != FWD_MFMA3X3_F32 && path != FWD_GEMM_F32) p.flags = flags &= ~UMI_CONV_F32_OPT_IN;      // refused there: the call runs without the flags
     // only the pointwise / tap-gather MFMA kernel adds into y
     if ((flags & UMI_CONV_ACCUMULATE) && (stat_part || path != FWD_MFMA1X1)) return UMI_ERR_UNSUPPORTED;
     if (flags & UMI_CONV_DGRAD_STRIDED) {
@@ -206,6 +207,7 @@ extern "C" int umi_conv_fwd(const void* x, int ldx, const void* tx, const void* 
     const hipStream_t s = (hipStream_t)stream;
     switch (path) {
     case FWD_MFMA3X3_F32: return umi_conv3x3_f32_mfma(p, x, tx, wp, y, stat_part, s);
+    case FWD_GEMM_F32: return umi_gemm_f32_mfma(p, x, tx, wp, bias, y, stat_part, s);
     case FWD_MFMA3X3:
         // the caller packed the weights for this path (umi_conv_fwd_plan said layout 1): misalignment is an error,
         // not a reason to silently reinterpret them
@@ -234,9 +236,9 @@ static WgradProblem wgrad_problem(int N, int H, int W, int Ci, int Co, int R, in
 extern "C" size_t umi_conv_wgrad_ws_bytes(int N, int Ho, int Wo, int Ci, int Co, int R, int S, int dtype, int flags) {
     // the call picks its path from more arguments than this query has: size for whichever path could need most
     WgradProblem p = wgrad_problem(N, 0, 0, Ci, Co, R, S, 0, 0, Ho, Wo, 0, 0, dtype, flags, false, false);
-    const size_t f32_mfma = umi_wgrad3x3_f32_mfma_ws_bound(p);
-    p.flags &= ~UMI_CONV_F32_MFMA;                       // the call may still find the flag refused (strides, a transform on dy)
-    const size_t bounds[] = {f32_mfma, umi_wgrad3x3_mfma_ws_bound(p), umi_wgrad1x1_mfma_ws_bound(p), umi_wgradT_mfma_ws_bound(p),
+    const size_t f32_mfma = umi_wgrad3x3_f32_mfma_ws_bound(p), f32_gemm = umi_wgrad_gemm_f32_mfma_ws_bound(p);
+    p.flags &= ~UMI_CONV_F32_OPT_IN;                     // the call may still find the flags refused (strides, a transform on dy)
+    const size_t bounds[] = {f32_mfma, f32_gemm, umi_wgrad3x3_mfma_ws_bound(p), umi_wgrad1x1_mfma_ws_bound(p), umi_wgradT_mfma_ws_bound(p),
                              umi_wgrad_gather_mfma_ws_bound(p), umi_stem_wgrad_ws_bound(p), umi_head_wgrad_ws_bound(p),
                              umi_root_wgrad_ws_bound(p), umi_head3_wgrad_ws_bound(p), umi_conv_wgrad_generic_ws_bound(p)};
     size_t most = 0;
@@ -248,11 +250,12 @@ extern "C" size_t umi_conv_wgrad_ws_bytes(int N, int Ho, int Wo, int Ci, int Co,
 static int conv_wgrad(const WgradProblem& asked, WgradPath path, const void* x, const void* txa, const void* dy, const void* txb,
                       const WgradOut& o, hipStream_t s) {
     WgradProblem p = asked;
-    if (path != WGRAD_MFMA3X3_F32) p.flags &= ~UMI_CONV_F32_MFMA;      // refused there: the call runs without the flag
+    if (path != WGRAD_MFMA3X3_F32 && path != WGRAD_GEMM_F32) p.flags &= ~UMI_CONV_F32_OPT_IN;      // refused there: the call runs without the flags
     if (!x || !dy || !o.dW || !o.ws || p.N <= 0 || p.H <= 0 || p.W <= 0 || p.Ci <= 0 || p.Co <= 0 || p.ldx < p.Ci || p.lddy < p.Co)
         return UMI_ERR_BADARG;
     switch (path) {
     case WGRAD_MFMA3X3_F32: return umi_wgrad3x3_f32_mfma(p, x, txa, dy, o, s);
+    case WGRAD_GEMM_F32: return umi_wgrad_gemm_f32_mfma(p, x, txa, dy, o, s);
     case WGRAD_MFMA3X3: return umi_wgrad3x3_mfma(p, x, txa, dy, o, s);
     case WGRAD_MFMA1X1: return umi_wgrad1x1_mfma(p, x, txa, dy, o, s);
     case WGRAD_T: return umi_wgradT_mfma(p, x, dy, txb, o, s);

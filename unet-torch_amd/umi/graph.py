@@ -89,6 +89,7 @@ class Tape:
         self._late_ready = []             # parameters whose bucket slot (gradient sink) is a deferred fill: mark_ready after it
         self._inputs = []
         self.conv3x3_flags = 0            # compute_dtype "fp32_mfma": lib.CONV_F32_MFMA, OR-ed into the 3x3 convolutions' calls
+        self.conv1x1_flags = 0            # "fp32_mfma_gemm": lib.CONV_F32_MFMA_1X1, OR-ed into the pointwise convolutions' calls
 
     # ---- helpers -----------------------------------------------------------------------
     def alloc(self, N, H, W, C, dtype=None, zero=False, device=None):
@@ -102,10 +103,15 @@ class Tape:
             return c.get(kind, weight, self.dtype, k8)
         return ops.PACKERS[kind](wf, self.dtype, k8=k8)
 
-    def _f3(self, R, S, stride, pad, cin):
-        """Flags for one call of a 3x3 / stride 1 / pad 1 convolution that reads `cin` channels: the tape's opt-in kernel flag where
-        the channel count allows it at all (the library ignores it for any other reason it cannot take the problem)."""
-        return self.conv3x3_flags if (R, S, stride, pad) == (3, 3, 1, 1) and cin % 8 == 0 else 0
+    def _fk(self, R, S, stride, pad, cin, cout):
+        """The tape's opt-in kernel flag that fits one convolution call's geometry: the 3x3 one for 3x3 / stride 1 / pad 1 calls that
+        read a multiple of 8 channels, the pointwise one for 1x1 / stride 1 / pad 0 calls between multiples of 8 channels, where the
+        channel counts allow it at all (the library ignores a flag for any other reason it cannot take the problem)."""
+        if (R, S, stride, pad) == (3, 3, 1, 1):
+            return self.conv3x3_flags if cin % 8 == 0 else 0
+        if (R, S, stride, pad) == (1, 1, 1, 0):
+            return self.conv1x1_flags if cin % 8 == 0 and cout % 8 == 0 else 0
+        return 0
 
     def _defer_list(self, weight, gw):
         """The list a weight gradient's split-K reduction is deferred to (and `gw` marked as filled at the flush), or None."""
@@ -245,8 +251,9 @@ class Tape:
         # the pointwise matrix-core kernel has no statistics epilogue: a 1x1 conv that feeds a BatchNorm (attention gates) runs
         # it without statistics and takes them in a separate HBM-bound pass over its (small: C_hidden channels) output; where
         # neither applies (odd channel counts) the generic kernel produces both
-        part, flags, two_pass = None, self._f3(R, S, stride, pad, Ci), False
-        if self.training and (R, S) == (1, 1):
+        part, flags, two_pass = None, self._fk(R, S, stride, pad, Ci, Co), False
+        # (the fp32 matrix-core pointwise kernel writes the statistics itself: nothing below applies to it)
+        if self.training and (R, S) == (1, 1) and not (flags and self.dtype == torch.float32):
             two_pass = (self.dtype == torch.float16 and Co % 8 == 0 and
                         ops.conv_plan(a.raw, out, R, S, stride, pad, 0, False)[0] == 1)
             # Co <= 8 (the gate's 1-channel psi conv): the narrow-output kernel, which has the statistics epilogue itself
@@ -318,7 +325,7 @@ class Tape:
                         ops.bn_bwd_apply(o.grad, out, tx, rstd, dbeta, dgamma)
                 if not fuse and not stem_fuse:
                     ops.conv_wgrad(a.raw, a.tx, o.grad, None, gw, Ci * R * S, R * S, 1, inv, R, S, stride, pad,
-                                   flags=self._f3(R, S, stride, pad, Ci), defer=self._defer_list(weight, gw))
+                                   flags=self._fk(R, S, stride, pad, Ci, Co), defer=self._defer_list(weight, gw))
                 self._set_pgrad(weight, gw)
                 if bias is not None:
                     gb = self._new_pgrad(bias)
@@ -350,7 +357,7 @@ class Tape:
                         a.bn_part, a.bn_part_at = part, a.gives + 1      # valid after the _give below and until the next one
                     else:
                         ops.conv_fwd(o.grad, None, lambda lay: self._pack("conv_dgrad", weight, wf, bool(lay)), None, dx,
-                                     R, S, 1, R - 1 - pad, flags=self._f3(R, S, stride, R - 1 - pad, Co))
+                                     R, S, 1, R - 1 - pad, flags=self._fk(R, S, stride, R - 1 - pad, Co, Ci))
                     self._give(a, dx)
             self.steps.append(bwd)
         return o
@@ -364,7 +371,7 @@ class Tape:
                          device=a.raw.device)
         wf0 = weight.detach().float()
         ops.conv_fwd(a.raw, a.tx, lambda lay: self._pack("conv_fwd", weight, wf0, bool(lay)),
-                     bias.detach().float() if bias is not None else None, out, R, S, 1, pad)
+                     bias.detach().float() if bias is not None else None, out, R, S, 1, pad, flags=self._fk(R, S, 1, pad, Ci, Co))
         o = Act(out, None)
         if self.record:
             def bwd():
@@ -388,7 +395,7 @@ class Tape:
                     fused_w = part is not None and want_w
                 if not fused_w:
                     ops.conv_wgrad(a.raw, a.tx, g, None, gw, Ci * R * S, R * S, 1, inv, R, S, 1, pad,
-                                   defer=self._defer_list(weight, gw))
+                                   flags=self._fk(R, S, 1, pad, Ci, Co), defer=self._defer_list(weight, gw))
                 self._set_pgrad(weight, gw)
                 if bias is not None:
                     gb = self._new_pgrad(bias)
@@ -402,7 +409,7 @@ class Tape:
                     else:
                         wf = weight.detach().float()
                         ops.conv_fwd(g, None, lambda lay: self._pack("conv_dgrad", weight, wf, bool(lay)), None, dx,
-                                     R, S, 1, R - 1 - pad)
+                                     R, S, 1, R - 1 - pad, flags=self._fk(R, S, 1, R - 1 - pad, Co, Ci))
                     self._give(a, dx)
             self.steps.append(bwd)
         return o

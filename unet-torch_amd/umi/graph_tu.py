@@ -84,7 +84,8 @@ class TUTape(Tape):
             xs, dys, gws = zip(*items)
             if len(items) < 2 or not ops.conv_wgrad_group(xs, dys, gws, s_co, s_ci, self.inv):
                 for x, dy, gw in items:
-                    ops.conv_wgrad(x, None, dy, None, gw, s_co, s_ci, 1, self.inv, 1, 1, 1, 0)
+                    ops.conv_wgrad(x, None, dy, None, gw, s_co, s_ci, 1, self.inv, 1, 1, 1, 0,
+                                   flags=self._fk(1, 1, 1, 0, x.shape[3], dy.shape[3]))
         self._wgrad_groups, self._readonly, self._colsum_groups = {}, set(), {}
 
     # ---- convolution with weight standardisation (no bias), output stored raw == activated -----------------------
@@ -111,7 +112,9 @@ class TUTape(Tape):
 
             def packed(kind):
                 return lambda lay: ops.PACKERS[kind](ws, self.dtype, k8=bool(lay))
-        ops.conv_fwd(a.raw, a.tx, packed("conv_fwd"), None, out, R, S, stride, pad)
+        # (only the mode that opts the pointwise kernels in puts its flags on the standardised convolutions, 3x3 ones included)
+        fk = self._fk if self.conv1x1_flags else (lambda *_: 0)
+        ops.conv_fwd(a.raw, a.tx, packed("conv_fwd"), None, out, R, S, stride, pad, flags=fk(R, S, stride, pad, Ci, Co))
         o = Act(out, None)
         if self.record:
             def bwd():
@@ -120,6 +123,7 @@ class TUTape(Tape):
                 slot = self._wstd_slot(ent, w) if ent is not None else None
                 gws = slot[0] if slot is not None else torch.empty_like(ws)
                 ops.conv_wgrad(a.raw, a.tx, o.grad, None, gws, Ci * R * S, R * S, 1, self.inv, R, S, stride, pad,
+                               flags=fk(R, S, stride, pad, Ci, Co),
                                defer=self._wgrad_deferred if slot is not None else None)
                 if slot is not None:
                     self._mark_deferred_fill(slot[1])
@@ -128,7 +132,8 @@ class TUTape(Tape):
                 if _wants_grad(a):
                     dx = self.alloc(N, H, W, Ci, device=out.device)
                     if stride == 1:
-                        ops.conv_fwd(o.grad, None, packed("conv_dgrad"), None, dx, R, S, 1, R - 1 - pad)
+                        ops.conv_fwd(o.grad, None, packed("conv_dgrad"), None, dx, R, S, 1, R - 1 - pad,
+                                     flags=fk(R, S, 1, R - 1 - pad, Co, Ci))
                     else:
                         self._strided_dgrad(o.grad, packed("conv_dgrad_strided"), dx, R, S, stride, pad)
                     self._give(a, dx)
@@ -281,7 +286,8 @@ class TUTape(Tape):
         if _fused is None or not _fused(out, lambda lay: self._pack("conv_fwd", weight, w4, bool(lay)), b32):
             if _fused is not None:
                 return None                             # the caller runs the unfused sequence
-            ops.conv_fwd(a.raw, a.tx, lambda lay: self._pack("conv_fwd", weight, w4, bool(lay)), b32, out, 1, 1, 1, 0)
+            ops.conv_fwd(a.raw, a.tx, lambda lay: self._pack("conv_fwd", weight, w4, bool(lay)), b32, out, 1, 1, 1, 0,
+                         flags=self._fk(1, 1, 1, 0, Ci, Co))
         o = Act(out, None)
         if self.record:
             def bwd():
@@ -289,7 +295,7 @@ class TUTape(Tape):
                     return
                 gw = self._new_pgrad(weight)
                 if not self._defer_wgrad(weight, a.raw, a.tx, o.grad, gw, Ci, 1):
-                    ops.conv_wgrad(a.raw, a.tx, o.grad, None, gw, Ci, 1, 1, self.inv, 1, 1, 1, 0)
+                    ops.conv_wgrad(a.raw, a.tx, o.grad, None, gw, Ci, 1, 1, self.inv, 1, 1, 1, 0, flags=self._fk(1, 1, 1, 0, Ci, Co))
                 self._set_pgrad(weight, gw)
                 if bias is not None:
                     gb = self._new_pgrad(bias)
@@ -298,7 +304,8 @@ class TUTape(Tape):
                     self._set_pgrad(bias, gb)
                 if _wants_grad(a):
                     dx = self.alloc(N, H, W, Ci, device=out.device)
-                    ops.conv_fwd(o.grad, None, lambda lay: self._pack("conv_dgrad", weight, w4, bool(lay)), None, dx, 1, 1, 1, 0)
+                    ops.conv_fwd(o.grad, None, lambda lay: self._pack("conv_dgrad", weight, w4, bool(lay)), None, dx, 1, 1, 1, 0,
+                                 flags=self._fk(1, 1, 1, 0, Co, Ci))
                     self._give(a, dx)
             self.steps.append(bwd)
         return o
@@ -505,7 +512,7 @@ class TUTape(Tape):
             def packed(kind):
                 return lambda lay: ops.PACKERS[kind](wcat, self.dtype, k8=bool(lay))
         qkv = self.alloc(N, H, W, 3 * C, device=a.raw.device)
-        ops.conv_fwd(a.raw, a.tx, packed("conv_fwd"), bcat, qkv, 1, 1, 1, 0)
+        ops.conv_fwd(a.raw, a.tx, packed("conv_fwd"), bcat, qkv, 1, 1, 1, 0, flags=self._fk(1, 1, 1, 0, C, 3 * C))
         q, k, v = (qkv[..., i * C:(i + 1) * C] for i in range(3))
         out = self.alloc(N, H, W, C, device=a.raw.device)
         lse = ops_tu.attn_fwd(q, k, v, out, heads)
@@ -523,7 +530,7 @@ class TUTape(Tape):
                         d_i = dqkv[..., i * C:(i + 1) * C]
                         gw = self._new_pgrad(m.weight)
                         if not self._defer_wgrad(m.weight, a.raw, a.tx, d_i, gw, C, 1):
-                            ops.conv_wgrad(a.raw, a.tx, d_i, None, gw, C, 1, 1, self.inv, 1, 1, 1, 0)
+                            ops.conv_wgrad(a.raw, a.tx, d_i, None, gw, C, 1, 1, self.inv, 1, 1, 1, 0, flags=self._fk(1, 1, 1, 0, C, C))
                         self._set_pgrad(m.weight, gw)
                         gb = self._new_pgrad(m.bias)
                         if not self._defer_colsum(d_i, gb):
@@ -532,7 +539,8 @@ class TUTape(Tape):
                 else:
                     gw = torch.empty(3 * C, C, dtype=torch.float32, device=out.device)
                     if not self._defer_wgrad(query.weight, a.raw, a.tx, dqkv, gw, C, 1):
-                        ops.conv_wgrad(a.raw, a.tx, dqkv, None, gw, C, 1, 1, self.inv, 1, 1, 1, 0)
+                        ops.conv_wgrad(a.raw, a.tx, dqkv, None, gw, C, 1, 1, self.inv, 1, 1, 1, 0,
+                                       flags=self._fk(1, 1, 1, 0, C, 3 * C))
                     gb = torch.empty(3 * C, dtype=torch.float32, device=out.device)
                     if not self._defer_colsum(dqkv, gb):
                         ops.colsum(dqkv, gb, self.inv)
@@ -541,7 +549,7 @@ class TUTape(Tape):
                         self._set_pgrad(m.bias, gb[i * C:(i + 1) * C])
                 if _wants_grad(a):
                     dx = self.alloc(N, H, W, C, device=out.device)
-                    ops.conv_fwd(dqkv, None, packed("conv_dgrad"), None, dx, 1, 1, 1, 0)
+                    ops.conv_fwd(dqkv, None, packed("conv_dgrad"), None, dx, 1, 1, 1, 0, flags=self._fk(1, 1, 1, 0, 3 * C, C))
                     self._give(a, dx)
             self.steps.append(bwd)
         return o
