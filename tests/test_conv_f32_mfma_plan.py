@@ -32,8 +32,8 @@ def test_compute_dtype_names():
         Model._resolve_dtype("fp33")
     from umi import lib
     assert lib.CONV_F32_MFMA == F32_MFMA
-    assert Model._resolve_conv3x3_flags("fp32_mfma") == F32_MFMA
-    assert Model._resolve_conv3x3_flags("fp32") == 0 and Model._resolve_conv3x3_flags("fp16") == 0
+    assert Model._resolve_conv_flags("fp32_mfma")[0] == F32_MFMA
+    assert Model._resolve_conv_flags("fp32")[0] == 0 and Model._resolve_conv_flags("fp16")[0] == 0
 
 
 def test_plan_names_the_new_path_on_eligible_problems():

@@ -36,23 +36,12 @@ def _resolve_dtype(compute_dtype):
     return table[name]
 
 
-def _resolve_conv3x3_flags(compute_dtype):
-    """Kernel flags the tape adds to its 3x3 convolutions: "fp32_mfma" opts into libunetmi's fp32 matrix-core kernels."""
-    name = compute_dtype or os.environ.get("UMI_COMPUTE_DTYPE", "fp16")
-    return G.L.CONV_F32_MFMA if name == "fp32_mfma" else 0
-
-
 def _resolve_conv_flags(compute_dtype):
     """(3x3 flag, pointwise flag) the tape adds to its convolution calls: "fp32_mfma" opts the 3x3 convolutions into libunetmi's
     fp32 matrix-core kernels, "fp32_mfma_gemm" the pointwise convolutions and linears as well."""
     name = compute_dtype or os.environ.get("UMI_COMPUTE_DTYPE", "fp16")
-    if name == "fp32_mfma_gemm":
-        return G.L.CONV_F32_MFMA, G.L.CONV_F32_MFMA_1X1
-    return _resolve_conv3x3_flags(name), 0
-
-
-def _set_tape_flags(tape, compute_dtype):
-    tape.conv3x3_flags, tape.conv1x1_flags = _resolve_conv_flags(compute_dtype)
+    mfma = name in ("fp32_mfma", "fp32_mfma_gemm")
+    return G.L.CONV_F32_MFMA if mfma else 0, G.L.CONV_F32_MFMA_1X1 if name == "fp32_mfma_gemm" else 0
 
 
 class _TapeFunction(torch.autograd.Function):
@@ -116,7 +105,7 @@ def _run_tape(module, inputs, build, tape_cls=None, dtype=None):
                         loss_scale=G.default_loss_scale(dtype, N * H * W),
                         grad_sink=getattr(module, "_umi_grad_sink", None) if record else None,
                         pack_cache=G.pack_cache_of(module), seed=seed, seed_dev=seed_dev)
-        _set_tape_flags(tape, getattr(module, "_compute_dtype", None))
+        tape.conv3x3_flags, tape.conv1x1_flags = _resolve_conv_flags(getattr(module, "_compute_dtype", None))
         acts = [tape.input_nchw(x, needs_grad=need) for x, need in zip(inputs, in_needs)]
         out_act = build(tape, *acts)
         tape.finish_forward()

@@ -22,7 +22,7 @@ import torch.nn as nn
 from torch.nn import Conv2d, Dropout, LayerNorm, Linear
 from torch.nn.modules.utils import _pair
 
-from Model import _TapeFunction, _resolve_conv_flags, _resolve_dtype, _run_tape, _set_tape_flags
+from Model import _TapeFunction, _resolve_conv_flags, _resolve_dtype, _run_tape
 from umi import graph as G
 from umi.graph_tu import TUTape
 
@@ -354,8 +354,8 @@ class VisionTransformer(nn.Module):
                           loss_scale=G.default_loss_scale(dtype, N * H * W),
                           grad_sink=getattr(self, "_umi_grad_sink", None) if record else None,
                           pack_cache=G.pack_cache_of(self))
-            if _resolve_conv_flags(self._compute_dtype)[1]:      # "fp32_mfma_gemm" ("fp32_mfma" sets no flag on this tape)
-                _set_tape_flags(tape, self._compute_dtype)
+            flags = _resolve_conv_flags(self._compute_dtype)
+            tape.conv3x3_flags, tape.conv1x1_flags = flags if flags[1] else (0, 0)       # "fp32_mfma" sets no flag on this tape
             a = tape.input_nchw(x, needs_grad=False)
             emb = self.transformer.embeddings
             h, skips = _build_embeddings(tape, a, emb)

@@ -13,12 +13,14 @@ parameter gradients are produced in fp32, unscaled, in the parameter's own layou
 Reference semantics implemented here: Model.py:7-26 (DoubleConv), :29-47 (Down),
 :50-83 (Up), :86-92 (OutConv); BatchNorm2d train/eval behaviour as torch.nn.
 """
+import math
 import os
 
 import torch
 
 from . import lib as L
 from . import ops
+from .deferred import Deferred
 
 
 def _fuse_bnred():
@@ -78,15 +80,15 @@ class Tape:
         self.steps = []
         self.param_grads = {}             # id(param) -> (param, grad tensor)
         self._deferred_unscale = []       # BatchNorm parameter gradients still carrying the loss scale
-        self._deferred_zero = []          # gradients that are identically zero (conv bias under a BatchNorm): one fill at the end
         self._nbt = []
-        self._wgrad_deferred = None
-        # Deferred fills: a gradient buffer registered in param_grads whose CONTENT is only written (with `=`) by a grouped
-        # launch at the end of the backward pass.  A later contribution to the same parameter (a module used twice in one
-        # tape) must not be add_()-ed onto the still unfilled buffer: it is parked and added after the flush.
-        self._pending_fill = []           # [lo, hi) address ranges of such buffers (gradients may be views into them)
-        self._late_adds = []              # (destination, addend) pairs applied after every deferred fill has run
-        self._late_ready = []             # parameters whose bucket slot (gradient sink) is a deferred fill: mark_ready after it
+        # Deferred fills (umi/deferred.py): gradients only written by a grouped launch at the end of the backward pass.  Under a
+        # gradient sink the U-Net tape defers nothing: every gradient goes to its bucket slot as the pass proceeds and the
+        # bucket's all-reduce overlaps the rest of the pass (TUTape flushes at marked points instead).
+        d = self.deferred = Deferred(self)
+        d.register("wgrad_reduce", lambda _, items, tape: ops.wgrad_reduce_flush(items),     # split-K reductions, 16 per launch
+                   on=lambda tape: (tape.grad_sink is None or tape.deferred.marks) and _defer_wgrad_reduce())
+        d.register("zero", lambda _, items, tape: torch._foreach_zero_(items),               # conv bias under a BatchNorm
+                   on=lambda tape: tape.grad_sink is None)
         self._inputs = []
         self.conv3x3_flags = 0            # compute_dtype "fp32_mfma": lib.CONV_F32_MFMA, OR-ed into the 3x3 convolutions' calls
         self.conv1x1_flags = 0            # "fp32_mfma_gemm": lib.CONV_F32_MFMA_1X1, OR-ed into the pointwise convolutions' calls
@@ -113,20 +115,9 @@ class Tape:
             return self.conv1x1_flags if cin % 8 == 0 and cout % 8 == 0 else 0
         return 0
 
-    def _defer_list(self, weight, gw):
-        """The list a weight gradient's split-K reduction is deferred to (and `gw` marked as filled at the flush), or None."""
-        if self._wgrad_deferred is None:
-            return None
-        self._mark_deferred_fill(gw)
-        return self._wgrad_deferred
-
-    def _mark_deferred_fill(self, *bufs):
-        for b in bufs:
-            self._pending_fill.append((b.data_ptr(), b.data_ptr() + b.numel() * b.element_size()))
-
-    def _is_pending_fill(self, t):
-        a = t.data_ptr()
-        return any(lo <= a < hi for lo, hi in self._pending_fill)
+    def _packer(self, kind, weight, wf):
+        """`weights` argument of ops.conv_fwd: packs for the layout the kernel plan asks for."""
+        return lambda lay: self._pack(kind, weight, wf, bool(lay))
 
     def _new_pgrad(self, p):
         """fp32 tensor the wgrad kernel writes into: a slot of the reducer's flat bucket when present."""
@@ -140,15 +131,15 @@ class Tape:
             if self.grad_sink is not None and self.grad_sink.buffer_for(p) is not None:
                 # its bucket may already be on the wire (mark_ready at the first use)
                 raise NotImplementedError("a parameter used twice in one tape under a gradient sink (umi.ddp.GradReducer)")
-            if self._is_pending_fill(dst) or self._is_pending_fill(g):
-                self._late_adds.append((dst, g))
+            if self.deferred.pending(dst) or self.deferred.pending(g):
+                self.deferred.park_add(dst, g)              # added after the flush, not onto a still unfilled buffer
             else:
                 dst.add_(g)
             return
         v = self.grad_sink.buffer_for(p) if self.grad_sink is not None else None
         late = False
         if v is not None:
-            late = self._is_pending_fill(g)
+            late = self.deferred.pending(g)
             if v.data_ptr() != g.data_ptr():
                 if late:
                     raise RuntimeError("deferred gradient fills must target the sink's bucket slot (Tape._new_pgrad)")
@@ -157,7 +148,7 @@ class Tape:
         self.param_grads[key] = (p, g)
         if v is not None:
             if late:
-                self._late_ready.append(p)          # the slot is written by a grouped launch: ready once that has been issued
+                self.deferred.park_ready(p)         # the slot is written by a grouped launch: ready once that has been issued
             else:
                 self.grad_sink.mark_ready(p)
 
@@ -259,7 +250,7 @@ class Tape:
             # Co <= 8 (the gate's 1-channel psi conv): the narrow-output kernel, which has the statistics epilogue itself
             narrow = self.dtype == torch.float16 and Co <= 8
             flags = 0 if (two_pass or narrow) else L.CONV_FORCE_GENERIC
-        res = ops.conv_fwd(a.raw, a.tx, lambda lay: self._pack("conv_fwd", weight, wf, bool(lay)), None, out,
+        res = ops.conv_fwd(a.raw, a.tx, self._packer("conv_fwd", weight, wf), None, out,
                            R, S, stride, pad, want_stats=self.training and not two_pass, flags=flags)
         part = ops.bn_stats(out) if two_pass else res
         if self.training and part is None:
@@ -325,17 +316,14 @@ class Tape:
                         ops.bn_bwd_apply(o.grad, out, tx, rstd, dbeta, dgamma)
                 if not fuse and not stem_fuse:
                     ops.conv_wgrad(a.raw, a.tx, o.grad, None, gw, Ci * R * S, R * S, 1, inv, R, S, stride, pad,
-                                   flags=self._fk(R, S, stride, pad, Ci, Co), defer=self._defer_list(weight, gw))
+                                   flags=self._fk(R, S, stride, pad, Ci, Co), defer=self.deferred.open("wgrad_reduce", fills=(gw,)))
                 self._set_pgrad(weight, gw)
                 if bias is not None:
                     gb = self._new_pgrad(bias)
                     # d/d bias of BatchNorm(conv + bias) vanishes identically: zero-filled with the other such gradients by ONE
                     # multi-tensor launch at the end of the backward pass (18 fills per U-Net step otherwise); with a gradient
                     # sink the slot must be final before it is handed over
-                    if self.grad_sink is None:
-                        self._deferred_zero.append(gb)
-                        self._mark_deferred_fill(gb)     # a second use of the bias in this tape parks its addition behind the fill
-                    else:
+                    if not self.deferred.defer("zero", None, gb, fills=(gb,)):
                         gb.zero_()
                     self._set_pgrad(bias, gb)
                 if _wants_grad(a):
@@ -343,7 +331,7 @@ class Tape:
                         raise NotImplementedError("dgrad for strided conv_bn")
                     tgt = self._accumulate_target(a, o.grad, R, S, 1, R - 1 - pad)
                     if tgt is not None:
-                        ops.conv_fwd(o.grad, None, lambda lay: self._pack("conv_dgrad", weight, wf, bool(lay)), None, tgt,
+                        ops.conv_fwd(o.grad, None, self._packer("conv_dgrad", weight, wf), None, tgt,
                                      R, S, 1, R - 1 - pad, flags=L.CONV_ACCUMULATE)
                         a.gives += 1
                         return
@@ -356,7 +344,7 @@ class Tape:
                     if part is not None:
                         a.bn_part, a.bn_part_at = part, a.gives + 1      # valid after the _give below and until the next one
                     else:
-                        ops.conv_fwd(o.grad, None, lambda lay: self._pack("conv_dgrad", weight, wf, bool(lay)), None, dx,
+                        ops.conv_fwd(o.grad, None, self._packer("conv_dgrad", weight, wf), None, dx,
                                      R, S, 1, R - 1 - pad, flags=self._fk(R, S, stride, R - 1 - pad, Co, Ci))
                     self._give(a, dx)
             self.steps.append(bwd)
@@ -370,7 +358,7 @@ class Tape:
         out = self.alloc(N, H + 2 * pad - R + 1, W + 2 * pad - S + 1, Co, dtype=out_dtype or self.dtype,
                          device=a.raw.device)
         wf0 = weight.detach().float()
-        ops.conv_fwd(a.raw, a.tx, lambda lay: self._pack("conv_fwd", weight, wf0, bool(lay)),
+        ops.conv_fwd(a.raw, a.tx, self._packer("conv_fwd", weight, wf0),
                      bias.detach().float() if bias is not None else None, out, R, S, 1, pad, flags=self._fk(R, S, 1, pad, Ci, Co))
         o = Act(out, None)
         if self.record:
@@ -395,7 +383,7 @@ class Tape:
                     fused_w = part is not None and want_w
                 if not fused_w:
                     ops.conv_wgrad(a.raw, a.tx, g, None, gw, Ci * R * S, R * S, 1, inv, R, S, 1, pad,
-                                   flags=self._fk(R, S, 1, pad, Ci, Co), defer=self._defer_list(weight, gw))
+                                   flags=self._fk(R, S, 1, pad, Ci, Co), defer=self.deferred.open("wgrad_reduce", fills=(gw,)))
                 self._set_pgrad(weight, gw)
                 if bias is not None:
                     gb = self._new_pgrad(bias)
@@ -408,7 +396,7 @@ class Tape:
                         a.bn_part, a.bn_part_at = part, a.gives + 1
                     else:
                         wf = weight.detach().float()
-                        ops.conv_fwd(g, None, lambda lay: self._pack("conv_dgrad", weight, wf, bool(lay)), None, dx,
+                        ops.conv_fwd(g, None, self._packer("conv_dgrad", weight, wf), None, dx,
                                      R, S, 1, R - 1 - pad, flags=self._fk(R, S, 1, R - 1 - pad, Co, Ci))
                     self._give(a, dx)
             self.steps.append(bwd)
@@ -461,7 +449,7 @@ class Tape:
         if dY or dX:
             dest.zero_()
         wf = weight.detach().float()
-        ops.conv_fwd(a.raw, a.tx, lambda lay: self._pack("convT_fwd", weight, wf, bool(lay)),
+        ops.conv_fwd(a.raw, a.tx, self._packer("convT_fwd", weight, wf),
                      bias.detach().float() if bias is not None else None, dest, 2, 2, 2, 0,
                      flags=L.CONV_UPSAMPLE2, up_offset=(oy, ox))
         o = Act(dest, None)
@@ -474,7 +462,7 @@ class Tape:
                 if dY or dX:
                     g = g[:, oy:oy + 2 * h, ox:ox + 2 * w, :].contiguous()
                 gw = self._new_pgrad(weight)
-                dlist = self._defer_list(weight, gw)
+                dlist = self.deferred.open("wgrad_reduce", fills=(gw,))
                 fused = False
                 if bias is not None:
                     gb = self._new_pgrad(bias)
@@ -493,8 +481,7 @@ class Tape:
                 if _wants_grad(a):
                     tgt = self._accumulate_target(a, g, 2, 2, 2, 0)
                     if tgt is not None:
-                        ops.conv_fwd(g, None, lambda lay: self._pack("convT_dgrad", weight, wf, bool(lay)), None, tgt,
-                                     2, 2, 2, 0, flags=L.CONV_ACCUMULATE)
+                        ops.conv_fwd(g, None, self._packer("convT_dgrad", weight, wf), None, tgt, 2, 2, 2, 0, flags=L.CONV_ACCUMULATE)
                         a.gives += 1
                         return
                     dx = self.alloc(N, h, w, Cin, device=dest.device)
@@ -508,8 +495,7 @@ class Tape:
                     if part is not None:
                         a.bn_part, a.bn_part_at = part, a.gives + 1
                     else:
-                        ops.conv_fwd(g, None, lambda lay: self._pack("convT_dgrad", weight, wf, bool(lay)), None, dx,
-                                     2, 2, 2, 0)
+                        ops.conv_fwd(g, None, self._packer("convT_dgrad", weight, wf), None, dx, 2, 2, 2, 0)
                     self._give(a, dx)
             self.steps.append(bwd)
         return o
@@ -617,42 +603,16 @@ class Tape:
         a.grad = torch.empty((N, H, W, C), dtype=self.dtype, device=g_nchw.device)
         a.grad.copy_(g)
 
-    # Deferred gradient fills under a gradient sink: the U-Net tape turns them off (every weight gradient goes to its bucket
-    # slot as the pass proceeds, the bucket's all-reduce overlaps the rest of the backward pass); TUTape keeps them and flushes
-    # at marked points (flush_mark), so whole groups of layers still cost one launch.
-    _defer_under_sink = False
-
-    def _flush_deferred(self):
-        """Run every deferred fill recorded so far, then the parked second contributions, then hand the filled bucket slots
-        to the gradient sink."""
-        if self._wgrad_deferred:
-            ops.wgrad_reduce_flush(self._wgrad_deferred)     # the split-K reductions of all layers, 16 per launch
-        if self._deferred_zero:
-            torch._foreach_zero_(self._deferred_zero)        # (a deferred fill like the others: before the parked additions)
-            self._deferred_zero = []
-        self._finish_param_grads()
-        for dst, src in self._late_adds:                    # second uses of a parameter whose first gradient was a deferred fill
-            dst.add_(src)
-        self._late_adds, self._pending_fill = [], []
-        for p in self._late_ready:
-            self.grad_sink.mark_ready(p)
-        self._late_ready = []
-
     def backward(self):
-        self._wgrad_deferred = [] if ((self.grad_sink is None or self._defer_under_sink) and _defer_wgrad_reduce()) else None
         for step in reversed(self.steps):
             step()
         self.steps = []
-        self._flush_deferred()
-        self._wgrad_deferred = None
+        self.deferred.flush()
         if self._deferred_unscale:
             torch._foreach_mul_(self._deferred_unscale, self.inv)
             self._deferred_unscale = []
         if self.grad_sink is not None:
             self.grad_sink.finish()
-
-    def _finish_param_grads(self):
-        """Hook: parameter-gradient work batched at the end of the backward pass (TUTape: StdConv2d standardisation)."""
 
     def input_grad_nchw(self, a: Act):
         if a.grad is None:
@@ -664,7 +624,6 @@ class Tape:
 
 
 def _eval_fold():
-    import os
     return os.environ.get("UMI_NO_EVAL_FOLD") != "1"
 
 
@@ -689,7 +648,6 @@ def dropout_seeds(module, device, training):
 def pack_cache_of(module):
     """The module's cache of kernel-layout weight copies (ops.PackCache); stale entries (optimizer step, load_state_dict)
     are re-packed here, in one launch, before the tape runs.  UMI_NO_PACK_CACHE=1 packs per use (A/B switch)."""
-    import os
     if os.environ.get("UMI_NO_PACK_CACHE") == "1":
         return None
     c = module.__dict__.get("_umi_pack_cache")
@@ -710,5 +668,4 @@ def default_loss_scale(dtype, n_pixels):
     fp16's normal range, so scale them to ~2^-4 (power of two: exact, undone in fp32)."""
     if dtype != torch.float16:
         return 1.0
-    import math
     return float(2 ** max(0, int(math.floor(math.log2(max(n_pixels, 1)))) - 3))

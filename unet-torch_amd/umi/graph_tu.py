@@ -7,6 +7,9 @@ decoder's conv+BatchNorm+ReLU layers keep the lazy consumer-side transform of th
 Reference semantics (TransUnet/): StdConv2d resnet_skip.py:18-25, PreActBottleneck :38-74, ResNetV2 :112-160,
 Embeddings vit_seg_modeling.py:122-165, Attention :50-94, Mlp :97-119, Block :168-187, DecoderBlock :284-315.
 """
+import ctypes
+import os
+
 import torch
 
 from . import lib as L
@@ -15,30 +18,52 @@ from .graph import Act, Tape, _wants_grad
 
 
 def _no_linear_fusion():
-    import os
     return os.environ.get("UMI_NO_LINEAR_FUSION") == "1"          # A/B knob, read per call
 
 
 def _no_wgrad_group():
-    import os
     return os.environ.get("UMI_NO_WGRAD_GROUP") == "1"           # A/B knob, read per call
 
 
+# ---- grouped launches of the deferred kinds (umi/deferred.py): items as recorded by the ops below ---------------------------
+def _wgrad_single(key, item, tape):
+    x, dy, gw = item
+    ops.conv_wgrad(x, None, dy, None, gw, *key[-2:], 1, tape.inv, 1, 1, 1, 0, flags=tape._fk(1, 1, 1, 0, x.shape[3], dy.shape[3]))
+
+
+def _norm_rows_group(rows, items, tape):
+    parts, dgs, dbs = zip(*items)
+    ops_tu.gn_param_grads_group(parts, rows, dgs, dbs, tape.inv)
+
+
+def _wstd_group(_, items, tape):
+    ents, flat = [e for e, _ in items], items[0][1]
+    slots = [tape.grad_sink.buffer_for(e.w()) for e in ents] if tape.grad_sink is not None else None
+    tape.pack_cache.wstd_bwd(ents, flat[0], flat[1], slots)
+
+
 class TUTape(Tape):
-    def __init__(self, *a, seed=0, seed_dev=None, **k):
+    def __init__(self, *a, **k):
         super().__init__(*a, **k)
-        self._seed = int(seed)
-        self._seed_dev = seed_dev         # int32 device scalar mixed into every dropout seed inside the kernel: a step replayed
-        self._drop_count = 0              # from a captured HIP graph (host-side `seed` frozen) still draws fresh masks
-        self._wstd_pending, self._wstd_flat = [], None
-        self._wgrad_groups, self._readonly, self._colsum_groups = {}, set(), {}
-        self._gn_pending = []
+        d = self.deferred
+        d.marks = True          # fills stay deferred under a gradient sink: flush_mark runs them group by group of layers
+        # weight gradients of the token linears, run per SHAPE: one launch for the twelve encoder layers' fc1 weights, one for
+        # fc2, ... (umi_conv_wgrad_group; one layer at a time these GEMMs took a 7-9-way split-K whose slabs cost more than the
+        # GEMM).  Their bias gradients (column sums of the same dy) ride along.  Items (dy, gb) and (x, dy, gw).
+        d.register("colsum", lambda _, items, tape: ops.colsum_group(*zip(*items), tape.inv),
+                   each=lambda _, item, tape: ops.colsum(*item, tape.inv))
+        d.register("wgrad_group", lambda key, items, tape: ops.conv_wgrad_group(*zip(*items), *key[-2:], tape.inv),
+                   each=_wgrad_single, on=lambda tape: not _no_wgrad_group())
+        # dgamma / dbeta of the GroupNorm and LayerNorm layers, summed from their rows: one launch per row count
+        d.register("norm_rows", _norm_rows_group)
+        # StdConv2d standardisation backward of every conv that holds a slot (_wstd_slot): one umi_wstd_bwd_multi launch
+        d.register("wstd", _wstd_group)
 
     # gradients of a value with several consumers are summed by a libunetmi kernel (no torch arithmetic)
     def _give(self, act, g):
         if act.parts is None and act.needs_grad and act.grad is not None:
             act.gives += 1
-            if act.grad.data_ptr() in self._readonly:       # another reader of this buffer is still to come: a deferred
+            if self.deferred.held(act.grad):                # another reader of this buffer is still to come: a deferred
                 tgt = torch.empty_like(act.grad)               # weight gradient, or the other addend of a residual add
                 ops_tu.add(act.grad, g, tgt)
                 act.grad = tgt
@@ -48,45 +73,20 @@ class TUTape(Tape):
         super()._give(act, g)
 
     def _accumulate_target(self, act, src, R, S, stride, pad):
-        if act.grad is not None and act.grad.data_ptr() in self._readonly:
+        if act.grad is not None and self.deferred.held(act.grad):
             return None                                        # read-only buffer (see _give)
         return super()._accumulate_target(act, src, R, S, stride, pad)
 
-    # ---- weight gradients of the token linears, deferred to the end of the backward pass and run per SHAPE: one launch for
-    # the twelve encoder layers' fc1 weights, one for fc2, ... (umi_conv_wgrad_group).  One layer at a time these GEMMs have
-    # only 4,704 rows to reduce over and 36-144 output tiles: filling 256 CUs took a 7-9-way split-K whose slabs cost more
-    # than the GEMM.  288 GB of HBM keep the ~0.8 GB of operands alive until then.
-    def _defer_wgrad(self, weight, x, tx, dy, gw, s_co, s_ci):
-        if tx is not None or self.dtype != torch.float16 or _no_wgrad_group():
+    def _defer_wgrad(self, x, tx, dy, gw, s_co, s_ci):
+        """Weight gradient of a token linear: joins its shape's grouped launch (dy stays read-only until then)?"""
+        if tx is not None or self.dtype != torch.float16:
             return False
         key = (tuple(x.shape), x.stride(), tuple(dy.shape), dy.stride(), s_co, s_ci)
-        self._wgrad_groups.setdefault(key, []).append((x, dy, gw))
-        self._readonly.add(dy.data_ptr())
-        self._mark_deferred_fill(gw)            # a module used twice: Tape._set_pgrad parks the second gradient until the flush
-        return True
+        return self.deferred.defer("wgrad_group", key, (x, dy, gw), fills=(gw,), reads=(dy,))
 
     def _defer_colsum(self, dy, gb):
         """Bias gradient = column sums of dy: with the weight gradient deferred, dy is alive until the end of the pass anyway."""
-        if dy.data_ptr() not in self._readonly:
-            return False
-        self._colsum_groups.setdefault((tuple(dy.shape), dy.stride()), []).append((dy, gb))
-        self._mark_deferred_fill(gb)
-        return True
-
-    def _flush_wgrad_groups(self):
-        for items in self._colsum_groups.values():
-            dys, gbs = zip(*items)
-            if len(items) < 2 or not ops.colsum_group(dys, gbs, self.inv):
-                for dy, gb in items:
-                    ops.colsum(dy, gb, self.inv)
-        self._colsum_groups = {}
-        for (xs_, _, dys_, _, s_co, s_ci), items in self._wgrad_groups.items():
-            xs, dys, gws = zip(*items)
-            if len(items) < 2 or not ops.conv_wgrad_group(xs, dys, gws, s_co, s_ci, self.inv):
-                for x, dy, gw in items:
-                    ops.conv_wgrad(x, None, dy, None, gw, s_co, s_ci, 1, self.inv, 1, 1, 1, 0,
-                                   flags=self._fk(1, 1, 1, 0, x.shape[3], dy.shape[3]))
-        self._wgrad_groups, self._readonly, self._colsum_groups = {}, set(), {}
+        return self.deferred.held(dy) and self.deferred.defer("colsum", (tuple(dy.shape), dy.stride()), (dy, gb), fills=(gb,))
 
     # ---- convolution with weight standardisation (no bias), output stored raw == activated -----------------------
     def std_conv(self, a: Act, conv):
@@ -124,9 +124,7 @@ class TUTape(Tape):
                 gws = slot[0] if slot is not None else torch.empty_like(ws)
                 ops.conv_wgrad(a.raw, a.tx, o.grad, None, gws, Ci * R * S, R * S, 1, self.inv, R, S, stride, pad,
                                flags=fk(R, S, stride, pad, Ci, Co),
-                               defer=self._wgrad_deferred if slot is not None else None)
-                if slot is not None:
-                    self._mark_deferred_fill(slot[1])
+                               defer=self.deferred.open("wgrad_reduce") if slot is not None else None)
                 # with a slot the standardisation's backward runs once for all convs at the end of the backward pass
                 self._set_pgrad(w, slot[1] if slot is not None else ops_tu.wstd_bwd(ws, rstd, gws))
                 if _wants_grad(a):
@@ -145,27 +143,23 @@ class TUTape(Tape):
         second is filled by ONE umi_wstd_bwd_multi launch at the next flush (under a gradient sink it IS the parameter's bucket
         slot).  None where that deferral is not safe: a conv used twice has ONE slot (its second gradient is computed at once and
         added after the flush, Tape._set_pgrad)."""
-        if id(w) in self.param_grads or any(e is ent for e in self._wstd_pending):
+        pend = self.deferred.open("wstd")          # (ent, flat buffers) of the convs that hold a slot
+        if id(w) in self.param_grads or any(e is ent for e, _ in pend):
             return None
         sink_slot = self.grad_sink.buffer_for(w) if self.grad_sink is not None else None
         if self.grad_sink is not None and sink_slot is None:
             return None
-        if self._wstd_flat is None:
+        if pend:
+            flat = pend[-1][1]
+        else:
             n = self.pack_cache.wstd_total
-            self._wstd_flat = (torch.empty(n, dtype=torch.float32, device=w.device),
-                               torch.empty(n, dtype=torch.float32, device=w.device) if self.grad_sink is None else None)
-        self._wstd_pending.append(ent)
-        gws = self._wstd_flat[0][ent.off:ent.off + w.numel()].view(w.shape)
-        if sink_slot is not None:              # the launch writes the parameter gradient straight into the bucket slot
-            return gws, sink_slot
-        return gws, self._wstd_flat[1][ent.off:ent.off + w.numel()].view(w.shape)
-
-    _defer_under_sink = True
-
-    def backward(self):
-        self._wstd_pending, self._wstd_flat = [], None
-        self._wgrad_groups, self._readonly, self._colsum_groups = {}, set(), {}
-        super().backward()
+            flat = (torch.empty(n, dtype=torch.float32, device=w.device),
+                    torch.empty(n, dtype=torch.float32, device=w.device) if self.grad_sink is None else None)
+        gws = flat[0][ent.off:ent.off + w.numel()].view(w.shape)
+        # (under a sink the launch writes the parameter gradient straight into the bucket slot)
+        gw = sink_slot if sink_slot is not None else flat[1][ent.off:ent.off + w.numel()].view(w.shape)
+        self.deferred.defer("wstd", None, (ent, flat), fills=(gw,))
+        return gws, gw
 
     def flush_mark(self):
         """Marks a point of the forward pass: when the backward pass comes back to it, every deferred gradient fill recorded so far
@@ -173,27 +167,10 @@ class TUTape(Tape):
         a mark between the ResNet hybrid and the ViT encoder, so the encoder's ~85 M gradient values (the first two thirds of a
         R50-ViT-B/16's buckets in reduction order) are on the wire while the hybrid's backward pass computes."""
         if self.record and self.grad_sink is not None:
-            self.steps.append(self._flush_deferred)
-
-    def _finish_param_grads(self):
-        self._flush_wgrad_groups()
-        by_n = {}
-        for part, n_, dg, db in self._gn_pending:
-            by_n.setdefault(n_, []).append((part, dg, db))
-        for n_, items in by_n.items():
-            parts, dgs, dbs = zip(*items)
-            ops_tu.gn_param_grads_group(parts, n_, dgs, dbs, self.inv)
-        self._gn_pending = []
-        if self._wstd_pending:
-            slots = None
-            if self.grad_sink is not None:
-                slots = [self.grad_sink.buffer_for(e.w()) for e in self._wstd_pending]
-            self.pack_cache.wstd_bwd(self._wstd_pending, self._wstd_flat[0], self._wstd_flat[1], slots)
-            self._wstd_pending = []
+            self.steps.append(self.deferred.flush)
 
     @staticmethod
     def _strided_dgrad(dy, wpd, dx, R, S, stride, pad):
-        import ctypes
         N, Hd, Wd, Cd, lddy = ops._nhwc(dy)
         _, Hx, Wx, Cx, lddx = ops._nhwc(dx)
         lay = ctypes.c_int(0)
@@ -205,7 +182,7 @@ class TUTape(Tape):
             raise ValueError("this data gradient takes the MFMA path: pass a callable so the weights get the k8 packing")
         L.call("umi_conv_fwd", dy.data_ptr(), lddy, None, wpd.data_ptr(), None, dx.data_ptr(), lddx, None,
                N, Hd, Wd, Cd, Cx, R, S, stride, pad, Hx, Wx, 0, 0, Hx, Wx, ops._dt(dy), ops._dt(dx),
-               L.CONV_DGRAD_STRIDED | L.CONV_UPSAMPLE2 * 0, ops._stream())
+               L.CONV_DGRAD_STRIDED, ops._stream())
 
     # ---- GroupNorm (+ residual) (+ ReLU) ---------------------------------------------------------------------------
     def group_norm(self, a: Act, gn, relu, residual: Act = None):
@@ -227,8 +204,7 @@ class TUTape(Tape):
                     part = ops_tu.gn_bwd(o.grad, out, a.raw, mean, rstd, g32, gn.num_groups, relu, dx, dres, self.inv,
                                          keep_part=True)
                     dg, db = self._new_pgrad(gn.weight), self._new_pgrad(gn.bias)
-                    self._gn_pending.append((part, N, dg, db))
-                    self._mark_deferred_fill(dg, db)
+                    self.deferred.defer("norm_rows", N, (part, dg, db), fills=(dg, db))
                 else:
                     dg, db = ops_tu.gn_bwd(o.grad, out, a.raw, mean, rstd, g32, gn.num_groups, relu, dx, dres, self.inv)
                 self._set_pgrad(gn.weight, dg)
@@ -283,10 +259,10 @@ class TUTape(Tape):
         w4 = weight.detach().float().reshape(Co, Ci, 1, 1)
         b32 = bias.detach().float() if bias is not None else None
         # (kernel-layout copies from the model's PackCache when `weight` is a parameter: MLP / out-projection / patch embedding)
-        if _fused is None or not _fused(out, lambda lay: self._pack("conv_fwd", weight, w4, bool(lay)), b32):
+        if _fused is None or not _fused(out, self._packer("conv_fwd", weight, w4), b32):
             if _fused is not None:
                 return None                             # the caller runs the unfused sequence
-            ops.conv_fwd(a.raw, a.tx, lambda lay: self._pack("conv_fwd", weight, w4, bool(lay)), b32, out, 1, 1, 1, 0,
+            ops.conv_fwd(a.raw, a.tx, self._packer("conv_fwd", weight, w4), b32, out, 1, 1, 1, 0,
                          flags=self._fk(1, 1, 1, 0, Ci, Co))
         o = Act(out, None)
         if self.record:
@@ -294,7 +270,7 @@ class TUTape(Tape):
                 if o.grad is None:
                     return
                 gw = self._new_pgrad(weight)
-                if not self._defer_wgrad(weight, a.raw, a.tx, o.grad, gw, Ci, 1):
+                if not self._defer_wgrad(a.raw, a.tx, o.grad, gw, Ci, 1):
                     ops.conv_wgrad(a.raw, a.tx, o.grad, None, gw, Ci, 1, 1, self.inv, 1, 1, 1, 0, flags=self._fk(1, 1, 1, 0, Ci, Co))
                 self._set_pgrad(weight, gw)
                 if bias is not None:
@@ -304,7 +280,7 @@ class TUTape(Tape):
                     self._set_pgrad(bias, gb)
                 if _wants_grad(a):
                     dx = self.alloc(N, H, W, Ci, device=out.device)
-                    ops.conv_fwd(o.grad, None, lambda lay: self._pack("conv_dgrad", weight, w4, bool(lay)), None, dx, 1, 1, 1, 0,
+                    ops.conv_fwd(o.grad, None, self._packer("conv_dgrad", weight, w4), None, dx, 1, 1, 1, 0,
                                  flags=self._fk(1, 1, 1, 0, Co, Ci))
                     self._give(a, dx)
             self.steps.append(bwd)
@@ -329,8 +305,7 @@ class TUTape(Tape):
                         and id(ln.bias) not in self.param_grads):
                     part, rows = ops_tu.ln_bwd(o.grad, a.raw, g32, mean, rstd, dx, self.inv, keep_part=True)
                     dg, db = self._new_pgrad(ln.weight), self._new_pgrad(ln.bias)
-                    self._gn_pending.append((part, rows, dg, db))        # summed with the GroupNorm rows at the end of the pass
-                    self._mark_deferred_fill(dg, db)
+                    self.deferred.defer("norm_rows", rows, (part, dg, db), fills=(dg, db))     # summed with the GroupNorm rows
                 else:
                     dg, db = ops_tu.ln_bwd(o.grad, a.raw, g32, mean, rstd, dx, self.inv)
                 self._set_pgrad(ln.weight, dg)
@@ -363,7 +338,7 @@ class TUTape(Tape):
                     return
                 # both addends receive the same tensor (no copy): it is marked read-only, an accumulation into either
                 # addend's gradient then goes to a fresh tensor (_give) instead of in place
-                self._readonly.add(o.grad.data_ptr())
+                self.deferred.hold(o.grad)
                 self._give(a, o.grad)
                 self._give(b, o.grad)
             self.steps.append(bwd)
@@ -430,7 +405,7 @@ class TUTape(Tape):
                 else:
                     ops_tu.dropout(o.grad, dx, mask, True, p, 0)
                 if add is not None:
-                    self._readonly.add(o.grad.data_ptr())
+                    self.deferred.hold(o.grad)
                     self._give(add, o.grad)
                 self._give(lin, dx)
             self.steps.append(bwd)
@@ -466,7 +441,7 @@ class TUTape(Tape):
                 else:
                     ops_tu.dropout(o.grad, dx, mask, True, p, 0)
                 if add is not None:                    # the residual branch receives the same tensor (read-only, see add())
-                    self._readonly.add(o.grad.data_ptr())
+                    self.deferred.hold(o.grad)
                     self._give(add, o.grad)
                 self._give(a, dx)
             self.steps.append(bwd)
@@ -529,7 +504,7 @@ class TUTape(Tape):
                     for i, m in enumerate(mods):
                         d_i = dqkv[..., i * C:(i + 1) * C]
                         gw = self._new_pgrad(m.weight)
-                        if not self._defer_wgrad(m.weight, a.raw, a.tx, d_i, gw, C, 1):
+                        if not self._defer_wgrad(a.raw, a.tx, d_i, gw, C, 1):
                             ops.conv_wgrad(a.raw, a.tx, d_i, None, gw, C, 1, 1, self.inv, 1, 1, 1, 0, flags=self._fk(1, 1, 1, 0, C, C))
                         self._set_pgrad(m.weight, gw)
                         gb = self._new_pgrad(m.bias)
@@ -538,7 +513,7 @@ class TUTape(Tape):
                         self._set_pgrad(m.bias, gb)
                 else:
                     gw = torch.empty(3 * C, C, dtype=torch.float32, device=out.device)
-                    if not self._defer_wgrad(query.weight, a.raw, a.tx, dqkv, gw, C, 1):
+                    if not self._defer_wgrad(a.raw, a.tx, dqkv, gw, C, 1):
                         ops.conv_wgrad(a.raw, a.tx, dqkv, None, gw, C, 1, 1, self.inv, 1, 1, 1, 0,
                                        flags=self._fk(1, 1, 1, 0, C, 3 * C))
                     gb = torch.empty(3 * C, dtype=torch.float32, device=out.device)
