@@ -370,6 +370,26 @@ int umi_attn_fwd(const void* q, const void* k, const void* v, int ld, void* o, i
 int umi_attn_bwd(const void* q, const void* k, const void* v, int ld, const void* o, const void* dO, int ldo,
                  const float* lse, void* dq, void* dk, void* dv, int ldd, float* delta, int B, int N, int heads, int D,
                  int dtype, umi_stream_t stream);
+/* umi_attn_fwd_flags / umi_attn_bwd_flags flags */
+enum { UMI_ATTN_F32_MFMA = 1 /* opt-in: fp32 attention runs on the fp32-input matrix-core instruction (v_mfma_f32_32x32x2_f32,
+                                csrc/attention_mfma_f32.hip: the fp16 kernels' forward / dQ / dKV decomposition, fp32 operands, the
+                                same log-sum-exp definition as the VALU kernels, so a forward of either feeds a backward of the
+                                other; no atomics, nothing allocated at launch).  Taken when dtype is UMI_F32, D = 64, ld, ldo and
+                                (backward) ldd are multiples of 4 and every tensor address is 16-byte aligned; any B, N, heads.
+                                IGNORED otherwise, like the two convolution flags: the call then runs exactly as without it */ };
+/* The two calls above with `flags` before the stream; flags = 0 is the call above, bit for bit. */
+int umi_attn_fwd_flags(const void* q, const void* k, const void* v, int ld, void* o, int ldo, float* lse, int B, int N, int heads,
+                       int D, int dtype, int flags, umi_stream_t stream);
+int umi_attn_bwd_flags(const void* q, const void* k, const void* v, int ld, const void* o, const void* dO, int ldo,
+                       const float* lse, void* dq, void* dk, void* dv, int ldd, float* delta, int B, int N, int heads, int D,
+                       int dtype, int flags, umi_stream_t stream);
+/* Host only, launches nothing: the selector of the calls above.  *kernel = 0 the VALU kernels, 1 the fp16 matrix-core kernels
+ * (UMI_F16, D = 64, strides % 8 == 0, 16-byte aligned addresses; no flag needed), 2 the fp32 matrix-core kernels.  ldd = 0 (a
+ * forward call) and null pointers mean "not given, assume fine"; a backward call also looks at dO, dq, dk and dv, which share
+ * o's and the gradients' strides.  A call whose plan names 2 never falls back.  UMI_ERR_BADARG for N <= 0, heads <= 0, an
+ * unknown dtype or a null `kernel`; UMI_ERR_UNSUPPORTED where no kernel serves D (the VALU kernels know 16, 32 and 64). */
+int umi_attn_plan(int N, int heads, int D, int ld, int ldo, int ldd, int dtype, int flags, const void* q, const void* k,
+                  const void* v, const void* o, int* kernel);
 
 /* UpsamplingBilinear2d(scale_factor=2), align_corners=True (vit_seg_modeling.py:307): forward x[N,H,W,C] -> y[N,2H,2W,C];
  * backward (x = dy [N,2H,2W,C]) -> y = dx [N,H,W,C] (deterministic gather form). */

@@ -8,7 +8,8 @@ embedding + position embedding, 12 pre-LN transformer blocks (softmax attention,
 (umi/graph_tu.py) with a hand-written backward; nothing runs through torch.nn.
 
 Keyword-only extra: `compute_dtype` ("fp16" default / "fp32" parity mode / "fp32_mfma_gemm": "fp32" with the linears, the 1x1 and
-the 3x3 / stride-1 convolutions on the fp32 matrix-core kernels; env UMI_COMPUTE_DTYPE).
+the 3x3 / stride-1 convolutions on the fp32 matrix-core kernels / "fp32_mfma_attn": "fp32_mfma_gemm" with the softmax attention
+on the fp32 matrix-core kernels as well (head dimension 64; ignored at any other); env UMI_COMPUTE_DTYPE).
 `VisionTransformerMultitask` / `VisionTransformerMultitaskEM` (reference :444-638): the same encoder with 2 / 6 CUP decoders
 and heads on one tape.
 Not supported: `vis=True` (attention maps are never materialised), the non-hybrid (pure ViT patch conv) variant.
@@ -22,7 +23,7 @@ import torch.nn as nn
 from torch.nn import Conv2d, Dropout, LayerNorm, Linear
 from torch.nn.modules.utils import _pair
 
-from Model import _TapeFunction, _resolve_conv_flags, _resolve_dtype, _run_tape
+from Model import _TapeFunction, _resolve_attn_flags, _resolve_conv_flags, _resolve_dtype, _run_tape
 from umi import graph as G
 from umi.graph_tu import TUTape
 
@@ -356,6 +357,7 @@ class VisionTransformer(nn.Module):
                           pack_cache=G.pack_cache_of(self))
             flags = _resolve_conv_flags(self._compute_dtype)
             tape.conv3x3_flags, tape.conv1x1_flags = flags if flags[1] else (0, 0)       # "fp32_mfma" sets no flag on this tape
+            tape.attn_flags = _resolve_attn_flags(self._compute_dtype)
             a = tape.input_nchw(x, needs_grad=False)
             emb = self.transformer.embeddings
             h, skips = _build_embeddings(tape, a, emb)

@@ -228,3 +228,12 @@ int umi_attn_fwd_mfma(const void* q, const void* k, const void* v, int ld, void*
 int umi_attn_bwd_mfma(const void* q, const void* k, const void* v, int ld, const void* o, const void* dO, int ldo,
                       const float* lse, void* dq, void* dk, void* dv, int ldd, float* delta, int B, int N, int Hh,
                       hipStream_t s);
+
+// ---- attention_mfma_f32.hip: only under UMI_ATTN_F32_MFMA -----------------------------------------------------------------------
+// ptrs: the OR of every tensor address of the call (16-byte alignment); ldd = 0 in a forward call
+bool umi_attn_f32_mfma_ok(int D, int ld, int ldo, int ldd, int dtype, int flags, uintptr_t ptrs);
+int umi_attn_fwd_f32_mfma(const void* q, const void* k, const void* v, int ld, void* o, int ldo, float* lse, int B, int N, int Hh,
+                          hipStream_t s);
+int umi_attn_bwd_f32_mfma(const void* q, const void* k, const void* v, int ld, const void* o, const void* dO, int ldo,
+                          const float* lse, void* dq, void* dk, void* dv, int ldd, float* delta, int B, int N, int Hh,
+                          hipStream_t s);

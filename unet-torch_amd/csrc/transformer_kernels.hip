@@ -825,11 +825,28 @@ static int attn_fwd_t(const void* q, const void* k, const void* v, int ld, void*
     else return UMI_ERR_UNSUPPORTED;
     return UMI_OK;
 }
-extern "C" int umi_attn_fwd(const void* q, const void* k, const void* v, int ld, void* o, int ldo, float* lse, int B, int N,
-                            int heads, int D, int dtype, umi_stream_t st) {
+// The ONE selector of the attention entry points: 0 = the VALU kernels of this file, 1 = attention_mfma.hip (fp16), 2 =
+// attention_mfma_f32.hip (fp32, only under UMI_ATTN_F32_MFMA).  ldd = 0 and null pointers stand for "not part of this call".
+static int attn_kernel_of(int D, int ld, int ldo, int ldd, int dtype, int flags, const void* q, const void* k, const void* v,
+                          uintptr_t others) {
+    if (umi_attn_mfma_ok(D, ld, ldo, dtype, q, k, v) && ldd % 8 == 0 && (others & 15) == 0) return 1;
+    if (umi_attn_f32_mfma_ok(D, ld, ldo, ldd, dtype, flags, (uintptr_t)q | (uintptr_t)k | (uintptr_t)v | others)) return 2;
+    return 0;
+}
+extern "C" int umi_attn_plan(int N, int heads, int D, int ld, int ldo, int ldd, int dtype, int flags, const void* q, const void* k,
+                             const void* v, const void* o, int* kernel) {
+    if (!kernel || N <= 0 || heads <= 0 || D <= 0 || (dtype != UMI_F32 && dtype != UMI_F16)) return UMI_ERR_BADARG;
+    *kernel = attn_kernel_of(D, ld, ldo, ldd, dtype, flags, q, k, v, (uintptr_t)o);
+    if (*kernel == 0 && D != 64 && D != 32 && D != 16) return UMI_ERR_UNSUPPORTED;
+    return UMI_OK;
+}
+
+extern "C" int umi_attn_fwd_flags(const void* q, const void* k, const void* v, int ld, void* o, int ldo, float* lse, int B, int N,
+                                  int heads, int D, int dtype, int flags, umi_stream_t st) {
     if (!q || !k || !v || !o || !lse || B <= 0 || N <= 0 || heads <= 0) return UMI_ERR_BADARG;
-    if (umi_attn_mfma_ok(D, ld, ldo, dtype, q, k, v) && (((uintptr_t)o) & 15) == 0)
-        return umi_attn_fwd_mfma(q, k, v, ld, o, ldo, lse, B, N, heads, (hipStream_t)st);
+    const int kernel = attn_kernel_of(D, ld, ldo, 0, dtype, flags, q, k, v, (uintptr_t)o);
+    if (kernel == 1) return umi_attn_fwd_mfma(q, k, v, ld, o, ldo, lse, B, N, heads, (hipStream_t)st);
+    if (kernel == 2) return umi_attn_fwd_f32_mfma(q, k, v, ld, o, ldo, lse, B, N, heads, (hipStream_t)st);
     int rc;
     if (dtype == UMI_F32) rc = attn_fwd_t<float>(q, k, v, ld, o, ldo, lse, B, N, heads, D, (hipStream_t)st);
     else if (dtype == UMI_F16) rc = attn_fwd_t<half_t>(q, k, v, ld, o, ldo, lse, B, N, heads, D, (hipStream_t)st);
@@ -837,6 +854,10 @@ extern "C" int umi_attn_fwd(const void* q, const void* k, const void* v, int ld,
     if (rc) return rc;
     UMI_LAUNCH_CHECK();
     return UMI_OK;
+}
+extern "C" int umi_attn_fwd(const void* q, const void* k, const void* v, int ld, void* o, int ldo, float* lse, int B, int N,
+                            int heads, int D, int dtype, umi_stream_t st) {
+    return umi_attn_fwd_flags(q, k, v, ld, o, ldo, lse, B, N, heads, D, dtype, 0, st);
 }
 
 template <typename T>
@@ -854,13 +875,17 @@ static int attn_bwd_t(const void* q, const void* k, const void* v, int ld, const
 #undef GO
     return UMI_OK;
 }
-extern "C" int umi_attn_bwd(const void* q, const void* k, const void* v, int ld, const void* o, const void* dO, int ldo,
-                            const float* lse, void* dq, void* dk, void* dv, int ldd, float* delta, int B, int N, int heads,
-                            int D, int dtype, umi_stream_t st) {
+extern "C" int umi_attn_bwd_flags(const void* q, const void* k, const void* v, int ld, const void* o, const void* dO, int ldo,
+                                  const float* lse, void* dq, void* dk, void* dv, int ldd, float* delta, int B, int N, int heads,
+                                  int D, int dtype, int flags, umi_stream_t st) {
     if (!q || !k || !v || !o || !dO || !lse || !dq || !dk || !dv || !delta) return UMI_ERR_BADARG;
-    if (umi_attn_mfma_ok(D, ld, ldo, dtype, q, k, v) && ldd % 8 == 0 &&
-        ((((uintptr_t)o) | ((uintptr_t)dO) | ((uintptr_t)dq) | ((uintptr_t)dk) | ((uintptr_t)dv)) & 15) == 0)
-        return umi_attn_bwd_mfma(q, k, v, ld, o, dO, ldo, lse, dq, dk, dv, ldd, delta, B, N, heads, (hipStream_t)st);
+    const int kernel = attn_kernel_of(D, ld, ldo, ldd, dtype, flags, q, k, v,
+                                      (uintptr_t)o | (uintptr_t)dO | (uintptr_t)dq | (uintptr_t)dk | (uintptr_t)dv);
+    if (kernel == 1) return umi_attn_bwd_mfma(q, k, v, ld, o, dO, ldo, lse, dq, dk, dv, ldd, delta, B, N, heads, (hipStream_t)st);
+    if (kernel == 2) {
+        if (B <= 0 || N <= 0 || heads <= 0) return UMI_ERR_BADARG;
+        return umi_attn_bwd_f32_mfma(q, k, v, ld, o, dO, ldo, lse, dq, dk, dv, ldd, delta, B, N, heads, (hipStream_t)st);
+    }
     int rc;
     if (dtype == UMI_F32) rc = attn_bwd_t<float>(q, k, v, ld, o, dO, ldo, lse, dq, dk, dv, ldd, delta, B, N, heads, D, (hipStream_t)st);
     else if (dtype == UMI_F16) rc = attn_bwd_t<half_t>(q, k, v, ld, o, dO, ldo, lse, dq, dk, dv, ldd, delta, B, N, heads, D, (hipStream_t)st);
@@ -868,6 +893,11 @@ extern "C" int umi_attn_bwd(const void* q, const void* k, const void* v, int ld,
     if (rc) return rc;
     UMI_LAUNCH_CHECK();
     return UMI_OK;
+}
+extern "C" int umi_attn_bwd(const void* q, const void* k, const void* v, int ld, const void* o, const void* dO, int ldo,
+                            const float* lse, void* dq, void* dk, void* dv, int ldd, float* delta, int B, int N, int heads,
+                            int D, int dtype, umi_stream_t st) {
+    return umi_attn_bwd_flags(q, k, v, ld, o, dO, ldo, lse, dq, dk, dv, ldd, delta, B, N, heads, D, dtype, 0, st);
 }
 
 extern "C" int umi_bilinear2x(const void* x, int ldx, const void* tx, void* y, int ldy, int backward, int N, int H, int W, int C,

@@ -45,6 +45,7 @@ def _wstd_group(_, items, tape):
 class TUTape(Tape):
     def __init__(self, *a, **k):
         super().__init__(*a, **k)
+        self.attn_flags = 0               # compute_dtype "fp32_mfma_attn": lib.UMI_ATTN_F32_MFMA, passed to the attention calls
         d = self.deferred
         d.marks = True          # fills stay deferred under a gradient sink: flush_mark runs them group by group of layers
         # weight gradients of the token linears, run per SHAPE: one launch for the twelve encoder layers' fc1 weights, one for
@@ -447,16 +448,21 @@ class TUTape(Tape):
             self.steps.append(bwd)
         return o
 
+    def _attn_kw(self):
+        """The attention calls' keyword: none without a flag, so that a flag-less tape calls ops_tu.attn_fwd / attn_bwd exactly as
+        before (positional arguments only)."""
+        return {"flags": self.attn_flags} if self.attn_flags else {}
+
     def attention(self, q: Act, k: Act, v: Act, heads):
         out = torch.empty_like(q.raw)
-        lse = ops_tu.attn_fwd(q.raw, k.raw, v.raw, out, heads)
+        lse = ops_tu.attn_fwd(q.raw, k.raw, v.raw, out, heads, **self._attn_kw())
         o = Act(out, None)
         if self.record:
             def bwd():
                 if o.grad is None:
                     return
                 dq, dk, dv = torch.empty_like(q.raw), torch.empty_like(q.raw), torch.empty_like(q.raw)
-                ops_tu.attn_bwd(q.raw, k.raw, v.raw, out, o.grad, lse, dq, dk, dv, heads)
+                ops_tu.attn_bwd(q.raw, k.raw, v.raw, out, o.grad, lse, dq, dk, dv, heads, **self._attn_kw())
                 self._give(q, dq)
                 self._give(k, dk)
                 self._give(v, dv)
@@ -490,14 +496,15 @@ class TUTape(Tape):
         ops.conv_fwd(a.raw, a.tx, packed("conv_fwd"), bcat, qkv, 1, 1, 1, 0, flags=self._fk(1, 1, 1, 0, C, 3 * C))
         q, k, v = (qkv[..., i * C:(i + 1) * C] for i in range(3))
         out = self.alloc(N, H, W, C, device=a.raw.device)
-        lse = ops_tu.attn_fwd(q, k, v, out, heads)
+        lse = ops_tu.attn_fwd(q, k, v, out, heads, **self._attn_kw())
         o = Act(out, None)
         if self.record:
             def bwd():
                 if o.grad is None:
                     return
                 dqkv = self.alloc(N, H, W, 3 * C, device=out.device)
-                ops_tu.attn_bwd(q, k, v, out, o.grad, lse, *(dqkv[..., i * C:(i + 1) * C] for i in range(3)), heads)
+                ops_tu.attn_bwd(q, k, v, out, o.grad, lse, *(dqkv[..., i * C:(i + 1) * C] for i in range(3)), heads,
+                                **self._attn_kw())
                 if self.grad_sink is not None:
                     # three items of the grouped launches, each writing its own bucket slot (the fused [3C, C] gradient would
                     # have to be copied into the three slots afterwards)

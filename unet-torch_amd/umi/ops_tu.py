@@ -159,26 +159,38 @@ def linear_fused(x, wp8, bias, y, epi, p, seed, seed_dev, mask, aux=None, y2=Non
                        _dt(x), _stream())
 
 
-def attn_fwd(q, k, v, o, heads):
+def attn_fwd(q, k, v, o, heads, flags=0):
+    """flags: lib.UMI_ATTN_F32_MFMA opts an fp32 / head-dim-64 call into the fp32 matrix-core kernels (ignored elsewhere)."""
     B, _, N, C = q.shape
     D = C // heads
     ld = _nhwc(q)[4]
     assert _nhwc(k)[4] == ld and _nhwc(v)[4] == ld
     lse = torch.empty(B * heads * N, dtype=torch.float32, device=q.device)
-    L.call("umi_attn_fwd", q.data_ptr(), k.data_ptr(), v.data_ptr(), ld, o.data_ptr(), _nhwc(o)[4], lse.data_ptr(), B,
-           N, heads, D, _dt(q), _stream())
+    L.call("umi_attn_fwd_flags", q.data_ptr(), k.data_ptr(), v.data_ptr(), ld, o.data_ptr(), _nhwc(o)[4], lse.data_ptr(), B,
+           N, heads, D, _dt(q), flags, _stream())
     return lse
 
 
-def attn_bwd(q, k, v, o, dO, lse, dq, dk, dv, heads):
+def attn_bwd(q, k, v, o, dO, lse, dq, dk, dv, heads, flags=0):
     B, _, N, C = q.shape
     D = C // heads
     ld, ldo, ldd = _nhwc(q)[4], _nhwc(o)[4], _nhwc(dq)[4]
     assert _nhwc(dO)[4] == ldo and _nhwc(dk)[4] == ldd and _nhwc(dv)[4] == ldd
     delta = torch.empty_like(lse)
-    L.call("umi_attn_bwd", q.data_ptr(), k.data_ptr(), v.data_ptr(), ld, o.data_ptr(), dO.data_ptr(), ldo,
+    L.call("umi_attn_bwd_flags", q.data_ptr(), k.data_ptr(), v.data_ptr(), ld, o.data_ptr(), dO.data_ptr(), ldo,
            lse.data_ptr(), dq.data_ptr(), dk.data_ptr(), dv.data_ptr(), ldd, delta.data_ptr(), B, N,
-           heads, D, _dt(q), _stream())
+           heads, D, _dt(q), flags, _stream())
+
+
+def attn_plan(q, k, v, o, heads, flags=0, dq=None):
+    """The kernel attn_fwd (dq None) / attn_bwd (dq: one of the gradient tensors) takes for these tensors, launching nothing:
+    0 the VALU kernels, 1 the fp16 matrix-core kernels, 2 the fp32 matrix-core kernels (umi_attn_plan)."""
+    import ctypes
+    B, _, N, C = q.shape
+    kernel = ctypes.c_int(-1)
+    L.call("umi_attn_plan", N, heads, C // heads, _nhwc(q)[4], _nhwc(o)[4], _nhwc(dq)[4] if dq is not None else 0, _dt(q), flags,
+           q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(), ctypes.addressof(kernel))
+    return kernel.value
 
 
 def bilinear2x(x, y, backward=False, tx=None):
