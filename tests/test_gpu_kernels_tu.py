@@ -528,7 +528,7 @@ def test_grouped_colsum_matches_per_tensor_launches(n, M, C, strided):
         _close(o, x[0, 0].float().sum(0) * 0.5, 2e-3)
 
 
-@pytest.mark.parametrize("shape", [(2, 15, 17, 64), (1, 112, 112, 64), (3, 8, 9, 24)])
+@pytest.mark.parametrize("shape", [(2, 15, 17, 64), (1, 112, 112, 64), (3, 8, 9, 24), (1, 256, 256, 64)])
 def test_pool3s2_fp16_with_recorded_taps(shape):
     """MaxPool2d(3, 2) fp16 vector kernels: forward against torch (ties included: values drawn from 8 levels), backward with the
     recorded winning taps against the backward that re-derives them from the input -- identical, and both equal to torch's
