@@ -527,6 +527,51 @@ int umi_optim_sgd_multi_dev(const void* descs, int n_desc, int total_blocks, con
 int umi_optim_adam_multi_dev(const void* descs, int n_desc, int total_blocks, const void* hyper, double beta1, double beta2,
                              double eps, double weight_decay, umi_stream_t stream);
 
+/* Guarded optimizer step: non-finite check, global gradient-norm clipping and a dynamic loss scale, all on the device so that a
+ * captured HIP graph keeps deciding per step.  The state is a DEVICE array of UMI_GUARD_LEN doubles (8-byte aligned; the
+ * partials workspace `ws` is 16-byte aligned):
+ *   last step   NORM (global L2 norm of the gradients with the loss scale divided out; inf / NaN as computed), NONFINITE
+ *               (count of inf / NaN gradient elements), COEF (factor the update multiplies every gradient by: clip / SCALE,
+ *               0 on a skipped step), SKIP (1: the update kernels store nothing)
+ *   state       SCALE (the dynamic loss-scale factor d the NEXT backward pass multiplies its seed by), STREAK (clean steps
+ *               since the scale last changed)
+ *   totals      STEPS, SKIPPED, CLIPPED
+ *   settings    MAX_NORM (<= 0: no clipping), GROWTH_INTERVAL (<= 0: static scale), GROWTH, BACKOFF, MIN_SCALE, MAX_SCALE
+ * One step:  umi_grad_norm_partials over every descriptor table (rows of `ws` are disjoint: block_offset), then ONE
+ * umi_grad_guard_finalize, then umi_optim_hyper_pre_guarded / umi_optim_*_multi_guarded per table.
+ *   partials  row block_offset + blk of `ws` <- { sum of g^2 over the block (squares and sums in double, fixed order, no atomics),
+ *             number of non-finite g }; reads g only.  ws_bytes >= umi_grad_guard_ws_bytes(block_offset + total_blocks), else
+ *             UMI_ERR_WORKSPACE.
+ *   finalize  S, K <- fixed-order sums of the first total_blocks rows; with d = SCALE:
+ *               NORM = sqrt(S) / d; NONFINITE = K; SKIP = K > 0
+ *               clean:   clip = MAX_NORM > 0 ? min(1, MAX_NORM / (NORM + 1e-6)) : 1; COEF = clip / d; CLIPPED += clip < 1
+ *               skipped: COEF = 0; SKIPPED += 1
+ *               STEPS += 1
+ *               then, if GROWTH_INTERVAL > 0 (torch.amp.GradScaler's rule):
+ *                 skipped: d = max(d * BACKOFF, MIN_SCALE), STREAK = 0
+ *                 clean:   STREAK += 1; at GROWTH_INTERVAL: d = min(d * GROWTH, MAX_SCALE), STREAK = 0
+ *             (COEF is formed with the d the backward pass used; only then does d change.)
+ *   update    SKIP set: returns before any store, except that a first SGD step zero-fills its (uninitialised) momentum
+ *             buffers.  Otherwise g' = (float)COEF == 1 ? g : g * (float)COEF (one fp32 rounding), then the arithmetic of
+ *             umi_optim_*_multi on g'.  `hyper` NULL: lr / step_size / bc2_sqrt are the host values given.  dampening != 0 is
+ *             UMI_ERR_BADARG (a skipped first step could not reproduce buf = clone(grad)).
+ *   hyper_pre_guarded  umi_optim_hyper_pre, but Adam's t and bias corrections advance only when SKIP is clear. */
+enum { UMI_GUARD_NORM = 0, UMI_GUARD_NONFINITE = 1, UMI_GUARD_COEF = 2, UMI_GUARD_SKIP = 3, UMI_GUARD_SCALE = 4,
+       UMI_GUARD_STREAK = 5, UMI_GUARD_STEPS = 6, UMI_GUARD_SKIPPED = 7, UMI_GUARD_CLIPPED = 8, UMI_GUARD_MAX_NORM = 9,
+       UMI_GUARD_GROWTH_INTERVAL = 10, UMI_GUARD_GROWTH = 11, UMI_GUARD_BACKOFF = 12, UMI_GUARD_MIN_SCALE = 13,
+       UMI_GUARD_MAX_SCALE = 14, UMI_GUARD_SPARE = 15, UMI_GUARD_LEN = 16 };
+size_t umi_grad_guard_ws_bytes(int total_blocks);
+int umi_grad_norm_partials(const void* descs, int n_desc, int total_blocks, int block_offset, void* ws, size_t ws_bytes,
+                           umi_stream_t stream);
+int umi_grad_guard_finalize(const void* ws, int total_blocks, double* state, umi_stream_t stream);
+int umi_optim_hyper_pre_guarded(void* hyper, int adam, const double* guard, umi_stream_t stream);
+int umi_optim_sgd_multi_guarded(const void* descs, int n_desc, int total_blocks, const void* hyper, double lr, double momentum,
+                                double dampening, double weight_decay, int nesterov, int first_step, const double* guard,
+                                umi_stream_t stream);
+int umi_optim_adam_multi_guarded(const void* descs, int n_desc, int total_blocks, const void* hyper, double step_size,
+                                 double beta1, double beta2, double bc2_sqrt, double eps, double weight_decay,
+                                 const double* guard, umi_stream_t stream);
+
 /* umi_pack_kn / umi_pack_kn8 of many weight tensors in one launch (all the convolution weights of a model after an
  * optimizer step).  `descs`: DEVICE array sorted by blk0; an entry owns ceil(T*Kpad*Npad / umi_pack_block_elems()) blocks. */
 typedef struct umi_pack_desc {

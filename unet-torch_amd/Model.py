@@ -115,6 +115,7 @@ def _run_tape(module, inputs, build, tape_cls=None, dtype=None):
                         grad_sink=getattr(module, "_umi_grad_sink", None) if record else None,
                         pack_cache=G.pack_cache_of(module), seed=seed, seed_dev=seed_dev)
         tape.conv3x3_flags, tape.conv1x1_flags = _resolve_conv_flags(getattr(module, "_compute_dtype", None))
+        tape.dyn_scale = getattr(module, "_umi_dyn_scale", None)          # umi.optim.GradGuard.attach(module)
         if hasattr(tape, "attn_flags"):              # TUTape: the standalone Attention / Block forwards
             tape.attn_flags = _resolve_attn_flags(getattr(module, "_compute_dtype", None))
         acts = [tape.input_nchw(x, needs_grad=need) for x, need in zip(inputs, in_needs)]

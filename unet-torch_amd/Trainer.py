@@ -32,6 +32,11 @@ then yield RAW batches -- uint8 / float32 HWC (or HW) images and a label map or 
 `Dataset.__getitem__` reads them before `transform` -- which are moved to the device as they are and transformed there, with
 freshly drawn augmentation parameters in the train phase and none in the validation phase, before the step and outside any
 captured graph.
+`Trainer(..., grad_guard=...)` (keyword-only; True, a dict of `umi.optim.GradGuard` arguments, or a GradGuard): the optimizer
+step skips on a non-finite gradient, clips to `max_norm` and follows a dynamic loss scale, decided on the device (eager and
+graph mode alike).  Adam then runs on its device schedule in eager mode too (a skipped step must not advance its step count).
+One line per epoch goes to `logs.txt`: `Guard on epoch N: skipped S, clipped C, loss scale X` (S and C count that epoch's
+steps).  A skipped step's loss still counts in the epoch mean.
 `lr_scheduler=True` (what the reference's train.py passes) crashes the reference in its first validation after epoch 5
 (`True.step`); here train() raises NotImplementedError before the first step whenever the run would reach that point.
 The remaining epoch loops of the reference (uncertainty-weighted multi-task, CLTR, Topo losses) are out of scope and raise.
@@ -57,7 +62,7 @@ _OTHER = ('CLTR',)
 class Trainer():
     def __init__(self, model, model_type, dtype, device, output_save_dir, dataloaders, batch_size, optimizer,
                  patience, num_epochs, loss_function, accuracy_metric, lr_scheduler=None, start_epoch=1, *, graph=None,
-                 batch_transform=None):
+                 batch_transform=None, grad_guard=None):
         self.model = model
         self.model_type = model_type
         self.dtype = dtype
@@ -87,12 +92,45 @@ class Trainer():
         self.graph = (os.environ.get("UMI_TRAINER_GRAPH") == "1") if graph is None else bool(graph)
         self._graphs, self._seen_shapes, self._dev_sched, self._side = {}, set(), False, None
         self.batch_transform = batch_transform
+        self._guard, self._guard_seen = self._make_guard(grad_guard), (0, 0)
         # multi_task_trainRatio: epoch > 5 (host, and in graph mode a device flag), ratioAccuracy of the last step
         self._ratio_gate, self._gate_dev, self._ratio = False, None, None
         self.alpha, self.alpha_list = None, []
 
         self.save_dir_model = os.path.join(self.output_save_dir, 'models/')
         os.makedirs(self.save_dir_model, exist_ok=True)
+
+    @staticmethod
+    def _make_guard(spec):
+        if spec is None or spec is False:
+            return None
+        from umi.optim import GradGuard
+        if isinstance(spec, GradGuard):
+            return spec
+        return GradGuard(**({} if spec is True else dict(spec)))
+
+    def _attach_guard(self):
+        """Before the first step: guard -> optimizer and model (whose parameters are on the device by now)."""
+        if self._guard is None or getattr(self.optimizer, "guard", None) is self._guard:
+            return
+        if not hasattr(self.optimizer, "grad_guard"):
+            raise TypeError("Trainer(grad_guard=...) needs a umi.optim optimizer")
+        self.optimizer.grad_guard(self._guard)
+        self._guard.attach(self.model)
+
+    def _device_schedule(self):
+        if not self._dev_sched:
+            poly = dict(base_lr=self.base_lr, max_iterations=self.max_iterations, power=0.9, iter_num=self.iter_num)
+            self.optimizer.device_schedule(poly=poly if self.lr_scheduler else None)
+            self._dev_sched = True
+
+    def _log_guard(self, say, epoch):
+        if self._guard is None:
+            return
+        r = self._guard.read()
+        say("Guard on epoch %i: skipped %i, clipped %i, loss scale %g"
+            % (epoch, r["skipped"] - self._guard_seen[0], r["clipped"] - self._guard_seen[1], r["scale"]))
+        self._guard_seen = (r["skipped"], r["clipped"])
 
     # ------------------------------------------------------------------------------------
     def train(self):
@@ -163,10 +201,14 @@ class Trainer():
     def train_step(self, inputs, labels):
         """One optimisation step (reference Trainer.py:700-726).  Returns the detached loss tensor."""
         inputs, labels = self._to_device(inputs, labels)
+        self._attach_guard()
         if self._graph_capable(inputs):
             return self._graphed_train_step(inputs, labels)
+        guarded_adam = self._guard is not None and "betas" in self.optimizer.param_groups[0]
+        if guarded_adam:
+            self._device_schedule()           # the step count advances on the device, and the poly rule with it
         loss = self._step_body(inputs, labels)
-        if self.lr_scheduler:
+        if self.lr_scheduler and not guarded_adam:
             lr_ = self.base_lr * (1.0 - self.iter_num / self.max_iterations) ** 0.9
             for group in self.optimizer.param_groups:
                 group['lr'] = lr_
@@ -175,10 +217,9 @@ class Trainer():
 
     def _graphed_train_step(self, inputs, labels):
         from umi.graphs import GraphedStep
-        if not self._dev_sched:
-            poly = dict(base_lr=self.base_lr, max_iterations=self.max_iterations, power=0.9, iter_num=self.iter_num)
-            self.optimizer.device_schedule(poly=poly if self.lr_scheduler else None)
-            self._dev_sched, self._side = True, torch.cuda.Stream()
+        self._device_schedule()
+        if self._side is None:
+            self._side = torch.cuda.Stream()
         flat = [inputs] + (list(labels) if isinstance(labels, (list, tuple)) else [labels])
         multi = isinstance(labels, (list, tuple))
         ratio = self._ratio_loop()
@@ -321,6 +362,7 @@ class Trainer():
                 self.alpha_list.append(self.alpha)
                 say("Alpha on epoch %i: %f" % (epoch, self.alpha))
                 say("Train loss on epoch %i: %f" % (epoch, epoch_loss))
+                self._log_guard(say, epoch)
                 total_time += elapsed
                 self.meanTimePerEpoch = total_time / epoch
                 torch.save(self.model.state_dict(), os.path.join(self.save_dir_model, 'last_epoch.pt'))
@@ -386,6 +428,7 @@ class Trainer():
                         self.train_loss_list_1.append(float(task_sums[0]) / steps)
                         self.train_loss_list_2.append(float(task_sums[1]) / steps)
                     say("Train loss on epoch %i: %f" % (epoch, epoch_loss))
+                    self._log_guard(say, epoch)
                     total_time += elapsed
                     self.meanTimePerEpoch = total_time / epoch
                     say('Curent mean training time per epoch: {:.0f}m {:.0f}s\n'.format(

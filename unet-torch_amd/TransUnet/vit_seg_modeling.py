@@ -358,6 +358,7 @@ class VisionTransformer(nn.Module):
             flags = _resolve_conv_flags(self._compute_dtype)
             tape.conv3x3_flags, tape.conv1x1_flags = flags if flags[1] else (0, 0)       # "fp32_mfma" sets no flag on this tape
             tape.attn_flags = _resolve_attn_flags(self._compute_dtype)
+            tape.dyn_scale = getattr(self, "_umi_dyn_scale", None)            # umi.optim.GradGuard.attach(self)
             a = tape.input_nchw(x, needs_grad=False)
             emb = self.transformer.embeddings
             h, skips = _build_embeddings(tape, a, emb)

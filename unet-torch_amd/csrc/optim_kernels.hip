@@ -61,8 +61,19 @@ __device__ inline void adam_one(float& p, float g, float& m, float& v, const Ada
     p = fmaf(-a.step_size, __fdiv_rn(m, denom), p);                    // param.addcdiv_(exp_avg, denom, value=-step_size)
 }
 
-template <bool ADAM, typename A>
-__global__ __launch_bounds__(256) void optim_multi_kernel(const umi_optim_desc* __restrict__ descs, int n_desc, A a) {
+// GUARD: the step is conditional on the device guard block (umi_grad_guard_finalize): nothing is stored on a skipped step, and
+// every gradient is multiplied by (float)COEF -- one fp32 rounding, as a torch multiply of the gradient would make -- before the
+// unchanged sgd_one / adam_one.  Without GUARD the body is the one the unguarded entry points have always run.
+template <bool ADAM, bool GUARD, typename A>
+__device__ __forceinline__ void optim_multi_body(const umi_optim_desc* __restrict__ descs, int n_desc, A a,
+                                                 const double* __restrict__ guard) {
+    bool skip = false;
+    float cf = 1.f;
+    if constexpr (GUARD) {
+        skip = guard[UMI_GUARD_SKIP] != 0.0;
+        cf = (float)guard[UMI_GUARD_COEF];
+    }
+    const auto gs = [cf](float g) { return (GUARD && cf != 1.f) ? __fmul_rn(g, cf) : g; };
     if (a.hp) {                               // learning rate / bias corrections from device memory (graph-safe)
         if constexpr (ADAM) { a.step_size = a.hp->step_size_f; a.bc2_sqrt = a.hp->bc2_sqrt_f; }
         else a.lr = a.hp->lr_f;
@@ -76,11 +87,21 @@ __global__ __launch_bounds__(256) void optim_multi_kernel(const umi_optim_desc* 
     const float* g = d.g + base;
     float* s0 = d.s0 ? d.s0 + base : nullptr;
     float* s1 = d.s1 ? d.s1 + base : nullptr;
+    if constexpr (GUARD) {
+        if (skip) {                           // (uniform) a skipped FIRST SGD step still owes the momentum buffer its zeros
+            if constexpr (!ADAM) {
+                if (a.first && s0)
+                    for (int i = threadIdx.x; i < cnt; i += 256) s0[i] = 0.f;
+            }
+            return;
+        }
+    }
     const unsigned long al = (unsigned long)p | (unsigned long)g | (unsigned long)s0 | (unsigned long)s1;
     if ((al & 15) == 0) {
         for (int i = threadIdx.x * 4; i + 4 <= cnt; i += 1024) {
             float4 pv = *reinterpret_cast<float4*>(p + i);
-            const float4 gv = *reinterpret_cast<const float4*>(g + i);
+            float4 gv = *reinterpret_cast<const float4*>(g + i);
+            if constexpr (GUARD) gv = make_float4(gs(gv.x), gs(gv.y), gs(gv.z), gs(gv.w));
             float4 mv = s0 ? *reinterpret_cast<float4*>(s0 + i) : make_float4(0.f, 0.f, 0.f, 0.f);
             float4 vv = (ADAM && s1) ? *reinterpret_cast<float4*>(s1 + i) : make_float4(0.f, 0.f, 0.f, 0.f);
             if constexpr (ADAM) {
@@ -98,19 +119,151 @@ __global__ __launch_bounds__(256) void optim_multi_kernel(const umi_optim_desc* 
         const int i = tail0 + threadIdx.x;
         if (i < cnt) {
             float pv = p[i], mv = s0 ? s0[i] : 0.f;
-            if constexpr (ADAM) { float vv = s1[i]; adam_one(pv, g[i], mv, vv, a); s1[i] = vv; }
-            else sgd_one(pv, g[i], mv, a);
+            if constexpr (ADAM) { float vv = s1[i]; adam_one(pv, gs(g[i]), mv, vv, a); s1[i] = vv; }
+            else sgd_one(pv, gs(g[i]), mv, a);
             p[i] = pv;
             if (s0) s0[i] = mv;
         }
     } else {
         for (int i = threadIdx.x; i < cnt; i += 256) {
             float pv = p[i], mv = s0 ? s0[i] : 0.f;
-            if constexpr (ADAM) { float vv = s1[i]; adam_one(pv, g[i], mv, vv, a); s1[i] = vv; }
-            else sgd_one(pv, g[i], mv, a);
+            if constexpr (ADAM) { float vv = s1[i]; adam_one(pv, gs(g[i]), mv, vv, a); s1[i] = vv; }
+            else sgd_one(pv, gs(g[i]), mv, a);
             p[i] = pv;
             if (s0) s0[i] = mv;
         }
+    }
+}
+
+template <bool ADAM, typename A>
+__global__ __launch_bounds__(256) void optim_multi_kernel(const umi_optim_desc* __restrict__ descs, int n_desc, A a) {
+    optim_multi_body<ADAM, false, A>(descs, n_desc, a, nullptr);
+}
+
+template <bool ADAM, typename A>
+__global__ __launch_bounds__(256) void optim_multi_guarded_kernel(const umi_optim_desc* __restrict__ descs, int n_desc, A a,
+                                                                  const double* __restrict__ guard) {
+    optim_multi_body<ADAM, true, A>(descs, n_desc, a, guard);
+}
+
+// ---- gradient guard: per-block sum of squares and non-finite count, then one workgroup that decides the step ----------------
+__device__ inline void guard_acc(float g, double& s, int& k) {
+    const double x = (double)g;
+    s += x * x;                                                        // fp32 squared is exact in double
+    k += (__float_as_uint(g) & 0x7f800000u) == 0x7f800000u;           // inf or NaN
+}
+
+// fixed-order tree over the NT threads of a workgroup; the result is valid in thread 0
+template <int NT>
+__device__ inline void guard_block_sum(double& s, double& k, double* sh_s, double* sh_k) {
+    sh_s[threadIdx.x] = s;
+    sh_k[threadIdx.x] = k;
+    __syncthreads();
+    for (int w = NT / 2; w > 0; w >>= 1) {
+        if ((int)threadIdx.x < w) {
+            sh_s[threadIdx.x] += sh_s[threadIdx.x + w];
+            sh_k[threadIdx.x] += sh_k[threadIdx.x + w];
+        }
+        __syncthreads();
+    }
+    s = sh_s[0];
+    k = sh_k[0];
+}
+
+__global__ __launch_bounds__(256) void grad_norm_partials_kernel(const umi_optim_desc* __restrict__ descs, int n_desc,
+                                                                 int block_offset, double* __restrict__ ws) {
+    __shared__ double sh_s[256], sh_k[256];
+    const int blk = blockIdx.x;
+    const umi_optim_desc d = descs[find_desc(descs, n_desc, blk)];
+    const long base = (long)(blk - d.blk0) * OPT_BLOCK;
+    const long left = d.n - base;
+    const int cnt = left < OPT_BLOCK ? (int)left : OPT_BLOCK;
+    const float* g = d.g + base;
+    double s = 0.0;
+    int k = 0;
+    if (((unsigned long)g & 15) == 0) {
+        if (cnt == OPT_BLOCK) {               // a full block: the four loads of a thread in flight together, summed in loop order
+            float4 gv[OPT_BLOCK / 1024];
+#pragma unroll
+            for (int j = 0; j < OPT_BLOCK / 1024; ++j) gv[j] = *reinterpret_cast<const float4*>(g + threadIdx.x * 4 + 1024 * j);
+#pragma unroll
+            for (int j = 0; j < OPT_BLOCK / 1024; ++j) {
+                guard_acc(gv[j].x, s, k); guard_acc(gv[j].y, s, k); guard_acc(gv[j].z, s, k); guard_acc(gv[j].w, s, k);
+            }
+        } else {
+            for (int i = threadIdx.x * 4; i + 4 <= cnt; i += 1024) {
+                const float4 gv = *reinterpret_cast<const float4*>(g + i);
+                guard_acc(gv.x, s, k); guard_acc(gv.y, s, k); guard_acc(gv.z, s, k); guard_acc(gv.w, s, k);
+            }
+            const int i = (cnt & ~3) + threadIdx.x;
+            if (i < cnt) guard_acc(g[i], s, k);
+        }
+    } else {
+        for (int i = threadIdx.x; i < cnt; i += 256) guard_acc(g[i], s, k);
+    }
+    double kd = (double)k;
+    guard_block_sum<256>(s, kd, sh_s, sh_k);
+    if (threadIdx.x == 0)
+        *reinterpret_cast<double2*>(ws + 2 * (long)(block_offset + blk)) = make_double2(s, kd);
+}
+
+// One workgroup of 1,024 threads: thread t sums rows t, t + 1024, ... in that order (four 16-byte row loads in flight per trip: a
+// U-Net has 30 k rows, a R50-ViT-B/16 103 k, and a loop of one dependent load per trip would run at the memory latency), then the tree.
+constexpr int FIN_THREADS = 1024;
+__global__ __launch_bounds__(FIN_THREADS) void grad_guard_finalize_kernel(const double* __restrict__ ws, int rows, double* st) {
+    __shared__ double sh_s[FIN_THREADS], sh_k[FIN_THREADS];
+    const double2* __restrict__ w2 = reinterpret_cast<const double2*>(ws);
+    double S = 0.0, K = 0.0;
+    for (int r = threadIdx.x; r < rows; r += 4 * FIN_THREADS) {
+        double2 v[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int rr = r + j * FIN_THREADS;
+            v[j] = rr < rows ? w2[rr] : make_double2(0.0, 0.0);
+        }
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+            if (r + j * FIN_THREADS < rows) { S += v[j].x; K += v[j].y; }
+    }
+    guard_block_sum<FIN_THREADS>(S, K, sh_s, sh_k);
+    if (threadIdx.x != 0) return;
+    double d = st[UMI_GUARD_SCALE];
+    const double norm = sqrt(S) / d;
+    st[UMI_GUARD_NORM] = norm;
+    st[UMI_GUARD_NONFINITE] = K;
+    const bool skip = K > 0.0;
+    st[UMI_GUARD_SKIP] = skip ? 1.0 : 0.0;
+    if (!skip) {
+        const double mn = st[UMI_GUARD_MAX_NORM];
+        double clip = 1.0;
+        if (mn > 0.0) {
+            const double r = mn / (norm + 1e-6);
+            clip = r < 1.0 ? r : 1.0;
+        }
+        st[UMI_GUARD_COEF] = clip / d;
+        if (clip < 1.0) st[UMI_GUARD_CLIPPED] += 1.0;
+    } else {
+        st[UMI_GUARD_COEF] = 0.0;
+        st[UMI_GUARD_SKIPPED] += 1.0;
+    }
+    st[UMI_GUARD_STEPS] += 1.0;
+    const double gi = st[UMI_GUARD_GROWTH_INTERVAL];
+    if (gi > 0.0) {                                                    // torch.amp.GradScaler.update
+        if (skip) {
+            const double b = d * st[UMI_GUARD_BACKOFF], lo = st[UMI_GUARD_MIN_SCALE];
+            d = b > lo ? b : lo;
+            st[UMI_GUARD_STREAK] = 0.0;
+        } else {
+            const double streak = st[UMI_GUARD_STREAK] + 1.0;
+            if (streak >= gi) {
+                const double b = d * st[UMI_GUARD_GROWTH], hi = st[UMI_GUARD_MAX_SCALE];
+                d = b < hi ? b : hi;
+                st[UMI_GUARD_STREAK] = 0.0;
+            } else {
+                st[UMI_GUARD_STREAK] = streak;
+            }
+        }
+        st[UMI_GUARD_SCALE] = d;
     }
 }
 
@@ -276,8 +429,8 @@ extern "C" int umi_optim_adam_multi(const void* descs, int n_desc, int total_blo
 }
 
 // ---- device-resident hyper-parameters (graph-safe learning rate / Adam step count) ------------------------------------
-__global__ void hyper_pre_kernel(Hyper* h, int adam) {
-    if (adam) {                                   // torch.optim.Adam: step += 1; bias corrections in double, then rounded
+__global__ void hyper_pre_kernel(Hyper* h, int adam, const double* guard) {
+    if (adam && !(guard && guard[UMI_GUARD_SKIP] != 0.0)) {                                   // torch.optim.Adam: step += 1; bias corrections in double, then rounded
         const double t = h->adam_t + 1.0;
         h->adam_t = t;
         const double bc1 = 1.0 - pow(h->beta1, t), bc2 = 1.0 - pow(h->beta2, t);
@@ -297,7 +450,7 @@ extern "C" size_t umi_optim_hyper_bytes(void) { return sizeof(Hyper); }
 
 extern "C" int umi_optim_hyper_pre(void* hyper, int adam, umi_stream_t stream) {
     if (!hyper || ((uintptr_t)hyper & 7)) return UMI_ERR_BADARG;
-    hipLaunchKernelGGL(hyper_pre_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, (Hyper*)hyper, adam);
+    hipLaunchKernelGGL(hyper_pre_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, (Hyper*)hyper, adam, (const double*)nullptr);
     UMI_LAUNCH_CHECK();
     return UMI_OK;
 }
@@ -327,6 +480,60 @@ extern "C" int umi_optim_adam_multi_dev(const void* descs, int n_desc, int total
                (const Hyper*)hyper};
     hipLaunchKernelGGL((optim_multi_kernel<true, AdamArgs>), dim3(total_blocks), dim3(256), 0, (hipStream_t)stream,
                        (const umi_optim_desc*)descs, n_desc, a);
+    UMI_LAUNCH_CHECK();
+    return UMI_OK;
+}
+
+// ---- guarded step (include/unetmi.h) ------------------------------------------------------------------------------------------
+extern "C" size_t umi_grad_guard_ws_bytes(int total_blocks) {
+    return total_blocks > 0 ? (size_t)total_blocks * 2 * sizeof(double) : 0;
+}
+
+extern "C" int umi_grad_norm_partials(const void* descs, int n_desc, int total_blocks, int block_offset, void* ws,
+                                      size_t ws_bytes, umi_stream_t stream) {
+    if (!descs || !ws || ((uintptr_t)ws & 15) || n_desc <= 0 || total_blocks <= 0 || block_offset < 0) return UMI_ERR_BADARG;
+    if ((long)block_offset + total_blocks > 0x7fffffffL) return UMI_ERR_BADARG;
+    if (ws_bytes < umi_grad_guard_ws_bytes(block_offset + total_blocks)) return UMI_ERR_WORKSPACE;
+    hipLaunchKernelGGL(grad_norm_partials_kernel, dim3(total_blocks), dim3(256), 0, (hipStream_t)stream,
+                       (const umi_optim_desc*)descs, n_desc, block_offset, (double*)ws);
+    UMI_LAUNCH_CHECK();
+    return UMI_OK;
+}
+
+extern "C" int umi_grad_guard_finalize(const void* ws, int total_blocks, double* state, umi_stream_t stream) {
+    if (!ws || !state || ((uintptr_t)ws & 15) || ((uintptr_t)state & 7) || total_blocks <= 0) return UMI_ERR_BADARG;
+    hipLaunchKernelGGL(grad_guard_finalize_kernel, dim3(1), dim3(FIN_THREADS), 0, (hipStream_t)stream, (const double*)ws, total_blocks,
+                       state);
+    UMI_LAUNCH_CHECK();
+    return UMI_OK;
+}
+
+extern "C" int umi_optim_hyper_pre_guarded(void* hyper, int adam, const double* guard, umi_stream_t stream) {
+    if (!hyper || !guard || (((uintptr_t)hyper | (uintptr_t)guard) & 7)) return UMI_ERR_BADARG;
+    hipLaunchKernelGGL(hyper_pre_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, (Hyper*)hyper, adam, guard);
+    UMI_LAUNCH_CHECK();
+    return UMI_OK;
+}
+
+extern "C" int umi_optim_sgd_multi_guarded(const void* descs, int n_desc, int total_blocks, const void* hyper, double lr,
+                                           double momentum, double dampening, double weight_decay, int nesterov,
+                                           int first_step, const double* guard, umi_stream_t stream) {
+    if (!descs || !guard || ((uintptr_t)guard & 7) || n_desc <= 0 || total_blocks <= 0 || dampening != 0.0) return UMI_ERR_BADARG;
+    SgdArgs a{(float)lr, (float)momentum, 1.f, (float)weight_decay, nesterov, first_step, (const Hyper*)hyper};
+    hipLaunchKernelGGL((optim_multi_guarded_kernel<false, SgdArgs>), dim3(total_blocks), dim3(256), 0, (hipStream_t)stream,
+                       (const umi_optim_desc*)descs, n_desc, a, guard);
+    UMI_LAUNCH_CHECK();
+    return UMI_OK;
+}
+
+extern "C" int umi_optim_adam_multi_guarded(const void* descs, int n_desc, int total_blocks, const void* hyper,
+                                            double step_size, double beta1, double beta2, double bc2_sqrt, double eps,
+                                            double weight_decay, const double* guard, umi_stream_t stream) {
+    if (!descs || !guard || ((uintptr_t)guard & 7) || n_desc <= 0 || total_blocks <= 0) return UMI_ERR_BADARG;
+    AdamArgs a{(float)step_size, (float)(1.0 - beta1), (float)beta2, (float)(1.0 - beta2), (float)bc2_sqrt, (float)eps,
+               (float)weight_decay, (const Hyper*)hyper};
+    hipLaunchKernelGGL((optim_multi_guarded_kernel<true, AdamArgs>), dim3(total_blocks), dim3(256), 0, (hipStream_t)stream,
+                       (const umi_optim_desc*)descs, n_desc, a, guard);
     UMI_LAUNCH_CHECK();
     return UMI_OK;
 }

@@ -8,7 +8,8 @@ into channel slices of one buffer and the concat `Act` just stacks the `tx` rows
 The backward pass is hand-written (no torch autograd inside the graph): every op
 pushes a closure on the tape; `Tape.backward` replays them in reverse.  Gradients of
 activations are NHWC in the compute dtype and carry the static loss scale (fp16 mode);
-parameter gradients are produced in fp32, unscaled, in the parameter's own layout.
+parameter gradients are produced in fp32, unscaled, in the parameter's own layout (with `dyn_scale` set -- a
+umi.optim.GradGuard attached to the model -- they carry that dynamic factor, which the guarded optimizer step removes).
 
 Reference semantics implemented here: Model.py:7-26 (DoubleConv), :29-47 (Down),
 :50-83 (Up), :86-92 (OutConv); BatchNorm2d train/eval behaviour as torch.nn.
@@ -92,6 +93,9 @@ class Tape:
         self._inputs = []
         self.conv3x3_flags = 0            # compute_dtype "fp32_mfma": lib.CONV_F32_MFMA, OR-ed into the 3x3 convolutions' calls
         self.conv1x1_flags = 0            # "fp32_mfma_gemm": lib.CONV_F32_MFMA_1X1, OR-ed into the pointwise convolutions' calls
+        self.dyn_scale = None             # 0-dim float64 DEVICE tensor d (umi.optim.GradGuard.attach): the seed gradient is multiplied
+                                          # by loss_scale * d, parameter gradients leave the tape carrying d (`inv` undoes
+                                          # only the static scale) and the guarded optimizer step divides it out
 
     # ---- helpers -----------------------------------------------------------------------
     def alloc(self, N, H, W, C, dtype=None, zero=False, device=None):
@@ -598,10 +602,16 @@ class Tape:
     def seed_grad_nchw(self, a: Act, g_nchw: torch.Tensor):
         N, C, H, W = g_nchw.shape
         g = g_nchw.permute(0, 2, 3, 1)
-        if self.loss_scale != 1.0:
+        if self.dyn_scale is not None:
+            g = g * self._dyn_factor()
+        elif self.loss_scale != 1.0:
             g = g * self.loss_scale
         a.grad = torch.empty((N, H, W, C), dtype=self.dtype, device=g_nchw.device)
         a.grad.copy_(g)
+
+    def _dyn_factor(self):
+        """loss_scale * d as an fp32 device scalar: a device-tensor multiply, so that a captured step reads the current d."""
+        return (self.dyn_scale * self.loss_scale).to(torch.float32)
 
     def backward(self):
         for step in reversed(self.steps):
@@ -618,7 +628,9 @@ class Tape:
         if a.grad is None:
             return None
         g = a.grad.permute(0, 3, 1, 2).float()
-        if self.loss_scale != 1.0:
+        if self.dyn_scale is not None:
+            g = g / self._dyn_factor()
+        elif self.loss_scale != 1.0:
             g = g / self.loss_scale
         return g.contiguous()
 

@@ -7,6 +7,9 @@ schedule) work unchanged.  `step()` updates every parameter of a group with ONE 
 (umi_optim_sgd_multi / umi_optim_adam_multi) that follows torch's operation order, instead of torch's 4-10 foreach
 launches per group.
 
+`GradGuard` + `optimizer.grad_guard(guard)`: a non-finite check that skips the step, global gradient-norm clipping and a
+dynamic loss scale, decided on the device inside the step (so a captured HIP graph keeps deciding).
+
 Parameters must live on the MI355X; there is no CPU path here (the CPU oracle uses torch.optim itself).
 """
 import math
@@ -91,6 +94,181 @@ def _table(tabs, key, cap, rows, also=()):
 
 
 _HYPER = np.dtype(L.STRUCTS["umi_optim_hyper"])
+
+
+# the guard block of include/unetmi.h: UMI_GUARD_LEN doubles, GUARD["SCALE"] etc. = the UMI_GUARD_* slot indices
+GUARD_LEN = L.UMI_GUARD_LEN
+GUARD = {k[len("UMI_GUARD_"):]: v for k, v in L.ENUMS.items() if k.startswith("UMI_GUARD_") and k != "UMI_GUARD_LEN"}
+
+
+def guard_update_numpy(state, S, K):
+    """The arithmetic of umi_grad_guard_finalize in float64: `state` (the UMI_GUARD_LEN doubles of a guard block) after a step
+    whose gradients have the sum of squares S and K non-finite elements.  Returns a new array."""
+    st = np.array(state, dtype=np.float64)
+    d = st[GUARD["SCALE"]]
+    with np.errstate(all="ignore"):
+        norm = np.sqrt(np.float64(S)) / d
+    st[GUARD["NORM"]], st[GUARD["NONFINITE"]] = norm, K
+    skip = K > 0
+    st[GUARD["SKIP"]] = 1.0 if skip else 0.0
+    if not skip:
+        clip = np.float64(1.0)
+        if st[GUARD["MAX_NORM"]] > 0:
+            r = st[GUARD["MAX_NORM"]] / (norm + 1e-6)
+            clip = r if r < 1.0 else np.float64(1.0)
+        st[GUARD["COEF"]] = clip / d
+        st[GUARD["CLIPPED"]] += clip < 1.0
+    else:
+        st[GUARD["COEF"]] = 0.0
+        st[GUARD["SKIPPED"]] += 1
+    st[GUARD["STEPS"]] += 1
+    if st[GUARD["GROWTH_INTERVAL"]] > 0:                        # torch.amp.GradScaler.update
+        if skip:
+            d = max(d * st[GUARD["BACKOFF"]], st[GUARD["MIN_SCALE"]])
+            st[GUARD["STREAK"]] = 0
+        else:
+            st[GUARD["STREAK"]] += 1
+            if st[GUARD["STREAK"]] >= st[GUARD["GROWTH_INTERVAL"]]:
+                d = min(d * st[GUARD["GROWTH"]], st[GUARD["MAX_SCALE"]])
+                st[GUARD["STREAK"]] = 0
+        st[GUARD["SCALE"]] = d
+    return st
+
+
+class GradGuard:
+    """Device-side guard of the optimizer step (include/unetmi.h, "Guarded optimizer step").
+
+        guard = GradGuard(max_norm=1.0, dynamic_scale=True, init_scale=2.0 ** 8)
+        optimizer.grad_guard(guard)            # umi.optim.SGD / Adam; before any HIP-graph capture
+        guard.attach(model)                    # only needed for a loss scale other than 1: the model's tape applies it
+
+    Every `optimizer.step()` then makes one extra pass over all gradients of all param groups (sum of squares in float64 and a
+    count of inf / NaN), and one small kernel decides: a step with a non-finite gradient is SKIPPED (parameters, momentum /
+    Adam moments and Adam's step count keep their bits; the learning-rate schedule still advances: it counts batches); otherwise
+    the gradients are clipped to the global L2 norm `max_norm` (as torch.nn.utils.clip_grad_norm_, error_if_nonfinite=False)
+    and the loss scale divided out.  Unlike torch's in-place clip, `p.grad` is NOT rewritten: the coefficient is applied as the
+    update kernel reads the gradient, so `p.grad` after the step still holds what the backward pass produced (times the
+    dynamic scale, if one is attached).
+
+    dynamic_scale=True follows torch.amp.GradScaler: the factor d (initially init_scale) is multiplied by backoff_factor after
+    a skipped step and by growth_factor after growth_interval clean steps in a row, within [min_scale, max_scale].  It rides on
+    top of the static per-shape loss scale of fp16 mode (umi.graph.default_loss_scale): `attach(model)` hands the model's tape
+    a device view of d, the tape multiplies the seed gradient by it, parameter gradients leave the tape carrying it, and the
+    update removes it.  With dynamic_scale=False d stays at init_scale.
+
+    Under umi.ddp the check runs in step(), i.e. after grad_sync: every rank sees the same reduced gradients and takes the same
+    decisions, without any extra communication.
+
+    `read()` synchronises once and returns
+        norm, nonfinite   of the LAST step: global gradient norm (loss scale divided out; inf / nan as computed) and the number of
+                          non-finite gradient elements
+        scale             the factor the NEXT backward pass will use
+        steps, skipped, clipped   running totals since the guard was created."""
+
+    def __init__(self, max_norm=None, dynamic_scale=False, init_scale=1.0, growth_interval=2000, growth_factor=2.0,
+                 backoff_factor=0.5, min_scale=2.0 ** -24, max_scale=2.0 ** 24):
+        if max_norm is not None and not max_norm > 0:
+            raise ValueError("GradGuard: max_norm must be positive (None: no clipping)")
+        if not (init_scale > 0 and math.isfinite(init_scale)):
+            raise ValueError("GradGuard: init_scale must be positive and finite")
+        if dynamic_scale and not (growth_interval >= 1 and growth_factor > 1.0 and 0.0 < backoff_factor < 1.0
+                                  and 0.0 < min_scale <= max_scale):
+            raise ValueError("GradGuard: need growth_interval >= 1, growth_factor > 1, 0 < backoff_factor < 1, "
+                             "0 < min_scale <= max_scale")
+        st = np.zeros(GUARD_LEN, dtype=np.float64)
+        st[GUARD["SCALE"]], st[GUARD["COEF"]] = init_scale, 1.0 / init_scale
+        st[GUARD["MAX_NORM"]] = 0.0 if max_norm is None else float(max_norm)
+        st[GUARD["GROWTH_INTERVAL"]] = float(growth_interval) if dynamic_scale else 0.0
+        st[GUARD["GROWTH"]], st[GUARD["BACKOFF"]] = growth_factor, backoff_factor
+        st[GUARD["MIN_SCALE"]], st[GUARD["MAX_SCALE"]] = min_scale, max_scale
+        self.initial = st
+        self.state, self._host, self._ws = None, None, None
+
+    def _device_state(self):
+        """The device block, filled once (umi_table_upload from a pinned copy of the initial values)."""
+        if self.state is None:
+            if torch.cuda.is_current_stream_capturing():
+                raise RuntimeError("umi.optim.GradGuard: first use inside a HIP-graph capture; run a warm-up step first")
+            self._host = torch.empty(GUARD_LEN, dtype=torch.float64).pin_memory()
+            self._host.numpy()[:] = self.initial
+            self.state = torch.empty(GUARD_LEN, dtype=torch.float64, device="cuda")
+            L.call("umi_table_upload", self._host.data_ptr(), self.state.data_ptr(), GUARD_LEN * 8, ops._stream())
+            torch.cuda.current_stream().synchronize()
+        return self.state
+
+    def _workspace(self, total_blocks):
+        """Partials workspace for `total_blocks` rows; allocated outside any capture (the eager warm-up step), like _Table._ensure."""
+        need = L.fn("umi_grad_guard_ws_bytes")(total_blocks)
+        if self._ws is None or self._ws.numel() * 8 < need:
+            if torch.cuda.is_current_stream_capturing():
+                raise RuntimeError("umi.optim.GradGuard: the partials workspace must be allocated before a HIP-graph capture; "
+                                   "run a warm-up step first (umi.graphs.GraphedStep does)")
+            self._ws = torch.empty(max(need // 8, 2048), dtype=torch.float64, device="cuda")
+        return self._ws
+
+    def attach(self, model):
+        """Hands `model` the dynamic loss-scale factor: tapes built for it from now on multiply the seed gradient by
+        (static loss scale) * d and divide input gradients by the same value.  Call before the first step and before any capture."""
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("umi.optim.GradGuard: attach() cannot run inside a HIP-graph capture")
+        model._umi_dyn_scale = self._device_state()[GUARD["SCALE"]]
+        return self
+
+    def read(self):
+        st = self.initial if self.state is None else self.state.cpu().numpy()
+        return dict(norm=float(st[GUARD["NORM"]]), nonfinite=int(st[GUARD["NONFINITE"]]), skipped=int(st[GUARD["SKIPPED"]]),
+                    clipped=int(st[GUARD["CLIPPED"]]), steps=int(st[GUARD["STEPS"]]), scale=float(st[GUARD["SCALE"]]))
+
+
+class _Guarded:
+    """Mixin: the guarded form of step() (see GradGuard)."""
+
+    def grad_guard(self, guard):
+        """Attach a GradGuard (None detaches).  Must happen before this optimizer's step is captured into a HIP graph: the
+        captured launches are the unguarded ones."""
+        captured = any(t.captured for t in self.__dict__.get("_umi_tables", {}).values())
+        if captured or (torch.cuda.is_available() and torch.cuda.is_current_stream_capturing()):
+            raise RuntimeError("umi.optim: grad_guard() after (or inside) a HIP-graph capture of this optimizer's step; attach "
+                               "the guard before the GraphedStep is built")
+        if guard is not None:
+            if not isinstance(guard, GradGuard):
+                raise TypeError("umi.optim: grad_guard() takes a GradGuard")
+            if any(float(g.get("dampening", 0.0)) != 0.0 for g in self.param_groups):
+                raise ValueError("umi.optim: a GradGuard needs dampening == 0 (a skipped first step cannot reproduce "
+                                 "buf = clone(grad))")
+        self._umi_guard = guard
+        return self
+
+    @property
+    def guard(self):
+        return self.__dict__.get("_umi_guard")
+
+    def _guarded_step(self, groups):
+        """groups: [(gi, tables, launch)], tables = [(ptr, n_desc, blocks, tag)], launch(table, guard_ptr) issues the update of
+        one table.  One partials pass per table into disjoint rows, ONE finalize (the norm is global over all param groups, as
+        in torch.nn.utils.clip_grad_norm_), then per group: guarded hyper_pre, guarded updates, poly rule."""
+        total = sum(t[2] for _, tables, _ in groups for t in tables)
+        if total == 0:
+            return
+        guard = self._umi_guard
+        st = guard._device_state().data_ptr()
+        ws = guard._workspace(total)
+        stream, off = ops._stream(), 0
+        for _, tables, _ in groups:
+            for ptr, n, blocks, _ in tables:
+                L.call("umi_grad_norm_partials", ptr, n, blocks, off, ws.data_ptr(), ws.numel() * 8, stream)
+                off += blocks
+        L.call("umi_grad_guard_finalize", ws.data_ptr(), total, st, stream)
+        hyper = self.device_hyper
+        for gi, tables, launch in groups:
+            if not tables:
+                continue
+            if hyper is not None:
+                L.call("umi_optim_hyper_pre_guarded", hyper[gi][0].data_ptr(), int("betas" in self.param_groups[gi]), st, stream)
+            for table in tables:
+                launch(table, st)
+            if hyper is not None and self._umi_poly:
+                L.call("umi_optim_hyper_poly", hyper[gi][0].data_ptr(), stream)
 
 
 class _DeviceHyper:
@@ -190,7 +368,7 @@ def _check(p):
         raise RuntimeError("umi.optim: parameters must be contiguous")
 
 
-class SGD(_DeviceHyper, torch.optim.SGD):
+class SGD(_DeviceHyper, _Guarded, torch.optim.SGD):
     """torch.optim.SGD(lr, momentum, dampening, weight_decay, nesterov) with a single-launch step."""
 
     @torch.no_grad()
@@ -199,6 +377,7 @@ class SGD(_DeviceHyper, torch.optim.SGD):
         if closure is not None:
             with torch.enable_grad():
                 loss = closure()
+        guarded = [] if self.guard is not None else None
         for gi, group in enumerate(self.param_groups):
             if group.get("maximize") or group.get("differentiable"):
                 raise NotImplementedError("umi.optim.SGD: maximize / differentiable are not supported")
@@ -222,6 +401,19 @@ class SGD(_DeviceHyper, torch.optim.SGD):
             tabs = self.__dict__.setdefault("_umi_tables", {})
             cap = torch.cuda.is_current_stream_capturing()       # a captured table-upload node re-reads its own staging buffers
             hyper = self.device_hyper
+            if guarded is not None:
+                if float(group["dampening"]) != 0.0:
+                    raise ValueError("umi.optim.SGD: a GradGuard needs dampening == 0")
+                tables = [_table(tabs, (gi, first), cap, rr, also=((gi, False),)) + (first,) for first, rr in rows.items() if rr]
+
+                def launch(table, st, group=group, mom=mom, hp=hyper[gi][0].data_ptr() if hyper is not None else None):
+                    ptr, n, blocks, first = table
+                    L.call("umi_optim_sgd_multi_guarded", ptr, n, blocks, hp, float(group["lr"]), mom, 0.0,
+                           float(group["weight_decay"]), int(bool(group["nesterov"])), int(first), st, ops._stream())
+                guarded.append((gi, tables, launch))
+                for p, _ in touched:
+                    _bump(p)
+                continue
             if hyper is not None:
                 L.call("umi_optim_hyper_pre", hyper[gi][0].data_ptr(), 0, ops._stream())
             for first, rr in rows.items():
@@ -240,10 +432,12 @@ class SGD(_DeviceHyper, torch.optim.SGD):
                 L.call("umi_optim_hyper_poly", hyper[gi][0].data_ptr(), ops._stream())
             for p, _ in touched:
                 _bump(p)
+        if guarded:
+            self._guarded_step(guarded)
         return loss
 
 
-class Adam(_DeviceHyper, torch.optim.Adam):
+class Adam(_DeviceHyper, _Guarded, torch.optim.Adam):
     """torch.optim.Adam(lr, betas, eps, weight_decay) (L2 weight decay, no amsgrad) with a single-launch step."""
 
     @torch.no_grad()
@@ -252,6 +446,11 @@ class Adam(_DeviceHyper, torch.optim.Adam):
         if closure is not None:
             with torch.enable_grad():
                 loss = closure()
+        guarded = [] if self.guard is not None else None
+        if guarded is not None and self.device_hyper is None:
+            # the host cannot know whether a step was skipped: Adam's step count has to advance on the device
+            raise RuntimeError("umi.optim.Adam: a guarded step needs the device-side step count; call "
+                               "optimizer.device_schedule() first (umi.graphs.GraphedStep(optimizers=[...]) does)")
         for gi, group in enumerate(self.param_groups):
             if group.get("amsgrad") or group.get("maximize") or group.get("differentiable") or group.get("capturable"):
                 raise NotImplementedError("umi.optim.Adam: amsgrad / maximize / differentiable / capturable are not supported")
@@ -288,6 +487,17 @@ class Adam(_DeviceHyper, torch.optim.Adam):
                                                   st["exp_avg_sq"].data_ptr(), p.numel()))
                 touched.append((p, g))
             tabs = self.__dict__.setdefault("_umi_tables", {})
+            if guarded is not None:
+                tables = [_table(tabs, (gi, slot), cap, rr) + (slot,) for slot, (t, rr) in enumerate(sorted(by_step.items()))]
+
+                def launch(table, st, group=group, b1=b1, b2=b2, hp=hyper[gi][0].data_ptr()):
+                    ptr, n, blocks, _ = table
+                    L.call("umi_optim_adam_multi_guarded", ptr, n, blocks, hp, 0.0, b1, b2, 1.0, float(group["eps"]),
+                           float(group["weight_decay"]), st, ops._stream())
+                guarded.append((gi, tables, launch))
+                for p, _ in touched:
+                    _bump(p)
+                continue
             if hyper is not None and touched:
                 L.call("umi_optim_hyper_pre", hyper[gi][0].data_ptr(), 1, ops._stream())
             for slot, (t, rr) in enumerate(sorted(by_step.items())):
@@ -304,4 +514,6 @@ class Adam(_DeviceHyper, torch.optim.Adam):
                 L.call("umi_optim_hyper_poly", hyper[gi][0].data_ptr(), ops._stream())
             for p, _ in touched:
                 _bump(p)
+        if guarded:
+            self._guarded_step(guarded)
         return loss
