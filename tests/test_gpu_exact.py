@@ -250,6 +250,84 @@ def test_maxpool_with_transform_is_exact_on_integer_data():
     assert torch.equal(da.float().cpu()[unique], act.grad.permute(0, 2, 3, 1)[unique])
 
 
+def _pool_case(case):
+    """Integer data with distinct values inside every 2 x 2 window (odd last row / column: values that no window reads), a
+    transform with integer effect, and F.max_pool2d with its autograd on the CPU: (x, t, act, pooled, dpool, dact)."""
+    N, H, W, C = case
+    Ho, Wo = H // 2, W // 2
+    g = torch.Generator().manual_seed(sum(case))
+    base = torch.stack([torch.randperm(4, generator=g) for _ in range(N * Ho * Wo * C)]).float()
+    x = _ints((N, H, W, C), 1, 4, g)
+    x[:, :2 * Ho, :2 * Wo] = base.view(N, Ho, Wo, C, 2, 2).permute(0, 1, 4, 2, 5, 3).reshape(N, 2 * Ho, 2 * Wo, C) + 1.0
+    t = torch.zeros(C, 4)
+    t[:, 1] = torch.tensor([1.0, 2.0])[torch.randint(0, 2, (C,), generator=g)]
+    t[:, 2] = _ints((C,), -2, 0, g)
+    act = _apply(x, t).permute(0, 3, 1, 2).requires_grad_(True)
+    ref = F.max_pool2d(act, 2)
+    dp = _ints((N, Ho, Wo, C), -3, 3, g)
+    ref.backward(dp.permute(0, 3, 1, 2))
+    return x, t, act.detach(), ref.detach().permute(0, 2, 3, 1), dp, act.grad.permute(0, 2, 3, 1)
+
+
+# N, H, W, C: odd H and / or W (the vector backward declines: pool2_bwd_kernel<half_t> covers the tail); 24 channels: the
+# vector forward declines too
+POOL_ODD_CASES = [(2, 13, 21, 64), (1, 12, 21, 64), (2, 13, 20, 128), (1, 5, 7, 1024), (2, 9, 11, 24)]
+
+
+@pytest.mark.parametrize("sliced", [False, True])
+@pytest.mark.parametrize("case", POOL_ODD_CASES)
+def test_maxpool_on_odd_sizes_is_exact_on_integer_data(case, sliced):
+    """fp16 MaxPool2d(2) where H or W is odd (floor: the last row / column belongs to no window).  Forward equal; backward
+    with accumulate=False into a NaN-filled `da` equal where the max is unique and exactly 0 on the odd tail; backward with
+    accumulate=True into integer `da`: the sum, and the tail unchanged.  sliced: `x` and `da` are channel slices of a wider
+    NaN-filled buffer whose foreign columns must stay NaN."""
+    lib, ops = _gpu()
+    N, H, W, C = case
+    Ho, Wo = H // 2, W // 2
+    x, t, act, ref, dp, dact = _pool_case(case)
+    assert (H | W) & 1 and torch.equal(dact[:, 2 * Ho:], torch.zeros(N, H - 2 * Ho, W, C)) \
+        and torch.equal(dact[:, :, 2 * Wo:], torch.zeros(N, H, W - 2 * Wo, C))
+
+    def home(v):
+        """`v` on the device in fp16: its own tensor, or channels [8, 8 + C) of a NaN-filled buffer 16 channels wider."""
+        if not sliced:
+            return None, v.half().to(DEV)
+        buf = torch.full((N, H, W, C + 16), float("nan"), device=DEV, dtype=torch.float16)
+        buf[..., 8:8 + C] = v.half().to(DEV)
+        return buf, buf[..., 8:8 + C]
+
+    def foreign_untouched(buf):
+        return buf is None or (bool(torch.isnan(buf[..., :8]).all()) and bool(torch.isnan(buf[..., 8 + C:]).all()))
+    xbuf, xd = home(x)
+    td, dpd = t.to(DEV), dp.half().to(DEV)
+    y = torch.full((N, Ho, Wo, C), float("nan"), device=DEV, dtype=torch.float16)
+    ops.pool2_fwd(xd, td, y)
+    assert torch.equal(y.float().cpu(), ref)
+    # windows whose activated values tie at 0 (ReLU clipped) route the gradient by convention: compare where the max is unique
+    a4 = act[:, :, :2 * Ho, :2 * Wo].reshape(N, C, Ho, 2, Wo, 2)
+    uniq = ((a4 == a4.amax((3, 5), keepdim=True)).sum((3, 5), keepdim=True) == 1).expand_as(a4).reshape(N, C, 2 * Ho, 2 * Wo)
+    unique = torch.ones(N, H, W, C, dtype=torch.bool)                   # (the tail is compared everywhere)
+    unique[:, :2 * Ho, :2 * Wo] = uniq.permute(0, 2, 3, 1)
+    assert unique.float().mean().item() > 0.5
+    dabuf, da = home(torch.full((N, H, W, C), float("nan")))
+    ops.pool2_bwd(dpd, xd, td, da, False)
+    got = da.float().cpu()
+    assert torch.equal(got[unique], dact[unique])
+    assert torch.equal(got[:, 2 * Ho:], torch.zeros(N, H - 2 * Ho, W, C))
+    assert torch.equal(got[:, :, 2 * Wo:], torch.zeros(N, H, W - 2 * Wo, C))
+    assert bool(torch.isfinite(got).all()) and foreign_untouched(dabuf) and foreign_untouched(xbuf)
+    # the sum of a window's four gradients is the pooled gradient wherever the max falls
+    assert torch.equal(got[:, :2 * Ho, :2 * Wo].reshape(N, Ho, 2, Wo, 2, C).sum((2, 4)), dp)
+    prior = _ints((N, H, W, C), -5, 5, torch.Generator().manual_seed(1 + sum(case)))
+    dabuf, da = home(prior)
+    ops.pool2_bwd(dpd, xd, td, da, True)
+    got = da.float().cpu()
+    assert torch.equal(got[unique], (prior + dact)[unique])
+    assert torch.equal(got[:, 2 * Ho:], prior[:, 2 * Ho:]) and torch.equal(got[:, :, 2 * Wo:], prior[:, :, 2 * Wo:])
+    assert torch.equal((got - prior)[:, :2 * Ho, :2 * Wo].reshape(N, Ho, 2, Wo, 2, C).sum((2, 4)), dp)
+    assert foreign_untouched(dabuf)
+
+
 @pytest.mark.parametrize("R,stride,pad,Ci,Co,H,W", [(3, 2, 1, 64, 128, 11, 13), (1, 2, 0, 128, 64, 11, 13), (3, 2, 1, 256, 256, 28, 28),
                                                    (1, 1, 0, 1024, 256, 14, 14), (7, 2, 3, 64, 64, 20, 17)])
 def test_strided_convs_are_exact_on_integer_data(R, stride, pad, Ci, Co, H, W):

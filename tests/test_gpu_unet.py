@@ -240,12 +240,18 @@ def test_unet_fp16_feat64_benchmark_widths(cin, ncls):
         absolute 0.5 for the worst tensor / 0.25 for the median (measured: median 0.16 against a floor of 0.12).
     The measured values of one such run are committed as profiles/r02_fp16_feat64_parity.json."""
     _need_gpu()
+    _check_fp16_feat64(str(cin), str(ncls))
+
+
+def _check_fp16_feat64(*args):
+    """Run tools/check_fp16_feat64.py as a child with UMI_TRACE_GENERIC=1 and apply the bars of
+    test_unet_fp16_feat64_benchmark_widths to what it measured."""
     import json
     import subprocess
     import sys
     repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, UMI_TRACE_GENERIC="1")
-    r = subprocess.run([sys.executable, os.path.join(repo, "tools", "check_fp16_feat64.py"), str(cin), str(ncls)],
+    r = subprocess.run([sys.executable, os.path.join(repo, "tools", "check_fp16_feat64.py"), *args],
                        capture_output=True, text=True, timeout=900, env=env)
     assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-2000:])
     assert "[umi generic" not in r.stderr, [l for l in r.stderr.splitlines() if "[umi generic" in l][:8]
@@ -259,6 +265,25 @@ def test_unet_fp16_feat64_benchmark_widths(cin, ncls):
     assert gq["median"] < 1.5 * fl["median"] + 0.01 and gq["worst"] < 2.0 * fl["worst"] + 0.02, (gq, fl)
     assert gq["median"] < 0.25 and gq["worst"] < 0.5, gq
     assert m["grad_cosine_vs_fp32_oracle"]["worst"] > 0.9, m["grad_cosine_vs_fp32_oracle"]
+    return m
+
+
+@pytest.mark.parametrize("model,cin,ncls,batch,height,width", [("unet", 1, 2, 2, 70, 90), ("unet", 3, 4, 1, 44, 72),
+                                                               ("multitask", 1, 2, 2, 70, 90)])
+def test_unet_fp16_feat64_ragged_sizes(model, cin, ncls, batch, height, width):
+    """The same bars, unchanged, at sizes that are no multiple of 16 and for UNet_multitask at width 64: floor in every pool2
+    (70 x 90 -> 35 x 45 -> 17 x 22 -> 8 x 11 -> 4 x 5; 44 x 72 -> ... -> 11 x 18 -> 5 x 9 -> 2 x 4), the zero-filled pad and
+    offset scatter of conv_transpose2x2 at three decoder levels, the sliced gradient in its backward, the odd-tail
+    pool2_bwd_kernel<half_t> the vector kernel declines, batch 1, and two decoders on one skip.  No 3x3, transposed or
+    pointwise convolution and no weight gradient may fall to the generic kernels at these sizes either.
+    The oracle alone stays inside the absolute caps here (CPU, seed 70; floor median / worst): unet 70 x 90 0.124 / 0.161,
+    unet 44 x 72 batch 1 0.132 / 0.176 (fp16 oracle 7.5e-3 of scale from the fp32 one, 87 % of pixels clear), multitask
+    70 x 90 0.110 / 0.177."""
+    _need_gpu()
+    m = _check_fp16_feat64(str(cin), str(ncls), "--model", model, "--batch", str(batch), "--height", str(height),
+                           "--width", str(width), "--seed", "70")
+    assert f"{batch}x{cin}x{height}x{width}" in m["model"] and ("multitask" in m["model"]) == (model == "multitask")
+    assert m["pixels"] == batch * height * width * (2 if model == "multitask" else 1)
 
 
 def test_unet_config1_scale_fp32(golden_dir):
