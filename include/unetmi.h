@@ -51,13 +51,23 @@ enum { UMI_CONV_UPSAMPLE2 = 1,   /* ConvTranspose2d(k=2,s=2): tap t=(dy,dx) scat
                                       bias, none of the flags above, Ci % 8 == Co % 8 == 0 and ldx % 4 == ldy % 4 == 0 (weight
                                       gradient: no transform on dy either); IGNORED otherwise: the call, umi_conv_fwd_plan and
                                       umi_conv_wgrad_ws_bytes then answer exactly as without it */
-       UMI_CONV_F32_MFMA_1X1 = 32  /* opt-in, independent of the flag above: an fp32 pointwise conv / nn.Linear (R = S = 1, stride 1,
+       UMI_CONV_F32_MFMA_1X1 = 32, /* opt-in, independent of the flag above: an fp32 pointwise conv / nn.Linear (R = S = 1, stride 1,
                                       pad 0: Y[M, Co] = X[M, Ci] . W[Ci, Co], M = N * H * W; forward, data gradient, weight gradient)
                                       runs on the same instruction (csrc/gemm_mfma_f32.hip).  Taken when in and out are UMI_F32, none
                                       of the flags 1, 2, 4, 8 is set, Ci % 8 == Co % 8 == 0 and ldx % 4 == ldy % 4 == 0 (weight
                                       gradient: lddy % 4 == 0 and no transform on dy); a bias, an input transform and statistics are
                                       all allowed.  IGNORED otherwise, like the flag above: UMI_CONV_F32_MFMA on a 1x1 call and this
-                                      flag on a 3x3 call are ignored, both together name the kernel that fits the geometry */ };
+                                      flag on a 3x3 call are ignored, both together name the kernel that fits the geometry */
+       UMI_CONV_F32_MFMA_2X2 = 64  /* opt-in, independent of the two flags above: an fp32 nn.ConvTranspose2d(k=2, s=2) runs on the same
+                                      instruction (csrc/convt_mfma_f32.hip) in its three calls: umi_conv_fwd with UMI_CONV_UPSAMPLE2
+                                      (the forward: input transform, bias, off_h / off_w inside a larger out_H x out_W image and
+                                      ldy > Co all allowed), umi_conv_fwd without it on R = S = 2, stride 2, pad 0 with H == 2 Ho and
+                                      W == 2 Wo (the data gradient), and umi_conv_wgrad(_deferred) of that geometry (a transform on
+                                      either side allowed).  Taken when in and out are UMI_F32, R = S = 2, stride 2, pad 0, none of the
+                                      flags 2, 4, 8 is set, Ci % 8 == Co % 8 == 0, ldx % 4 == ldy % 4 == 0 (weight gradient:
+                                      lddy % 4 == 0) and x, y, the weights and the transforms (weight gradient: x, dy and the
+                                      transforms) are 16-byte aligned.  IGNORED otherwise, like the two flags above (a call with a
+                                      misaligned pointer runs as without the flag, whatever the plan said: both read one packing).  These kernels write no BatchNorm statistics (see umi_conv_fwd_plan) */ };
 
 int umi_version(void);
 const char* umi_arch(void);          /* "gfx950" */
@@ -120,6 +130,10 @@ int umi_linear_fused(const void* x, int ldx, const void* wp8, const float* bias,
  * With UMI_CONV_F32_MFMA_1X1, where that flag's conditions hold, the fp32 matrix-core pointwise kernel is named: *layout = 0
  * (umi_pack_kn's [1][Ci][Co]; the transposed pack for a data gradient) and *stat_rows = one row per 128 consecutive output rows,
  * ceil(N * H * W / 128); a plan that names it is never followed by UMI_ERR_UNSUPPORTED from umi_conv_fwd either.
+ * With UMI_CONV_F32_MFMA_2X2, where that flag's conditions hold, the fp32 matrix-core ConvTranspose2d kernels are named: *layout = 0
+ * (umi_pack_kn's [4][Cin][Cout] for the forward, [4][Cout][Cin] for the data gradient) and *stat_rows = 0.  They write no statistics
+ * (no BatchNorm follows a ConvTranspose2d and the fp32 data gradient fuses no reduction), so here the sentence above does NOT hold:
+ * like the fp16 tap-gather kernel, umi_conv_fwd with `stat_part` returns UMI_ERR_UNSUPPORTED on this path and writes nothing.
  * *stat_rows = rows of `stat_part` the call will write.  UMI_ERR_UNSUPPORTED: UMI_CONV_ACCUMULATE off the pointwise kernel. */
 int umi_conv_fwd_plan(int N, int H, int W, int Ci, int Co, int R, int S, int stride, int pad,
                       int ldx, int ldy, int in_dtype, int out_dtype, int flags, int has_bias,
@@ -219,7 +233,17 @@ int umi_bn_bwd_from_partials(const float* part, int rows, int C, float* sum_dz, 
  * own way).  The split rule of the pointwise fp32 matrix-core kernel: the M = N * Ho * Wo rows are cut into chunks of 32; with
  * tiles = ceil(Ci / TI) * ceil(Co / TJ), TI = 64 if Ci <= 64 else 128 and TJ likewise from Co, it wants ceil(512 / tiles) splits
  * but at most ceil(chunks / 4), at least 1; a split is ceil(chunks / wanted) consecutive chunks, splits = ceil(chunks / that), and
- * the workspace is splits slabs of Ci * Co fp32 values, [split][1][Ci][Co]. */
+ * the workspace is splits slabs of Ci * Co fp32 values, [split][1][Ci][Co].  UMI_CONV_F32_MFMA_2X2 is a flag of this call too (the
+ * ConvTranspose2d weight gradient: x = d(up) [N, 2 Ho, 2 Wo, Ci], dy = the ConvT's input [N, Ho, Wo, Co], txb its transform).  Its
+ * split rule is the same with the four taps counted as tiles: the M = N * Ho * Wo pixels are cut into chunks of 32; with tiles =
+ * 4 * ceil(Ci / TI) * ceil(Co / TJ), TI and TJ as above, it wants ceil(512 / tiles) splits but at most ceil(chunks / 4), at least 1;
+ * a split is ceil(chunks / wanted) consecutive chunks, splits = ceil(chunks / that), and the workspace is splits slabs of
+ * 4 * Ci * Co fp32 values, [split][4][Ci][Co]; umi_conv_wgrad_ws_bytes gives the larger of that and the flag-less answer.
+ * Summation orders of the three 2x2 kernels (every output ONE fmaf chain, no atomics, identical inputs give identical bits):
+ *   forward        k ascending over 0 .. Cin - 1, the bias added once after the chain;
+ *   data gradient  taps ascending (t = 2 r + s), channels ascending inside a tap, one accumulator across the four taps;
+ *   weight grad.   pixels ascending in (n, ho, wo) order inside a split, one accumulator per (tap, ci, co) and split, then the
+ *                  splits' slabs summed by the shared reduction in its fixed order. */
 size_t umi_conv_wgrad_ws_bytes(int N, int Ho, int Wo, int Ci, int Co, int R, int S, int dtype, int flags);
 int umi_conv_wgrad(const void* x, int ldx, const void* txa, const void* dy, int lddy, const void* txb,
                    float* dW, long s_co, long s_ci, long s_t, float out_scale,

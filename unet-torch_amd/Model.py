@@ -13,9 +13,10 @@ Build-specific, keyword-only extras (never positional, so reference call sites a
 unaffected): `compute_dtype` = "fp16" (fp16 storage + fp32 accumulate, loss-scaled
 gradients; default, env UMI_COMPUTE_DTYPE), "fp32" (parity mode), "fp32_mfma" ("fp32" in storage,
 state and every kernel but the 3x3 convolutions, which run on the fp32-input matrix-core kernels),
-"fp32_mfma_gemm" ("fp32_mfma" plus the pointwise convolutions and linears on the fp32 matrix-core GEMM) or "fp32_mfma_attn"
+"fp32_mfma_gemm" ("fp32_mfma" plus the pointwise convolutions and linears on the fp32 matrix-core GEMM), "fp32_mfma_attn"
 ("fp32_mfma_gemm" plus TransUNet's softmax attention on the fp32 matrix-core kernels; the same as "fp32_mfma_gemm" for the
-U-Net family, which has no attention).
+U-Net family, which has no attention) or "fp32_mfma_convt" ("fp32_mfma_attn" plus the 2x2 transposed convolutions of `Up` and the
+attention gates on the fp32 matrix-core kernels; the same as "fp32_mfma_attn" for TransUNet, which has no transposed convolution).
 
 There is no CPU path here: inputs must live on the MI355X ("cuda" in PyTorch-ROCm naming).
 """
@@ -33,24 +34,34 @@ def _resolve_dtype(compute_dtype):
         return name
     table = {"fp16": torch.float16, "float16": torch.float16, "half": torch.float16,
              "fp32": torch.float32, "float32": torch.float32, "fp32_mfma": torch.float32, "fp32_mfma_gemm": torch.float32,
-             "fp32_mfma_attn": torch.float32}
+             "fp32_mfma_attn": torch.float32, "fp32_mfma_convt": torch.float32}
     if name not in table:
-        raise ValueError(f"compute_dtype must be fp16, fp32, fp32_mfma, fp32_mfma_gemm or fp32_mfma_attn, got {name!r}")
+        raise ValueError(f"compute_dtype must be fp16, fp32, fp32_mfma, fp32_mfma_gemm, fp32_mfma_attn or fp32_mfma_convt, "
+                         f"got {name!r}")
     return table[name]
 
 
 def _resolve_conv_flags(compute_dtype):
     """(3x3 flag, pointwise flag) the tape adds to its convolution calls: "fp32_mfma" opts the 3x3 convolutions into libunetmi's
-    fp32 matrix-core kernels, "fp32_mfma_gemm" and "fp32_mfma_attn" the pointwise convolutions and linears as well."""
+    fp32 matrix-core kernels, "fp32_mfma_gemm", "fp32_mfma_attn" and "fp32_mfma_convt" the pointwise convolutions and linears as
+    well."""
     name = compute_dtype or os.environ.get("UMI_COMPUTE_DTYPE", "fp16")
-    gemm = name in ("fp32_mfma_gemm", "fp32_mfma_attn")
+    gemm = name in ("fp32_mfma_gemm", "fp32_mfma_attn", "fp32_mfma_convt")
     return G.L.CONV_F32_MFMA if gemm or name == "fp32_mfma" else 0, G.L.CONV_F32_MFMA_1X1 if gemm else 0
 
 
 def _resolve_attn_flags(compute_dtype):
-    """The flag a TransUNet tape adds to its attention calls: "fp32_mfma_attn" opts them into the fp32 matrix-core kernels."""
+    """The flag a TransUNet tape adds to its attention calls: "fp32_mfma_attn" (and "fp32_mfma_convt", which includes it) opts
+    them into the fp32 matrix-core kernels."""
     name = compute_dtype or os.environ.get("UMI_COMPUTE_DTYPE", "fp16")
-    return G.L.UMI_ATTN_F32_MFMA if name == "fp32_mfma_attn" else 0
+    return G.L.UMI_ATTN_F32_MFMA if name in ("fp32_mfma_attn", "fp32_mfma_convt") else 0
+
+
+def _resolve_convt_flags(compute_dtype):
+    """The flag a tape adds to the three calls of a ConvTranspose2d(2, 2): "fp32_mfma_convt" opts them into the fp32 matrix-core
+    kernels."""
+    name = compute_dtype or os.environ.get("UMI_COMPUTE_DTYPE", "fp16")
+    return G.L.CONV_F32_MFMA_2X2 if name == "fp32_mfma_convt" else 0
 
 
 class _TapeFunction(torch.autograd.Function):
@@ -115,6 +126,7 @@ def _run_tape(module, inputs, build, tape_cls=None, dtype=None):
                         grad_sink=getattr(module, "_umi_grad_sink", None) if record else None,
                         pack_cache=G.pack_cache_of(module), seed=seed, seed_dev=seed_dev)
         tape.conv3x3_flags, tape.conv1x1_flags = _resolve_conv_flags(getattr(module, "_compute_dtype", None))
+        tape.convt_flags = _resolve_convt_flags(getattr(module, "_compute_dtype", None))
         tape.dyn_scale = getattr(module, "_umi_dyn_scale", None)          # umi.optim.GradGuard.attach(module)
         if hasattr(tape, "attn_flags"):              # TUTape: the standalone Attention / Block forwards
             tape.attn_flags = _resolve_attn_flags(getattr(module, "_compute_dtype", None))

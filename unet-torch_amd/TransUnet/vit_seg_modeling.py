@@ -9,7 +9,8 @@ embedding + position embedding, 12 pre-LN transformer blocks (softmax attention,
 
 Keyword-only extra: `compute_dtype` ("fp16" default / "fp32" parity mode / "fp32_mfma_gemm": "fp32" with the linears, the 1x1 and
 the 3x3 / stride-1 convolutions on the fp32 matrix-core kernels / "fp32_mfma_attn": "fp32_mfma_gemm" with the softmax attention
-on the fp32 matrix-core kernels as well (head dimension 64; ignored at any other); env UMI_COMPUTE_DTYPE).
+on the fp32 matrix-core kernels as well (head dimension 64; ignored at any other) / "fp32_mfma_convt": the same as
+"fp32_mfma_attn" here, there is no transposed convolution in this network; env UMI_COMPUTE_DTYPE).
 `VisionTransformerMultitask` / `VisionTransformerMultitaskEM` (reference :444-638): the same encoder with 2 / 6 CUP decoders
 and heads on one tape.
 Not supported: `vis=True` (attention maps are never materialised), the non-hybrid (pure ViT patch conv) variant.

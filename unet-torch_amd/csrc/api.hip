@@ -74,6 +74,7 @@ extern "C" int umi_conv_fwd_plan(int N, int H, int W, int Ci, int Co, int R, int
     if (stat_rows)
         *stat_rows = path == FWD_MFMA3X3_F32 ? umi_conv3x3_f32_mfma_stat_rows(N, H, W)
                      : path == FWD_GEMM_F32 ? umi_gemm_f32_mfma_stat_rows((long)N * H * W)
+                     : path == FWD_CONVT_F32 ? 0                      // it writes no statistics
                      : path == FWD_MFMA3X3 ? umi_conv3x3_mfma_stat_rows(N, H, W, Co)
                      : path == FWD_STEM  ? umi_stem_stat_rows(N, H, W)
                      : path == FWD_HEAD  ? umi_head_stat_rows((long)N * H * W, Ci)
@@ -190,7 +191,7 @@ extern "C" int umi_conv_fwd(const void* x, int ldx, const void* tx, const void* 
     ConvFwdProblem p = fwd_problem(N, H, W, Ci, Co, R, S, stride, pad, Ho, Wo, ldx, ldy, in_dtype, out_dtype, flags,
                                    tx != nullptr, bias != nullptr, stat_part != nullptr);
     const ConvFwdPath path = umi_conv_fwd_path(p);
-    if (path != FWD_MFMA3X3_F32 && path != FWD_GEMM_F32) p.flags = flags &= ~UMI_CONV_F32_OPT_IN;      // refused there: the call runs without the flags
+    if (path != FWD_MFMA3X3_F32 && path != FWD_GEMM_F32 && path != FWD_CONVT_F32) p.flags = flags &= ~UMI_CONV_F32_OPT_IN;      // refused there: the call runs without the flags
     // only the pointwise / tap-gather MFMA kernel adds into y
     if ((flags & UMI_CONV_ACCUMULATE) && (stat_part || path != FWD_MFMA1X1)) return UMI_ERR_UNSUPPORTED;
     if (flags & UMI_CONV_DGRAD_STRIDED) {
@@ -208,6 +209,13 @@ extern "C" int umi_conv_fwd(const void* x, int ldx, const void* tx, const void* 
     switch (path) {
     case FWD_MFMA3X3_F32: return umi_conv3x3_f32_mfma(p, x, tx, wp, y, stat_part, s);
     case FWD_GEMM_F32: return umi_gemm_f32_mfma(p, x, tx, wp, bias, y, stat_part, s);
+    case FWD_CONVT_F32:
+        // 16-byte alignment is one of this flag's conditions, and the flag-less kernel reads the same weight packing: ignored here too
+        if (((uintptr_t)x | (uintptr_t)y | (uintptr_t)wp | (uintptr_t)tx) & 15)
+            return umi_conv_fwd(x, ldx, tx, wp, bias, y, ldy, stat_part, N, H, W, Ci, Co, R, S, stride, pad, Ho, Wo, off_h, off_w, out_H,
+                                out_W, in_dtype, out_dtype, flags & ~UMI_CONV_F32_OPT_IN, stream);
+        if (stat_part) return UMI_ERR_UNSUPPORTED;      // no BatchNorm follows a ConvTranspose2d, its data gradient fuses no reduction
+        return umi_convt_f32_mfma(p, x, tx, wp, bias, y, off_h, off_w, out_H, out_W, s);
     case FWD_MFMA3X3:
         // the caller packed the weights for this path (umi_conv_fwd_plan said layout 1): misalignment is an error,
         // not a reason to silently reinterpret them
@@ -236,9 +244,10 @@ static WgradProblem wgrad_problem(int N, int H, int W, int Ci, int Co, int R, in
 extern "C" size_t umi_conv_wgrad_ws_bytes(int N, int Ho, int Wo, int Ci, int Co, int R, int S, int dtype, int flags) {
     // the call picks its path from more arguments than this query has: size for whichever path could need most
     WgradProblem p = wgrad_problem(N, 0, 0, Ci, Co, R, S, 0, 0, Ho, Wo, 0, 0, dtype, flags, false, false);
-    const size_t f32_mfma = umi_wgrad3x3_f32_mfma_ws_bound(p), f32_gemm = umi_wgrad_gemm_f32_mfma_ws_bound(p);
+    const size_t f32_mfma = umi_wgrad3x3_f32_mfma_ws_bound(p), f32_gemm = umi_wgrad_gemm_f32_mfma_ws_bound(p),
+                 f32_convt = umi_wgrad_convt_f32_mfma_ws_bound(p);
     p.flags &= ~UMI_CONV_F32_OPT_IN;                     // the call may still find the flags refused (strides, a transform on dy)
-    const size_t bounds[] = {f32_mfma, f32_gemm, umi_wgrad3x3_mfma_ws_bound(p), umi_wgrad1x1_mfma_ws_bound(p), umi_wgradT_mfma_ws_bound(p),
+    const size_t bounds[] = {f32_mfma, f32_gemm, f32_convt, umi_wgrad3x3_mfma_ws_bound(p), umi_wgrad1x1_mfma_ws_bound(p), umi_wgradT_mfma_ws_bound(p),
                              umi_wgrad_gather_mfma_ws_bound(p), umi_stem_wgrad_ws_bound(p), umi_head_wgrad_ws_bound(p),
                              umi_root_wgrad_ws_bound(p), umi_head3_wgrad_ws_bound(p), umi_conv_wgrad_generic_ws_bound(p)};
     size_t most = 0;
@@ -250,12 +259,18 @@ extern "C" size_t umi_conv_wgrad_ws_bytes(int N, int Ho, int Wo, int Ci, int Co,
 static int conv_wgrad(const WgradProblem& asked, WgradPath path, const void* x, const void* txa, const void* dy, const void* txb,
                       const WgradOut& o, hipStream_t s) {
     WgradProblem p = asked;
-    if (path != WGRAD_MFMA3X3_F32 && path != WGRAD_GEMM_F32) p.flags &= ~UMI_CONV_F32_OPT_IN;      // refused there: the call runs without the flags
+    if (path != WGRAD_MFMA3X3_F32 && path != WGRAD_GEMM_F32 && path != WGRAD_CONVT_F32) p.flags &= ~UMI_CONV_F32_OPT_IN;      // refused there: the call runs without the flags
     if (!x || !dy || !o.dW || !o.ws || p.N <= 0 || p.H <= 0 || p.W <= 0 || p.Ci <= 0 || p.Co <= 0 || p.ldx < p.Ci || p.lddy < p.Co)
         return UMI_ERR_BADARG;
     switch (path) {
     case WGRAD_MFMA3X3_F32: return umi_wgrad3x3_f32_mfma(p, x, txa, dy, o, s);
     case WGRAD_GEMM_F32: return umi_wgrad_gemm_f32_mfma(p, x, txa, dy, o, s);
+    case WGRAD_CONVT_F32:
+        if (((uintptr_t)x | (uintptr_t)dy | (uintptr_t)txa | (uintptr_t)txb) & 15) {      // not 16-byte aligned: the flag is ignored
+            p.flags &= ~UMI_CONV_F32_OPT_IN;
+            return conv_wgrad(p, umi_conv_wgrad_path(p), x, txa, dy, txb, o, s);
+        }
+        return umi_wgrad_convt_f32_mfma(p, x, txa, dy, txb, o, s);
     case WGRAD_MFMA3X3: return umi_wgrad3x3_mfma(p, x, txa, dy, o, s);
     case WGRAD_MFMA1X1: return umi_wgrad1x1_mfma(p, x, txa, dy, o, s);
     case WGRAD_T: return umi_wgradT_mfma(p, x, dy, txb, o, s);

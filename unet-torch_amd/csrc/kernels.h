@@ -9,12 +9,13 @@ struct ConvFwdProblem {
     bool has_tx, has_bias, has_stats;      // an input transform / a bias / BatchNorm statistics of the output are asked for
 };
 // in cascade order: umi_conv_fwd_path returns the first whose predicate accepts the problem
-enum ConvFwdPath { FWD_MFMA3X3_F32, FWD_GEMM_F32, FWD_MFMA3X3, FWD_MFMA1X1, FWD_STEM, FWD_HEAD, FWD_SMALLK, FWD_ROOT, FWD_HEAD3, FWD_GENERIC };
+enum ConvFwdPath { FWD_MFMA3X3_F32, FWD_GEMM_F32, FWD_CONVT_F32, FWD_MFMA3X3, FWD_MFMA1X1, FWD_STEM, FWD_HEAD, FWD_SMALLK, FWD_ROOT, FWD_HEAD3, FWD_GENERIC };
 
 // A predicate carries every refusal that depends on the problem alone.  The launcher it guards may then fail only on pointer
 // alignment (UMI_ERR_BADARG), a workspace below its own bound (UMI_ERR_WORKSPACE), a HIP error or an env switch.
 bool umi_conv3x3_f32_mfma_ok(const ConvFwdProblem& p);  // conv_mfma_f32.hip: only under UMI_CONV_F32_MFMA
 bool umi_gemm_f32_mfma_ok(const ConvFwdProblem& p);     // gemm_mfma_f32.hip: only under UMI_CONV_F32_MFMA_1X1
+bool umi_convt_f32_mfma_ok(const ConvFwdProblem& p);    // convt_mfma_f32.hip: only under UMI_CONV_F32_MFMA_2X2
 bool umi_conv3x3_mfma_ok(const ConvFwdProblem& p);      // conv_mfma.hip
 bool umi_conv1x1_mfma_ok(const ConvFwdProblem& p);      // conv1x1_mfma.hip
 bool umi_stem_fwd_ok(const ConvFwdProblem& p);          // stem_head.hip
@@ -27,14 +28,16 @@ bool umi_head3_fwd_ok(const ConvFwdProblem& p);
 // (the host packs the weights for them before it knows the pointers); the pointwise one writes no statistics, so a caller
 // that wants them gets UMI_ERR_UNSUPPORTED from umi_conv_fwd.  The narrow kernels below the head write none either and
 // give way to the generic kernel when statistics are asked for.
-// UMI_CONV_F32_MFMA (3x3) and UMI_CONV_F32_MFMA_1X1 (pointwise) ask for the fp32 matrix-core kernels, each predicate reads its own
-// flag, and a flag is IGNORED where its kernel refuses the problem: the rest of the cascade then sees the problem without
-// either, so every answer is the flag-less one.
-constexpr int UMI_CONV_F32_OPT_IN = UMI_CONV_F32_MFMA | UMI_CONV_F32_MFMA_1X1;
+// UMI_CONV_F32_MFMA (3x3), UMI_CONV_F32_MFMA_1X1 (pointwise) and UMI_CONV_F32_MFMA_2X2 (ConvTranspose2d(2, 2) and its gradients) ask
+// for the fp32 matrix-core kernels, each predicate reads its own flag, and a flag is IGNORED where its kernel refuses the problem:
+// the rest of the cascade then sees the problem without any of them, so every answer is the flag-less one.  The 2x2 kernels write
+// no statistics: like the tap-gather kernel's, their plan stands and a call that asks for them gets UMI_ERR_UNSUPPORTED.
+constexpr int UMI_CONV_F32_OPT_IN = UMI_CONV_F32_MFMA | UMI_CONV_F32_MFMA_1X1 | UMI_CONV_F32_MFMA_2X2;
 inline ConvFwdPath umi_conv_fwd_path(const ConvFwdProblem& p) {
     if (p.flags & UMI_CONV_F32_OPT_IN) {
         if (umi_conv3x3_f32_mfma_ok(p)) return FWD_MFMA3X3_F32;
         if (umi_gemm_f32_mfma_ok(p)) return FWD_GEMM_F32;
+        if (umi_convt_f32_mfma_ok(p)) return FWD_CONVT_F32;
         ConvFwdProblem q = p;
         q.flags &= ~UMI_CONV_F32_OPT_IN;
         return umi_conv_fwd_path(q);
@@ -68,6 +71,9 @@ int umi_conv3x3_f32_mfma(const ConvFwdProblem& p, const void* x, const void* tx,
 int umi_gemm_f32_mfma_stat_rows(long M);                                                                      // gemm_mfma_f32.hip
 int umi_gemm_f32_mfma(const ConvFwdProblem& p, const void* x, const void* tx, const void* wp, const float* bias, void* y,
                       float* stat_part, hipStream_t s);
+// UMI_CONV_UPSAMPLE2 in p.flags: the ConvT forward (scatter at off_h / off_w of the out_H x out_W image); else its data gradient
+int umi_convt_f32_mfma(const ConvFwdProblem& p, const void* x, const void* tx, const void* wp, const float* bias, void* y,
+                       int off_h, int off_w, int out_H, int out_W, hipStream_t s);                          // convt_mfma_f32.hip
 int umi_conv3x3_mfma_stat_rows(int N, int H, int W, int Co);                                                  // conv_mfma.hip
 int umi_conv3x3_mfma(const ConvFwdProblem& p, const void* x, const void* tx, const void* wp8, void* y, float* stat_part,
                      hipStream_t s);
@@ -108,10 +114,11 @@ struct WgradOut {
 // stage 3 of the BatchNorm(+ReLU) backward formed while the gradient operand is staged (umi_conv_wgrad_bnapply): `dy` is then
 // the gradient of the ACTIVATED output
 struct WgradBnApply { const void* y; int ldy; const void* tx_bn; const float *rstd, *sum_dz, *sum_dzx; void* dz; int lddz; };
-enum WgradPath { WGRAD_MFMA3X3_F32, WGRAD_GEMM_F32, WGRAD_MFMA3X3, WGRAD_MFMA1X1, WGRAD_T, WGRAD_GATHER, WGRAD_STEM, WGRAD_HEAD, WGRAD_ROOT, WGRAD_HEAD3, WGRAD_GENERIC };
+enum WgradPath { WGRAD_MFMA3X3_F32, WGRAD_GEMM_F32, WGRAD_CONVT_F32, WGRAD_MFMA3X3, WGRAD_MFMA1X1, WGRAD_T, WGRAD_GATHER, WGRAD_STEM, WGRAD_HEAD, WGRAD_ROOT, WGRAD_HEAD3, WGRAD_GENERIC };
 
 bool umi_wgrad3x3_f32_mfma_ok(const WgradProblem& p);   // conv_mfma_f32.hip: only under UMI_CONV_F32_MFMA
 bool umi_wgrad_gemm_f32_mfma_ok(const WgradProblem& p); // gemm_mfma_f32.hip: only under UMI_CONV_F32_MFMA_1X1
+bool umi_wgrad_convt_f32_mfma_ok(const WgradProblem& p); // convt_mfma_f32.hip: only under UMI_CONV_F32_MFMA_2X2
 bool umi_wgrad3x3_mfma_ok(const WgradProblem& p);       // wgrad_mfma.hip
 bool umi_wgrad1x1_mfma_ok(const WgradProblem& p);
 bool umi_wgradT_mfma_ok(const WgradProblem& p);
@@ -126,6 +133,7 @@ inline WgradPath umi_conv_wgrad_path(const WgradProblem& p) {
     if (p.flags & UMI_CONV_F32_OPT_IN) {                    // ignored where refused, as in umi_conv_fwd_path
         if (umi_wgrad3x3_f32_mfma_ok(p)) return WGRAD_MFMA3X3_F32;
         if (umi_wgrad_gemm_f32_mfma_ok(p)) return WGRAD_GEMM_F32;
+        if (umi_wgrad_convt_f32_mfma_ok(p)) return WGRAD_CONVT_F32;
         WgradProblem q = p;
         q.flags &= ~UMI_CONV_F32_OPT_IN;
         return umi_conv_wgrad_path(q);
@@ -145,6 +153,7 @@ inline WgradPath umi_conv_wgrad_path(const WgradProblem& p) {
 // field is unset): the most workspace the path could ask for over the problems it takes with those facts, 0 if it takes none.
 size_t umi_wgrad3x3_f32_mfma_ws_bound(const WgradProblem& p);      // 0 without UMI_CONV_F32_MFMA
 size_t umi_wgrad_gemm_f32_mfma_ws_bound(const WgradProblem& p);     // 0 without UMI_CONV_F32_MFMA_1X1
+size_t umi_wgrad_convt_f32_mfma_ws_bound(const WgradProblem& p);    // 0 without UMI_CONV_F32_MFMA_2X2
 size_t umi_wgrad3x3_mfma_ws_bound(const WgradProblem& p);
 size_t umi_wgrad1x1_mfma_ws_bound(const WgradProblem& p);
 size_t umi_wgradT_mfma_ws_bound(const WgradProblem& p);
@@ -158,6 +167,8 @@ size_t umi_conv_wgrad_generic_ws_bound(const WgradProblem& p);      // generic_k
 // launchers: partial slabs into o.ws, then umi_launch_wgrad_reduce
 int umi_wgrad3x3_f32_mfma(const WgradProblem& p, const void* x, const void* txa, const void* dy, const WgradOut& o, hipStream_t s);
 int umi_wgrad_gemm_f32_mfma(const WgradProblem& p, const void* x, const void* txa, const void* dy, const WgradOut& o, hipStream_t s);
+int umi_wgrad_convt_f32_mfma(const WgradProblem& p, const void* x, const void* txa, const void* dy, const void* txb,
+                             const WgradOut& o, hipStream_t s);
 int umi_wgrad3x3_mfma(const WgradProblem& p, const void* x, const void* txa, const void* dy, const WgradOut& o, hipStream_t s,
                       const WgradBnApply* bna = nullptr);
 int umi_wgrad1x1_mfma(const WgradProblem& p, const void* x, const void* txa, const void* dy, const WgradOut& o, hipStream_t s);

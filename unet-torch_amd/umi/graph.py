@@ -93,6 +93,7 @@ class Tape:
         self._inputs = []
         self.conv3x3_flags = 0            # compute_dtype "fp32_mfma": lib.CONV_F32_MFMA, OR-ed into the 3x3 convolutions' calls
         self.conv1x1_flags = 0            # "fp32_mfma_gemm": lib.CONV_F32_MFMA_1X1, OR-ed into the pointwise convolutions' calls
+        self.convt_flags = 0              # "fp32_mfma_convt": lib.CONV_F32_MFMA_2X2, OR-ed into the three calls of conv_transpose2x2
         self.dyn_scale = None             # 0-dim float64 DEVICE tensor d (umi.optim.GradGuard.attach): the seed gradient is multiplied
                                           # by loss_scale * d, parameter gradients leave the tape carrying d (`inv` undoes
                                           # only the static scale) and the guarded optimizer step divides it out
@@ -453,9 +454,12 @@ class Tape:
         if dY or dX:
             dest.zero_()
         wf = weight.detach().float()
+        # the opt-in fp32 matrix-core kernels, where the channel counts allow them at all (the library ignores the flag for any
+        # other reason it cannot take a call)
+        fk = self.convt_flags if Cin % 8 == 0 and Cout % 8 == 0 else 0
         ops.conv_fwd(a.raw, a.tx, self._packer("convT_fwd", weight, wf),
                      bias.detach().float() if bias is not None else None, dest, 2, 2, 2, 0,
-                     flags=L.CONV_UPSAMPLE2, up_offset=(oy, ox))
+                     flags=L.CONV_UPSAMPLE2 | fk, up_offset=(oy, ox))
         o = Act(dest, None)
         if self.record:
             def bwd():
@@ -480,7 +484,7 @@ class Tape:
                     self._set_pgrad(bias, gb)
                 # dW[ci][co][t] = sum_p act(a)[p][ci] * g[2p+t][co]: a wgrad with the roles of x and dy swapped
                 if not fused:
-                    ops.conv_wgrad(g, None, a.raw, a.tx, gw, Cout * 4, 4, 1, inv, 2, 2, 2, 0, defer=dlist)
+                    ops.conv_wgrad(g, None, a.raw, a.tx, gw, Cout * 4, 4, 1, inv, 2, 2, 2, 0, flags=fk, defer=dlist)
                 self._set_pgrad(weight, gw)
                 if _wants_grad(a):
                     tgt = self._accumulate_target(a, g, 2, 2, 2, 0)
@@ -499,7 +503,7 @@ class Tape:
                     if part is not None:
                         a.bn_part, a.bn_part_at = part, a.gives + 1
                     else:
-                        ops.conv_fwd(g, None, self._packer("convT_dgrad", weight, wf), None, dx, 2, 2, 2, 0)
+                        ops.conv_fwd(g, None, self._packer("convT_dgrad", weight, wf), None, dx, 2, 2, 2, 0, flags=fk)
                     self._give(a, dx)
             self.steps.append(bwd)
         return o
