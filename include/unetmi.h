@@ -420,6 +420,19 @@ int umi_attn_plan(int N, int heads, int D, int ld, int ldo, int ldd, int dtype, 
 int umi_bilinear2x(const void* x, int ldx, const void* tx, void* y, int ldy, int backward, int N, int H, int W, int C,
                    int dtype, umi_stream_t stream);   /* tx: consumer transform of x, forward only (nullable) */
 
+/* Patch gather of the pure-ViT variants (vit_seg_modeling.py:137-140: Conv2d(C, hidden, kernel_size=P, stride=P) on the image): the
+ * non-overlapping patches of a contiguous NCHW tensor x[B][C][H][W] as the token-major rows of that convolution's GEMM,
+ *   rows[(b*gh + ty)*gw + tx][(c*P + ky)*P + kx] = x[b][c][ty*P + ky][tx*P + kx],  gh = H / P, gw = W / P (integer division),
+ * M = B*gh*gw rows of K = C*P*P elements, row stride ld >= K (elements).  The column order is PyTorch's flattening of a
+ * [hidden][C][P][P] weight.  in_dtype -> out_dtype: any of UMI_F32 / UMI_F16 each; fp32 -> fp16 rounds to nearest even, equal
+ * types copy.  Image rows from gh*P and columns from gw*P on are never read; nothing outside rows[0:M][0:K] is written.  Any
+ * P >= 1, C >= 1; 64-bit addressing.  16-byte accesses when P, W and ld are multiples of 16 / sizeof(in) elements and both
+ * addresses are aligned to their access, element-wise otherwise with the same result.  No LDS, no atomics.
+ * UMI_ERR_BADARG (nothing launched): a null pointer, B, C, H, W or P <= 0, P > H or P > W (no patch), ld < K, an unknown dtype.
+ * UMI_ERR_UNSUPPORTED: C*P*P or H*W >= 2^31. */
+int umi_patch_rows(const void* x, int in_dtype, void* rows, long ld, int out_dtype, int B, int C, int H, int W, int P,
+                   umi_stream_t stream);
+
 /* Fused training loss 'dice_bce_mc' (reference loss.py:488-500, DiceLoss loss.py:215-251) on NCHW fp32 logits [N,C,HW],
  * C <= 8: 0.5 * CrossEntropy + 0.5 * mean_c(1 - (2*sum(p*t)+1e-5)/(sum(p*p)+sum(t*t)+1e-5)), p = softmax(logits).
  * target [N,HW] class indices; target_dtype 0 = int64, 1 = float32, 2 = uint8, 3 = int32.

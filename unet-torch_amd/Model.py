@@ -109,9 +109,10 @@ class _TapeFunction(torch.autograd.Function):
         return (None, None, None, *gin, *gpar)
 
 
-def _run_tape(module, inputs, build, tape_cls=None, dtype=None):
+def _run_tape(module, inputs, build, tape_cls=None, dtype=None, enter=None):
     """Run `build(tape, *input_acts) -> Act (or tuple of Acts)` for `module`; returns NCHW fp32 tensor(s).  `tape_cls`:
-    G.Tape (default) or umi.graph_tu.TUTape for the TransUNet blocks."""
+    G.Tape (default) or umi.graph_tu.TUTape for the TransUNet blocks.  `enter(tape, x, needs_grad) -> Act`: how an input enters
+    the tape (default: `tape.input_nchw`, the NHWC copy)."""
     params = [p for p in module.parameters()]
     dtype = dtype if dtype is not None else module._umi_dtype()
     N, _, H, W = inputs[0].shape
@@ -130,7 +131,8 @@ def _run_tape(module, inputs, build, tape_cls=None, dtype=None):
         tape.dyn_scale = getattr(module, "_umi_dyn_scale", None)          # umi.optim.GradGuard.attach(module)
         if hasattr(tape, "attn_flags"):              # TUTape: the standalone Attention / Block forwards
             tape.attn_flags = _resolve_attn_flags(getattr(module, "_compute_dtype", None))
-        acts = [tape.input_nchw(x, needs_grad=need) for x, need in zip(inputs, in_needs)]
+        acts = [enter(tape, x, need) if enter is not None else tape.input_nchw(x, needs_grad=need)
+                for x, need in zip(inputs, in_needs)]
         out_act = build(tape, *acts)
         tape.finish_forward()
 

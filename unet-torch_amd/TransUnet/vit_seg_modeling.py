@@ -2,8 +2,10 @@
 
 `VisionTransformer(config, img_size=224, num_classes=21843, zero_head=False, vis=False)` keeps the reference
 constructor (vit_seg_modeling.py:371), attribute tree (409 `state_dict` keys for R50-ViT-B_16) and construction order
-(same initial weights under the same seed).  `forward` emits the whole network -- hybrid ResNetV2 with skips, 1x1 patch
-embedding + position embedding, 12 pre-LN transformer blocks (softmax attention, exact-GELU MLP), CUP decoder
+(same initial weights under the same seed).  `forward` emits the whole network -- hybrid ResNetV2 with skips and a 1x1 patch
+embedding, or (pure ViT: `ViT-B_16`, `ViT-B_32`, `ViT-L_16`, `ViT-L_32` with `n_skip = 0`) the P x P / stride-P patch embedding
+straight on the image as a device patch gather in front of the linear path's GEMM, + position embedding, the pre-LN
+transformer blocks (softmax attention, exact-GELU MLP), CUP decoder
 (bilinear x2 align_corners, cat([x, skip]), conv+BN+ReLU x2) and the 3x3 segmentation head -- onto a libunetmi tape
 (umi/graph_tu.py) with a hand-written backward; nothing runs through torch.nn.
 
@@ -13,7 +15,7 @@ on the fp32 matrix-core kernels as well (head dimension 64; ignored at any other
 "fp32_mfma_attn" here, there is no transposed convolution in this network; env UMI_COMPUTE_DTYPE).
 `VisionTransformerMultitask` / `VisionTransformerMultitaskEM` (reference :444-638): the same encoder with 2 / 6 CUP decoders
 and heads on one tape.
-Not supported: `vis=True` (attention maps are never materialised), the non-hybrid (pure ViT patch conv) variant.
+Not supported: `vis=True` (attention maps are never materialised).
 """
 import copy
 import logging
@@ -102,14 +104,23 @@ class Mlp(nn.Module):
 
 
 class Embeddings(nn.Module):
-    """Hybrid ResNetV2 -> 1x1 patch conv + bias -> + position embedding -> dropout (reference :122-165)."""
+    """Hybrid ResNetV2 -> 1x1 patch conv + bias, or (no `patches.grid`: pure ViT) the P x P / stride-P patch conv + bias on the
+    image itself, -> + position embedding -> dropout (reference :122-165)."""
 
     def __init__(self, config, img_size, in_channels=3):
         super().__init__()
         self.config = config
         img_size = _pair(img_size)
         if config.patches.get("grid") is None:
-            raise NotImplementedError("only the hybrid (ResNet grid) TransUNet variant is on the MI355X hot path")
+            patch = _pair(config.patches["size"])
+            if patch[0] != patch[1] or patch[0] < 1:
+                raise NotImplementedError(f"patch size {patch}: the patch gather takes square patches")
+            self.hybrid = False                       # (no hybrid_model: no `hybrid_model.*` keys, reference :142-144)
+            self.patch_embeddings = Conv2d(in_channels=in_channels, out_channels=config.hidden_size, kernel_size=patch, stride=patch)
+            n_patches = (img_size[0] // patch[0]) * (img_size[1] // patch[1])
+            self.position_embeddings = nn.Parameter(torch.zeros(1, n_patches, config.hidden_size))
+            self.dropout = Dropout(config.transformer["dropout_rate"])
+            return
         grid = config.patches["grid"]
         patch = (img_size[0] // 16 // grid[0], img_size[1] // 16 // grid[1])
         if patch != (1, 1):
@@ -123,15 +134,16 @@ class Embeddings(nn.Module):
         self.dropout = Dropout(config.transformer["dropout_rate"])
 
     def forward(self, x):
-        """NCHW image -> (tokens [B, N, hidden], [skip features, deepest first]) (reference :154-165)."""
+        """NCHW image -> (tokens [B, N, hidden], [skip features, deepest first]; None for the pure ViT) (reference :154-165)."""
+        _check_tokens(self, x)
         if x.size()[1] == 1:
             x = x.repeat(1, 3, 1, 1)
 
         def build(t, a):
             h, skips = _build_embeddings(t, a, self)
             return (h,) + tuple(skips)
-        outs = _run_tape(self, [x], build, tape_cls=TUTape, dtype=_sub_dtype(self))
-        return _tok_out(outs[0]), list(outs[1:])
+        outs = _run_tape(self, [x], build, tape_cls=TUTape, dtype=_sub_dtype(self), enter=_image_entry(self))
+        return _tok_out(outs[0]), list(outs[1:]) if self.hybrid else None
 
 
 class Block(nn.Module):
@@ -193,8 +205,9 @@ class Transformer(nn.Module):
         self.encoder = Encoder(config, vis)
 
     def forward(self, input_ids):
-        """NCHW image -> (encoded tokens, [], skip features) (reference :253-256)."""
+        """NCHW image -> (encoded tokens, [], skip features; None for the pure ViT) (reference :253-256)."""
         x = input_ids
+        _check_tokens(self.embeddings, x)
         if x.size()[1] == 1:
             x = x.repeat(1, 3, 1, 1)
 
@@ -203,8 +216,8 @@ class Transformer(nn.Module):
             for blk in self.encoder.layer:
                 h = _build_block(t, h, blk)
             return (t.layer_norm(h, self.encoder.encoder_norm),) + tuple(skips)
-        outs = _run_tape(self, [x], build, tape_cls=TUTape, dtype=_sub_dtype(self))
-        return _tok_out(outs[0]), [], list(outs[1:])
+        outs = _run_tape(self, [x], build, tape_cls=TUTape, dtype=_sub_dtype(self), enter=_image_entry(self.embeddings))
+        return _tok_out(outs[0]), [], list(outs[1:]) if self.embeddings.hybrid else None
 
 
 class Conv2dReLU(nn.Sequential):
@@ -289,7 +302,36 @@ def _build_block(t, h, blk: Block, cfg=None):
     return _build_mlp(t, t.layer_norm(h, blk.ffn_norm), blk.ffn, residual=h)
 
 
+def _check_tokens(emb: Embeddings, x):
+    """Pure ViT: the input's token count must be the position embedding's, and a square number (the decoder folds the tokens
+    back into a sqrt(n) x sqrt(n) map, reference :356-359).  Host arithmetic only: raises before anything is launched."""
+    if emb.hybrid:
+        return
+    P = emb.patch_embeddings.kernel_size[0]
+    H, W = int(x.shape[2]), int(x.shape[3])
+    n, n_pos = (H // P) * (W // P), emb.position_embeddings.shape[1]
+    if n != n_pos:
+        raise ValueError(f"a {H}x{W} input has {n} patches of {P}x{P}, the position embedding holds {n_pos} tokens "
+                         f"(img_size of the constructor)")
+    if int(np.sqrt(n)) ** 2 != n:
+        raise ValueError(f"a {H}x{W} input has {n} patches of {P}x{P}: {n} is not a square number, the position embedding holds "
+                         f"{n_pos} tokens")
+
+
+def _image_entry(emb: Embeddings):
+    """How the image enters a tape (Model._run_tape's `enter`): as its NHWC copy for the hybrid (None: the default), as its patch
+    rows for the pure ViT (TUTape.patch_rows: no NHWC copy is made)."""
+    if emb.hybrid:
+        return None
+    return lambda t, x, need: t.patch_rows(x, emb.patch_embeddings.kernel_size[0])
+
+
 def _build_embeddings(t, a, emb: Embeddings):
+    """-> (tokens, skips) from the image as it entered the tape (_image_entry).  Pure ViT: `a` holds the patch rows; the patch
+    conv is a linear over K = 3 P P (+ bias) -> + position embedding -> dropout, no skips."""
+    if not emb.hybrid:
+        h = t.linear(a, emb.patch_embeddings.weight, emb.patch_embeddings.bias)
+        return t.dropout(t.add_position(h, emb.position_embeddings), emb.dropout.p), []
     feat, skips = build_resnet(t, a, emb.hybrid_model)
     h = t.map_to_tokens(t.conv1x1_bias(feat, emb.patch_embeddings))
     return t.dropout(t.add_position(h, emb.position_embeddings), emb.dropout.p), skips
@@ -341,6 +383,7 @@ class VisionTransformer(nn.Module):
         return _resolve_dtype(self._compute_dtype)
 
     def forward(self, x):
+        _check_tokens(self.transformer.embeddings, x)
         if x.size()[1] == 1:
             x = x.repeat(1, 3, 1, 1)                        # reference :387-388
         params = list(self.parameters())
@@ -360,8 +403,9 @@ class VisionTransformer(nn.Module):
             tape.conv3x3_flags, tape.conv1x1_flags = flags if flags[1] else (0, 0)       # "fp32_mfma" sets no flag on this tape
             tape.attn_flags = _resolve_attn_flags(self._compute_dtype)
             tape.dyn_scale = getattr(self, "_umi_dyn_scale", None)            # umi.optim.GradGuard.attach(self)
-            a = tape.input_nchw(x, needs_grad=False)
             emb = self.transformer.embeddings
+            enter = _image_entry(emb)                   # pure ViT: the image enters the tape as its patch rows, no NHWC copy
+            a = enter(tape, x, False) if enter is not None else tape.input_nchw(x, needs_grad=False)
             h, skips = _build_embeddings(tape, a, emb)
             gh = gw = int(np.sqrt(h.shape[2]))
             assert gh * gw == h.shape[2]
@@ -373,7 +417,7 @@ class VisionTransformer(nn.Module):
             h = tape.layer_norm(h, self.transformer.encoder.encoder_norm)
             outs = []
             for dname, hname in self.HEADS:             # every decoder reads the same tokens and skips: their gradients add up
-                y = _build_decoder(tape, h, skips, getattr(self, dname), gh, gw)
+                y = _build_decoder(tape, h, skips or None, getattr(self, dname), gh, gw)
                 head = getattr(self, hname)[0]
                 outs.append(tape.conv_bias(y, head.weight, head.bias, out_dtype=torch.float32, pad=head.padding[0]))
             tape.finish_forward()
@@ -385,8 +429,9 @@ class VisionTransformer(nn.Module):
         return _TapeFunction.apply(run, record, 1, x, *params)
 
     def load_from(self, weights):
-        """Load a JAX `.npz` ViT/R50 checkpoint (reference :394-441).  The reference's checkpoint file is not part of
-        its tree; this mapping is therefore exercised by shape only."""
+        """Load a JAX `.npz` ViT/R50 checkpoint (reference :394-441; a pure-ViT checkpoint has no ResNet keys and its
+        `embedding/kernel` is HWIO [P, P, 3, hidden]).  The reference's checkpoint file is not part of its tree; this mapping is
+        therefore exercised by shape only."""
         from scipy import ndimage
         with torch.no_grad():
             emb = self.transformer.embeddings
@@ -410,6 +455,8 @@ class VisionTransformer(nn.Module):
                 new.copy_(np2th(grid.reshape(1, gs_new * gs_new, -1)))
             for uname, unit in enc.layer.named_children():
                 unit.load_from(weights, n_block=uname)
+            if not emb.hybrid:                           # reference :432
+                return
             hm = emb.hybrid_model
             hm.root.conv.weight.copy_(np2th(weights["conv_root/kernel"], conv=True))
             hm.root.gn.weight.copy_(np2th(weights["gn_root/scale"]).view(-1))

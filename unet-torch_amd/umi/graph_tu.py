@@ -253,17 +253,20 @@ class TUTape(Tape):
     def linear(self, a: Act, weight, bias, _fused=None):
         """nn.Linear ([Co,Ci] weight) or a 1x1 Conv2d ([Co,Ci,1,1] weight) + bias on [B,1,N,Cin] tokens / NHWC maps.
         `_fused(out, packed_weights, bias32) -> bool` (linear_dropout): runs the forward GEMM itself, with an epilogue."""
-        Co, Ci = weight.shape[0], weight.shape[1]
+        Co = weight.shape[0]
+        Ci = weight.numel() // Co                        # the flattened fan-in: C * P * P of the pure ViT's [Co, C, P, P] patch weight
         N, H, W, Ca = a.shape
         assert Ca == Ci
         out = self.alloc(N, H, W, Co, device=a.raw.device)
         w4 = weight.detach().float().reshape(Co, Ci, 1, 1)
+        # a weight with taps is packed as its [Co, fan-in] matrix; the PARAMETER stays the key of the pack cache and of the sink
+        k_fwd, k_dgrad = ("linear_fwd", "linear_dgrad") if weight.dim() == 4 and weight.shape[1] != Ci else ("conv_fwd", "conv_dgrad")
         b32 = bias.detach().float() if bias is not None else None
         # (kernel-layout copies from the model's PackCache when `weight` is a parameter: MLP / out-projection / patch embedding)
-        if _fused is None or not _fused(out, self._packer("conv_fwd", weight, w4), b32):
+        if _fused is None or not _fused(out, self._packer(k_fwd, weight, w4), b32):
             if _fused is not None:
                 return None                             # the caller runs the unfused sequence
-            ops.conv_fwd(a.raw, a.tx, self._packer("conv_fwd", weight, w4), b32, out, 1, 1, 1, 0,
+            ops.conv_fwd(a.raw, a.tx, self._packer(k_fwd, weight, w4), b32, out, 1, 1, 1, 0,
                          flags=self._fk(1, 1, 1, 0, Ci, Co))
         o = Act(out, None)
         if self.record:
@@ -281,11 +284,29 @@ class TUTape(Tape):
                     self._set_pgrad(bias, gb)
                 if _wants_grad(a):
                     dx = self.alloc(N, H, W, Ci, device=out.device)
-                    ops.conv_fwd(o.grad, None, self._packer("conv_dgrad", weight, w4), None, dx, 1, 1, 1, 0,
+                    ops.conv_fwd(o.grad, None, self._packer(k_dgrad, weight, w4), None, dx, 1, 1, 1, 0,
                                  flags=self._fk(1, 1, 1, 0, Co, Ci))
                     self._give(a, dx)
             self.steps.append(bwd)
         return o
+
+    def patch_rows(self, x: torch.Tensor, P):
+        """Graph input of the pure ViT: the P x P patches of the contiguous NCHW image as [B, 1, gh * gw, C * P * P] tokens in the
+        compute dtype (umi_patch_rows; column order = the flattening of the [hidden, C, P, P] patch weight).  The image takes no
+        gradient."""
+        if not x.is_cuda:
+            raise RuntimeError("unet-torch_amd: the HIP path needs the input on device 'cuda' (MI355X); "
+                               "no CPU fallback exists in the product path")
+        if x.dtype not in (torch.float32, torch.float16):
+            x = x.float()
+        x = x.contiguous()
+        B, C, H, W = x.shape
+        n, K = (H // P) * (W // P), C * P * P
+        raw = self.alloc(B, 1, n, K, device=x.device)
+        ops_tu.patch_rows(x, P, raw.view(B * n, K))
+        a = Act(raw, None, needs_grad=False)
+        self._inputs.append(a)
+        return a
 
     def conv1x1_bias(self, a: Act, conv):
         """Patch embedding: Conv2d(k=1) + bias (vit_seg_modeling.py:145-148)."""

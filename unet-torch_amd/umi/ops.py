@@ -123,6 +123,8 @@ def _pack_args(kind, shape):
     """(T, K, N, st, sk, sn, flip_t) of the weight packings above."""
     if len(shape) == 2:                              # nn.Linear weight [Co, Ci] = a 1x1 convolution
         shape = (shape[0], shape[1], 1, 1)
+    if kind in ("linear_fwd", "linear_dgrad"):       # any weight as its [Co, fan-in] matrix (the patch embedding's [Co, C, P, P])
+        kind, shape = "conv" + kind[6:], (shape[0], int(np.prod(shape[1:])), 1, 1)
     if kind == "conv_fwd":
         Co, Ci, R, S = shape
         return R * S, Ci, Co, 1, R * S, Ci * R * S, 0
@@ -150,7 +152,9 @@ def pack_conv_dgrad_strided(w, dtype, k8=False):
 
 
 PACKERS = {"conv_fwd": pack_conv_fwd, "conv_dgrad": pack_conv_dgrad, "convT_fwd": pack_convT_fwd,
-           "convT_dgrad": pack_convT_dgrad, "conv_dgrad_strided": pack_conv_dgrad_strided}
+           "convT_dgrad": pack_convT_dgrad, "conv_dgrad_strided": pack_conv_dgrad_strided,
+           # (the uncached form receives the weight already flattened to [Co, fan-in, 1, 1])
+           "linear_fwd": pack_conv_fwd, "linear_dgrad": pack_conv_dgrad}
 
 
 class PackCache:

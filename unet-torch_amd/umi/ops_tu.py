@@ -2,7 +2,7 @@
 import torch
 
 from . import lib as L
-from .ops import _dt, _nhwc, _ptr, _stream, workspace, pack_kn
+from .ops import _dt, _need_cuda, _nhwc, _ptr, _stream, workspace, pack_kn
 
 
 def _rows(t):
@@ -201,6 +201,22 @@ def bilinear2x(x, y, backward=False, tx=None):
         N, H, W, C, ldx = _nhwc(x)
         ldy = _nhwc(y)[4]
     L.call("umi_bilinear2x", x.data_ptr(), ldx, _ptr(tx), y.data_ptr(), ldy, int(backward), N, H, W, C, _dt(x), _stream())
+
+
+def patch_rows(x, P, rows):
+    """rows[(b*gh + ty)*gw + tx, (c*P + ky)*P + kx] = x[b, c, ty*P + ky, tx*P + kx] (umi_patch_rows): the P x P patches of a
+    contiguous NCHW tensor as the token-major rows of the patch convolution's GEMM.  `rows`: [M, K] with contiguous columns
+    (any row stride >= K), fp32 or fp16; fp32 -> fp16 rounds to nearest even."""
+    if x.dim() != 4 or not x.is_contiguous():
+        raise ValueError(f"expected a contiguous NCHW tensor, got {tuple(x.shape)} / {x.stride()}")
+    B, C, H, W = x.shape
+    M, K = B * (H // P) * (W // P), C * P * P
+    if rows.dim() != 2 or tuple(rows.shape) != (M, K) or (K > 1 and rows.stride(1) != 1):
+        raise ValueError(f"expected rows [{M}, {K}] with contiguous columns, got {tuple(rows.shape)} / {rows.stride()}")
+    _need_cuda(x, rows)
+    L.call("umi_patch_rows", x.data_ptr(), _dt(x), rows.data_ptr(), rows.stride(0) if M > 1 else max(rows.stride(0), K), _dt(rows),
+           B, C, H, W, P, _stream())
+    return rows
 
 
 from .ops import pack_conv_dgrad_strided  # noqa: E402,F401  (kept under its old name)
