@@ -388,7 +388,10 @@ int umi_dropout_fused(const void* x, int ldx, void* y, int ldy, void* mask, int 
                       int dtype, const unsigned* seed_dev, const void* aux, int ldaux, int gelu, umi_stream_t stream);
 
 /* Multi-head softmax attention (vit_seg_modeling.py:73-91): q,k,v,o are [B, N, heads*D] token tensors (row stride ld),
- * head h = channels [h*D, (h+1)*D); softmax(q k^T / sqrt(D)) v.  lse/delta: [B*heads*N] fp32 scratch kept for backward. */
+ * head h = channels [h*D, (h+1)*D); softmax(q k^T / sqrt(D)) v.  lse/delta: [B*heads*N] fp32 scratch kept for backward.
+ * Three kernel families serve these calls (umi_attn_plan names the one a call takes): the VALU kernels (D = 16, 32, 64; fp32 and
+ * fp16), the fp16 matrix-core kernels (D = 64) and, opt-in, the fp32 matrix-core kernels (D = 64).  Dropout on the probabilities:
+ * umi_attn_fwd_dropout / umi_attn_bwd_dropout below, in all three. */
 int umi_attn_fwd(const void* q, const void* k, const void* v, int ld, void* o, int ldo, float* lse, int B, int N, int heads,
                  int D, int dtype, umi_stream_t stream);
 int umi_attn_bwd(const void* q, const void* k, const void* v, int ld, const void* o, const void* dO, int ldo,
@@ -414,6 +417,25 @@ int umi_attn_bwd_flags(const void* q, const void* k, const void* v, int ld, cons
  * unknown dtype or a null `kernel`; UMI_ERR_UNSUPPORTED where no kernel serves D (the VALU kernels know 16, 32 and 64). */
 int umi_attn_plan(int N, int heads, int D, int ld, int ldo, int ldd, int dtype, int flags, const void* q, const void* k,
                   const void* v, const void* o, int* kernel);
+/* Attention-probability dropout (reference vit_seg_modeling.py:78,86-88: nn.Dropout on the softmax probabilities), in every
+ * kernel family.  With P = softmax(q k^T / sqrt(D)), M the keep mask and Z = M / (1 - p):
+ *   forward : o = (P o Z) v.  lse is the undropped softmax's, bit for bit what the call without dropout stores: only the operand
+ *             of the P.v product is masked, and the final scale is 1 / (rowsum * (1 - p)).
+ *   backward: delta = rowsum(dO o o) (o already carries Z); dS = P o (Z o (dO v^T) - delta); dq = scale dS k; dk = scale dS^T q;
+ *             dv = (P o Z)^T dO.
+ * The mask is never stored: each of the three kernels of a family regenerates its bits, in registers, from umi_dropout's stream
+ * on the dense [B * heads * N, N] tensor of probabilities -- element e = ((b * heads + h) * N + i) * N + j in 64 bits (the high
+ * word enters as umi_dropout states), seed' = seed + seed_dev[0] * 0x9E3779B9, keep iff u >= p.  So a forward and its backward
+ * must be given the same (p, seed, *seed_dev); seed_dev (nullable) is read inside the kernels, a replayed graph draws fresh masks.
+ * The kernel is umi_attn_plan's: dropout never changes the selection (a call whose plan names 2 still never falls back), and
+ * D must be one the selected family knows (UMI_ERR_UNSUPPORTED otherwise).  0 <= p <= 1, UMI_ERR_BADARG otherwise (NaN
+ * included) before anything else is looked at; p == 0 IS umi_attn_fwd_flags / umi_attn_bwd_flags, bit for bit; p == 1 keeps
+ * nothing: o = 0, dq = dk = dv = 0, nothing non-finite.  No atomics, nothing allocated at launch, no static device state. */
+int umi_attn_fwd_dropout(const void* q, const void* k, const void* v, int ld, void* o, int ldo, float* lse, int B, int N, int heads,
+                         int D, int dtype, int flags, float p, unsigned seed, const unsigned* seed_dev, umi_stream_t stream);
+int umi_attn_bwd_dropout(const void* q, const void* k, const void* v, int ld, const void* o, const void* dO, int ldo,
+                         const float* lse, void* dq, void* dk, void* dv, int ldd, float* delta, int B, int N, int heads, int D,
+                         int dtype, int flags, float p, unsigned seed, const unsigned* seed_dev, umi_stream_t stream);
 
 /* UpsamplingBilinear2d(scale_factor=2), align_corners=True (vit_seg_modeling.py:307): forward x[N,H,W,C] -> y[N,2H,2W,C];
  * backward (x = dy [N,2H,2W,C]) -> y = dx [N,H,W,C] (deterministic gather form). */

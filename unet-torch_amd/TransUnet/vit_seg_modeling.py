@@ -284,9 +284,7 @@ class DecoderCup(nn.Module):
 # ---- tape builders -------------------------------------------------------------------------------------------------------
 def _build_attention(t, x, attn: Attention, residual=None):
     """`residual`: the block's skip input, added by the projection dropout's kernel (Block.forward's `x + h`)."""
-    if attn.attn_dropout.p > 0 and t.training:
-        raise NotImplementedError("attention-probability dropout > 0 is not supported (all reference configs use 0.0)")
-    ctx = t.qkv_attention(x, attn.query, attn.key, attn.value, attn.num_attention_heads)
+    ctx = t.qkv_attention(x, attn.query, attn.key, attn.value, attn.num_attention_heads, p=attn.attn_dropout.p)
     return t.linear_dropout(ctx, attn.out.weight, attn.out.bias, attn.proj_dropout.p, add=residual)
 
 

@@ -12,6 +12,11 @@
 //   backward dQ  : same decomposition; also writes delta = rowsum(dO * O).
 //   backward dKV : block = 128 keys (4 waves x 32) of one (batch, head); Q/dO streamed in 32-query tiles.
 // Deterministic (no atomics): dQ and dK/dV come from two kernels that each recompute P from the saved log-sum-exp.
+//
+// DROP (all three kernels): attention-probability dropout, O = (P o Z) V, Z = keep / (1 - p).  A lane owns one query column (one
+// key column on the K/V side) and 16 rows of a 32x32 tile, so it regenerates its 16 keep bits per tile from the stream
+// (common.h: umi_stream_keep) with one 64-bit base index per lane: no mask tensor, no LDS, no atomics.  The row statistics and
+// the stored log-sum-exp stay those of the undropped softmax.  DROP = the kernel was given a UmiAttnDrop (common.h).
 #include "common.h"
 
 typedef _Float16 half8 __attribute__((ext_vector_type(8)));
@@ -62,13 +67,16 @@ __device__ __forceinline__ void stage_rows(const half_t* __restrict__ src, int l
 template <bool BWD> struct ChunkKeys { static constexpr int value = BWD ? 128 : 224; };
 
 // ------------------------------------------------------------------------------------------------------------------------
-template <bool BWD>
+template <bool BWD, typename... DA>
 __global__ __launch_bounds__(256, 2) void attn_q_side_kernel(const half_t* __restrict__ q, const half_t* __restrict__ k,
                                                              const half_t* __restrict__ v, int ld,
                                                              half_t* __restrict__ o /*fwd: out; bwd: forward output (read)*/,
                                                              const half_t* __restrict__ dO, int ldo,
                                                              float* __restrict__ lse, half_t* __restrict__ dq, int lddq,
-                                                             float* __restrict__ delta, int B, int N, int Hh, float scale) {
+                                                             float* __restrict__ delta, int B, int N, int Hh, float scale,
+                                                             DA... da) {
+    constexpr bool DROP = sizeof...(DA) != 0;
+    const UmiAttnDrop drop = umi_attn_drop_of(da...);
     constexpr int KC = ChunkKeys<BWD>::value;
     // LDS: K row-major [KC][RROW] (+ chunked copy for dQ), V: fwd chunked [2][KC][CROW]; bwd row-major [KC][RROW]
     __shared__ __attribute__((aligned(16))) unsigned char smem[KC * RROW + 2 * KC * CROW + (BWD ? KC * RROW : 0)];
@@ -86,6 +94,8 @@ __global__ __launch_bounds__(256, 2) void attn_q_side_kernel(const half_t* __res
     const half_t* qh = q + h * D;
     const half_t* kh = k + h * D;
     const half_t* vh = v + h * D;
+    const unsigned dseed = DROP ? umi_stream_seed(drop) : 0u;
+    const unsigned long erow = DROP ? ((unsigned long)bh * N + qi) * N + 4 * lh : 0ul;   // dense index of P[qi][4 * lh]
 
     // Q^T (and dO^T) B-operand fragments: lane = query column, k = 8 consecutive d of chunk dc
     half8 qf[4], dof[4];
@@ -133,6 +143,12 @@ __global__ __launch_bounds__(256, 2) void attn_q_side_kernel(const half_t* __res
         __syncthreads();
         const int kend = (N - kc0) < KC ? (N - kc0) : KC;
         for (int kt = 0; kt < kend; kt += 32) {
+            unsigned keepbits = 0;                                 // bit r: keep of P[qi][key of register r]; independent of the
+            if (DROP) {                                            // products below, so the hashes run under their latency
+#pragma unroll
+                for (int r = 0; r < 16; ++r)
+                    keepbits |= (unsigned)umi_stream_keep(erow + (kc0 + kt + (r & 3) + 8 * (r >> 2)), dseed, drop.thr) << r;
+            }
             // S^T tile [32 keys][32 queries]
             floatx16 s;
 #pragma unroll
@@ -160,6 +176,10 @@ __global__ __launch_bounds__(256, 2) void attn_q_side_kernel(const half_t* __res
                 ps += lane_xchg32(ps);
                 lsum = lsum * corr + ps;
                 mx = mn;
+                if (DROP) {                                        // only the operand of P . V is masked
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) p[r] = (keepbits >> r & 1) ? p[r] : 0.f;
+                }
 #pragma unroll
                 for (int a = 0; a < 2; ++a)
 #pragma unroll
@@ -178,7 +198,8 @@ __global__ __launch_bounds__(256, 2) void attn_q_side_kernel(const half_t* __res
                 for (int r = 0; r < 16; ++r) {
                     int key = kt + (r & 3) + 8 * (r >> 2) + 4 * lh;
                     float pr = key < kend ? __expf(s[r] * scale - L) : 0.f;
-                    p[r] = pr * (dp[r] - dl);
+                    if (DROP) p[r] = pr * (((keepbits >> r & 1) ? dp[r] * drop.inv_keep : 0.f) - dl);   // dS = P o (Z o dP - delta)
+                    else p[r] = pr * (dp[r] - dl);
                 }
             }
             half8 f0, f1;
@@ -193,7 +214,7 @@ __global__ __launch_bounds__(256, 2) void attn_q_side_kernel(const half_t* __res
         }
     }
     if (qv) {
-        const float fin = BWD ? scale : 1.f / lsum;
+        const float fin = BWD ? scale : (DROP ? drop.inv_keep / lsum : 1.f / lsum);
         half_t* dst = BWD ? dq + (tok0 + qi) * lddq + h * D : o + (tok0 + qi) * ldo + h * D;
 #pragma unroll
         for (int mt = 0; mt < 2; ++mt)
@@ -214,12 +235,15 @@ __global__ __launch_bounds__(256, 2) void attn_q_side_kernel(const half_t* __res
 // ------------------------------------------------------------------------------------------------------------------------
 // dK / dV: wave = 32 keys (lane = key column of S[q][key]); Q and dO tiles of 32 queries are staged row-major (A operand of
 // S = Q.K^T and dP = dO.V^T) and chunked (transposed A operand of dV^T = dO^T.P, dK^T = Q^T.dS).
+template <typename... DA>
 __global__ __launch_bounds__(256, 2) void attn_kv_side_kernel(const half_t* __restrict__ q, const half_t* __restrict__ k,
                                                               const half_t* __restrict__ v, int ld,
                                                               const half_t* __restrict__ dO, int ldo,
                                                               const float* __restrict__ lse, const float* __restrict__ delta,
                                                               half_t* __restrict__ dk, half_t* __restrict__ dv, int lddk, int B,
-                                                              int N, int Hh, float scale) {
+                                                              int N, int Hh, float scale, DA... da) {
+    constexpr bool DROP = sizeof...(DA) != 0;
+    const UmiAttnDrop drop = umi_attn_drop_of(da...);
     constexpr int QT = 32;
     __shared__ __attribute__((aligned(16))) unsigned char smem[2 * (QT * RROW + 2 * QT * CROW)];
     __shared__ float lse_s[QT], del_s[QT];
@@ -235,6 +259,8 @@ __global__ __launch_bounds__(256, 2) void attn_kv_side_kernel(const half_t* __re
     const int lk = lane & 31, lh = lane >> 5;
     const int ki = k0 + lk;
     const bool kv = ki < N;
+    const unsigned dseed = DROP ? umi_stream_seed(drop) : 0u;
+    const unsigned long ecol = DROP ? ((unsigned long)bh * N + 4 * lh) * N + ki : 0ul;   // dense index of P[4 * lh][ki]
     half8 kf[4], vf[4];                                            // K^T / V^T B-operand fragments (lane = key column)
 #pragma unroll
     for (int dc = 0; dc < 4; ++dc) {
@@ -265,6 +291,12 @@ __global__ __launch_bounds__(256, 2) void attn_kv_side_kernel(const half_t* __re
             del_s[tid] = in ? delta[(long)bh * N + q0 + tid] : 0.f;
         }
         __syncthreads();
+        unsigned keepbits = 0;                                     // bit r: keep of P[query of register r][ki]
+        if (DROP) {
+#pragma unroll
+            for (int r = 0; r < 16; ++r)
+                keepbits |= (unsigned)umi_stream_keep(ecol + (unsigned long)(q0 + (r & 3) + 8 * (r >> 2)) * N, dseed, drop.thr) << r;
+        }
         floatx16 s, dp;
 #pragma unroll
         for (int r = 0; r < 16; ++r) { s[r] = 0.f; dp[r] = 0.f; }
@@ -280,6 +312,12 @@ __global__ __launch_bounds__(256, 2) void attn_kv_side_kernel(const half_t* __re
         for (int r = 0; r < 16; ++r) {
             int qq = (r & 3) + 8 * (r >> 2) + 4 * lh;                                   // query row of this register
             float pr = (q0 + qq < N && kv) ? __expf(s[r] * scale - lse_s[qq]) : 0.f;
+            if (DROP) {                                                                 // dV takes P o Z, dK takes dS
+                const bool keep = keepbits >> r & 1;
+                p[r] = keep ? pr * drop.inv_keep : 0.f;
+                ds[r] = pr * ((keep ? dp[r] * drop.inv_keep : 0.f) - del_s[qq]) * scale;
+                continue;
+            }
             p[r] = pr;
             ds[r] = pr * (dp[r] - del_s[qq]) * scale;
         }
@@ -321,23 +359,32 @@ bool umi_attn_mfma_ok(int D_, int ld, int ldo, int dtype, const void* a, const v
 }
 
 int umi_attn_fwd_mfma(const void* q, const void* k, const void* v, int ld, void* o, int ldo, float* lse, int B, int N, int Hh,
-                      hipStream_t s) {
+                      const UmiAttnDrop* drop, hipStream_t s) {
     dim3 grid((N + 127) / 128, B * Hh), block(256);
-    hipLaunchKernelGGL(attn_q_side_kernel<false>, grid, block, 0, s, (const half_t*)q, (const half_t*)k, (const half_t*)v, ld,
-                       (half_t*)o, (const half_t*)nullptr, ldo, lse, (half_t*)nullptr, 0, (float*)nullptr, B, N, Hh, 0.125f);
+#define UMI_ARGS (const half_t*)q, (const half_t*)k, (const half_t*)v, ld, (half_t*)o, (const half_t*)nullptr, ldo, lse, \
+                 (half_t*)nullptr, 0, (float*)nullptr, B, N, Hh, 0.125f
+    if (drop) hipLaunchKernelGGL(attn_q_side_kernel<false>, grid, block, 0, s, UMI_ARGS, *drop);
+    else hipLaunchKernelGGL(attn_q_side_kernel<false>, grid, block, 0, s, UMI_ARGS);
+#undef UMI_ARGS
     UMI_LAUNCH_CHECK();
     return UMI_OK;
 }
 
 int umi_attn_bwd_mfma(const void* q, const void* k, const void* v, int ld, const void* o, const void* dO, int ldo,
                       const float* lse, void* dq, void* dk, void* dv, int ldd, float* delta, int B, int N, int Hh,
-                      hipStream_t s) {
+                      const UmiAttnDrop* drop, hipStream_t s) {
     dim3 grid((N + 127) / 128, B * Hh), block(256);
-    hipLaunchKernelGGL(attn_q_side_kernel<true>, grid, block, 0, s, (const half_t*)q, (const half_t*)k, (const half_t*)v, ld,
-                       (half_t*)o, (const half_t*)dO, ldo, (float*)lse, (half_t*)dq, ldd, delta, B, N, Hh, 0.125f);
+#define UMI_Q_ARGS (const half_t*)q, (const half_t*)k, (const half_t*)v, ld, (half_t*)o, (const half_t*)dO, ldo, (float*)lse, \
+                   (half_t*)dq, ldd, delta, B, N, Hh, 0.125f
+#define UMI_KV_ARGS (const half_t*)q, (const half_t*)k, (const half_t*)v, ld, (const half_t*)dO, ldo, lse, (const float*)delta, \
+                    (half_t*)dk, (half_t*)dv, ldd, B, N, Hh, 0.125f
+    if (drop) hipLaunchKernelGGL(attn_q_side_kernel<true>, grid, block, 0, s, UMI_Q_ARGS, *drop);
+    else hipLaunchKernelGGL(attn_q_side_kernel<true>, grid, block, 0, s, UMI_Q_ARGS);
     UMI_LAUNCH_CHECK();
-    hipLaunchKernelGGL(attn_kv_side_kernel, grid, block, 0, s, (const half_t*)q, (const half_t*)k, (const half_t*)v, ld,
-                       (const half_t*)dO, ldo, lse, (const float*)delta, (half_t*)dk, (half_t*)dv, ldd, B, N, Hh, 0.125f);
+    if (drop) hipLaunchKernelGGL(attn_kv_side_kernel, grid, block, 0, s, UMI_KV_ARGS, *drop);
+    else hipLaunchKernelGGL(attn_kv_side_kernel, grid, block, 0, s, UMI_KV_ARGS);
+#undef UMI_Q_ARGS
+#undef UMI_KV_ARGS
     UMI_LAUNCH_CHECK();
     return UMI_OK;
 }

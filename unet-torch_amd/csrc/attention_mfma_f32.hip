@@ -22,6 +22,8 @@
 //            same kind of tile (consecutive dwords, conflict-free).  dQ^T = K^T . dS^T, dV^T = dO^T . P and dK^T = Q^T . dS
 //            work the same way.
 //   Rows past N enter the LDS tiles as zeros and their probabilities are forced to zero: no unknown memory is multiplied.
+// DROP (all three kernels): attention-probability dropout, O = (P o Z) V, Z = keep / (1 - p): as in attention_mfma.hip, a lane
+// regenerates the 16 keep bits of its tile column from the stream (common.h: umi_stream_keep); statistics and lse are undropped.
 // Independent accumulators in flight per wave: forward 2 (the score chain is split in two halves of the head dimension, the two
 // 32-channel halves of O), backward 2 (S and dP) and 2 / 4 (dQ halves; dK and dV halves).
 #include "kernels.h"
@@ -88,13 +90,15 @@ __device__ __forceinline__ void store_row(float* __restrict__ dst, const f32x16 
 }
 
 // ---- forward (BWD = false) and backward query side (BWD = true) ---------------------------------------------------------------
-template <bool BWD>
+template <bool BWD, typename... DA>
 __global__ __launch_bounds__(256, 2) void attn_f32_q_side_kernel(const float* __restrict__ q, const float* __restrict__ k,
                                                                  const float* __restrict__ v, int ld,
                                                                  float* __restrict__ o /*fwd: out; bwd: forward output (read)*/,
                                                                  const float* __restrict__ dO, int ldo, float* __restrict__ lse,
                                                                  float* __restrict__ dq, int lddq, float* __restrict__ delta,
-                                                                 int N, int Hh, int tiles, float scale) {
+                                                                 int N, int Hh, int tiles, float scale, DA... da) {
+    constexpr bool DROP = sizeof...(DA) != 0;
+    const UmiAttnDrop drop = umi_attn_drop_of(da...);
     __shared__ float ks[KC * PITCH], vs[KC * PITCH];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, lq = lane & 31, lh = lane >> 5;
     const int bh = blockIdx.x / tiles, b = bh / Hh, h = bh % Hh;
@@ -103,6 +107,8 @@ __global__ __launch_bounds__(256, 2) void attn_f32_q_side_kernel(const float* __
     const bool qv = qi < N, wave_on = q0 < N;          // a wave with no query only helps staging
     const float* kh = k + h * D;
     const float* vh = v + h * D;
+    const unsigned dseed = DROP ? umi_stream_seed(drop) : 0u;
+    const unsigned long erow = DROP ? ((unsigned long)bh * N + qi) * N : 0ul;          // dense index of P[qi][0]
 
     float qr[32], dor[32];
     float dl = 0.f, L = 0.f;
@@ -135,6 +141,12 @@ __global__ __launch_bounds__(256, 2) void attn_f32_q_side_kernel(const float* __
         const int kend = (N - kc0) < KC ? (N - kc0) : KC;
         for (int kt = 0; kt < kend; kt += 32) {
             const float* ka = ks + (kt + lq) * PITCH + lh * 32;
+            unsigned keepbits = 0;                      // bit r: keep of P[qi][key of register r]; independent of the products
+            if (DROP) {                                 // below, so the hashes run under their latency
+#pragma unroll
+                for (int r = 0; r < 16; ++r)
+                    keepbits |= (unsigned)umi_stream_keep(erow + (kc0 + kt + d_row(r, lh)), dseed, drop.thr) << r;
+            }
             f32x16 p;
             if (!BWD) {
                 // S^T tile [32 keys][32 queries] of the scaled scores, as two chains over the even and the odd steps
@@ -159,6 +171,10 @@ __global__ __launch_bounds__(256, 2) void attn_f32_q_side_kernel(const float* __
                 ps += lane_xchg32(ps);
                 lsum = lsum * corr + ps;
                 mx = mn;
+                if (DROP) {                             // only the operand of P . V is masked
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) p[r] = (keepbits >> r & 1) ? p[r] : 0.f;
+                }
 #pragma unroll
                 for (int a = 0; a < 2; ++a)
 #pragma unroll
@@ -175,7 +191,8 @@ __global__ __launch_bounds__(256, 2) void attn_f32_q_side_kernel(const float* __
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
                     const float pr = kt + d_row(r, lh) < kend ? __expf(s[r] - L) : 0.f;
-                    p[r] = pr * (dp[r] - dl);
+                    if (DROP) p[r] = pr * (((keepbits >> r & 1) ? dp[r] * drop.inv_keep : 0.f) - dl);   // dS = P o (Z o dP - delta)
+                    else p[r] = pr * (dp[r] - dl);
                 }
             }
             // acc^T[d][query] += X^T . p, X = V (forward) or K (backward): step t covers the two keys that register t holds
@@ -190,7 +207,7 @@ __global__ __launch_bounds__(256, 2) void attn_f32_q_side_kernel(const float* __
     }
     if (qv) {
         if (BWD) store_row(dq + (tok0 + qi) * lddq + h * D, acc, scale, lh);
-        else store_row(o + (tok0 + qi) * ldo + h * D, acc, 1.f / lsum, lh);
+        else store_row(o + (tok0 + qi) * ldo + h * D, acc, DROP ? drop.inv_keep / lsum : 1.f / lsum, lh);
         if (lh == 0) {
             if (BWD) delta[(long)bh * N + qi] = dl;
             else lse[(long)bh * N + qi] = mx + __logf(lsum);
@@ -202,12 +219,15 @@ __global__ __launch_bounds__(256, 2) void attn_f32_q_side_kernel(const float* __
 // A wave owns 32 keys (lane = key column of S[query][key]); its K (pre-scaled) and V rows are the B operands of S = Q . K^T and
 // dP = dO . V^T, whose A operands are rows of the staged Q and dO tiles.  P and dS = P * (dP - delta) * scale then feed
 // dV^T[d][key] += dO^T . P and dK^T[d][key] += Q^T . dS from the accumulator, with row reads of the same two tiles.
+template <typename... DA>
 __global__ __launch_bounds__(256, 2) void attn_f32_kv_side_kernel(const float* __restrict__ q, const float* __restrict__ k,
                                                                   const float* __restrict__ v, int ld,
                                                                   const float* __restrict__ dO, int ldo,
                                                                   const float* __restrict__ lse, const float* __restrict__ delta,
                                                                   float* __restrict__ dk, float* __restrict__ dv, int lddk, int N,
-                                                                  int Hh, int tiles, float scale) {
+                                                                  int Hh, int tiles, float scale, DA... da) {
+    constexpr bool DROP = sizeof...(DA) != 0;
+    const UmiAttnDrop drop = umi_attn_drop_of(da...);
     __shared__ float qs[QT * PITCH], os[QT * PITCH];
     __shared__ float lse_s[QT], del_s[QT];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, lk = lane & 31, lh = lane >> 5;
@@ -217,6 +237,8 @@ __global__ __launch_bounds__(256, 2) void attn_f32_kv_side_kernel(const float* _
     const bool kv = ki < N, wave_on = k0 < N;
     const float* qh = q + h * D;
     const float* oh = dO + h * D;
+    const unsigned dseed = DROP ? umi_stream_seed(drop) : 0u;
+    const unsigned long ecol = DROP ? (unsigned long)bh * N * N + ki : 0ul;            // dense index of P[0][ki]
 
     float kf[32], vf[32];
     load_row_half(k + (tok0 + ki) * ld + h * D + lh * 32, kv, scale, kf);
@@ -236,6 +258,16 @@ __global__ __launch_bounds__(256, 2) void attn_f32_kv_side_kernel(const float* _
         if (!wave_on) continue;
         const float* qa = qs + lk * PITCH + lh * 32;
         const float* oa = os + lk * PITCH + lh * 32;
+        unsigned keepbits = 0;                          // bit r: keep of P[query of register r][ki]
+        if (DROP) {
+            // four hashes at a time, NOT unrolled further: this kernel has no registers to spare (16 hashes in flight spill)
+#pragma unroll 1
+            for (int g = 0; g < 4; ++g)
+#pragma unroll
+                for (int j = 0; j < 4; ++j)
+                    keepbits |= (unsigned)umi_stream_keep(ecol + (unsigned long)(q0 + d_row(4 * g + j, lh)) * N, dseed, drop.thr)
+                                << (4 * g + j);
+        }
         f32x16 s = zero16(), dp = zero16();
 #pragma unroll
         for (int t = 0; t < 32; ++t) {
@@ -247,6 +279,12 @@ __global__ __launch_bounds__(256, 2) void attn_f32_kv_side_kernel(const float* _
         for (int r = 0; r < 16; ++r) {
             const int qq = d_row(r, lh);                // query row of this register
             const float pr = (q0 + qq < N && kv) ? __expf(s[r] - lse_s[qq]) : 0.f;
+            if (DROP) {                                 // dV takes P o Z, dK takes dS
+                const bool keep = keepbits >> r & 1;
+                p[r] = keep ? pr * drop.inv_keep : 0.f;
+                ds[r] = pr * ((keep ? dp[r] * drop.inv_keep : 0.f) - del_s[qq]) * scale;
+                continue;
+            }
             p[r] = pr;
             ds[r] = pr * (dp[r] - del_s[qq]) * scale;
         }
@@ -284,29 +322,36 @@ bool umi_attn_f32_mfma_ok(int D_, int ld, int ldo, int ldd, int dtype, int flags
 }
 
 int umi_attn_fwd_f32_mfma(const void* q, const void* k, const void* v, int ld, void* o, int ldo, float* lse, int B, int N, int Hh,
-                          hipStream_t s) {
+                          const UmiAttnDrop* drop, hipStream_t s) {
     int tiles;
     unsigned blocks;
     if (!grid_of(B, N, Hh, &tiles, &blocks)) return UMI_ERR_BADARG;
-    hipLaunchKernelGGL(attn_f32_q_side_kernel<false>, dim3(blocks), dim3(256), 0, s, (const float*)q, (const float*)k,
-                       (const float*)v, ld, (float*)o, (const float*)nullptr, ldo, lse, (float*)nullptr, 0, (float*)nullptr, N, Hh,
-                       tiles, 0.125f);
+#define UMI_ARGS (const float*)q, (const float*)k, (const float*)v, ld, (float*)o, (const float*)nullptr, ldo, lse, (float*)nullptr, 0, \
+                 (float*)nullptr, N, Hh, tiles, 0.125f
+    if (drop) hipLaunchKernelGGL(attn_f32_q_side_kernel<false>, dim3(blocks), dim3(256), 0, s, UMI_ARGS, *drop);
+    else hipLaunchKernelGGL(attn_f32_q_side_kernel<false>, dim3(blocks), dim3(256), 0, s, UMI_ARGS);
+#undef UMI_ARGS
     UMI_LAUNCH_CHECK();
     return UMI_OK;
 }
 
 int umi_attn_bwd_f32_mfma(const void* q, const void* k, const void* v, int ld, const void* o, const void* dO, int ldo,
                           const float* lse, void* dq, void* dk, void* dv, int ldd, float* delta, int B, int N, int Hh,
-                          hipStream_t s) {
+                          const UmiAttnDrop* drop, hipStream_t s) {
     int tiles;
     unsigned blocks;
     if (!grid_of(B, N, Hh, &tiles, &blocks)) return UMI_ERR_BADARG;
-    hipLaunchKernelGGL(attn_f32_q_side_kernel<true>, dim3(blocks), dim3(256), 0, s, (const float*)q, (const float*)k,
-                       (const float*)v, ld, (float*)o, (const float*)dO, ldo, (float*)lse, (float*)dq, ldd, delta, N, Hh, tiles,
-                       0.125f);
+#define UMI_Q_ARGS (const float*)q, (const float*)k, (const float*)v, ld, (float*)o, (const float*)dO, ldo, (float*)lse, (float*)dq, ldd, \
+                   delta, N, Hh, tiles, 0.125f
+#define UMI_KV_ARGS (const float*)q, (const float*)k, (const float*)v, ld, (const float*)dO, ldo, lse, (const float*)delta, (float*)dk, \
+                    (float*)dv, ldd, N, Hh, tiles, 0.125f
+    if (drop) hipLaunchKernelGGL(attn_f32_q_side_kernel<true>, dim3(blocks), dim3(256), 0, s, UMI_Q_ARGS, *drop);
+    else hipLaunchKernelGGL(attn_f32_q_side_kernel<true>, dim3(blocks), dim3(256), 0, s, UMI_Q_ARGS);
     UMI_LAUNCH_CHECK();
-    hipLaunchKernelGGL(attn_f32_kv_side_kernel, dim3(blocks), dim3(256), 0, s, (const float*)q, (const float*)k, (const float*)v,
-                       ld, (const float*)dO, ldo, lse, (const float*)delta, (float*)dk, (float*)dv, ldd, N, Hh, tiles, 0.125f);
+    if (drop) hipLaunchKernelGGL(attn_f32_kv_side_kernel, dim3(blocks), dim3(256), 0, s, UMI_KV_ARGS, *drop);
+    else hipLaunchKernelGGL(attn_f32_kv_side_kernel, dim3(blocks), dim3(256), 0, s, UMI_KV_ARGS);
+#undef UMI_Q_ARGS
+#undef UMI_KV_ARGS
     UMI_LAUNCH_CHECK();
     return UMI_OK;
 }

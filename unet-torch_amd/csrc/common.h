@@ -102,6 +102,35 @@ __device__ __forceinline__ umi_half8 umi_tx8(umi_half8 v, const float4* t) {
     return __builtin_elementwise_max(__builtin_bit_cast(umi_half8, out), lo);
 }
 
+// The dropout stream of include/unetmi.h (umi_dropout) for kernels that REGENERATE their mask instead of storing it: the three
+// attention families (transformer_kernels.hip, attention_mfma.hip, attention_mfma_f32.hip).  One definition; the kernels that
+// store mask bytes (dropout_kernel, dropout8*_kernel, the conv1x1 epilogue) keep their own, older copies of the same rule.
+//   keep(e) = u >= p,  u = (hash32(e_lo, seed' ^ e_hi) >> 8) * 2^-24,  seed' = seed + seed_dev[0] * 0x9E3779B9
+// u is a multiple of 2^-24 and p * 2^24 is exact in fp32, so u >= p is the integer comparison (x >> 8) >= ceil(p * 2^24).
+struct UmiAttnDrop {
+    unsigned thr;                 // ceil(p * 2^24), 0 < p <= 1 (p == 0 never reaches a DROP kernel); 2^24 for p == 1: keeps nothing
+    float inv_keep;               // 1 / (1 - p); 0 for p == 1, where nothing is kept and no infinite scale is multiplied in
+    unsigned seed;
+    const unsigned* seed_dev;     // nullable device counter, read inside the kernel
+};
+// The attention kernels take the struct as a trailing parameter PACK (empty or one UmiAttnDrop): the instantiation without
+// dropout then has exactly the parameter list -- kernel-argument segment, argument loads, register allocation -- it had before
+// the feature existed, not merely unused extra arguments.
+__device__ __forceinline__ UmiAttnDrop umi_attn_drop_of() { return UmiAttnDrop{}; }
+__device__ __forceinline__ UmiAttnDrop umi_attn_drop_of(const UmiAttnDrop& d) { return d; }
+__device__ __forceinline__ unsigned umi_stream_hash32(unsigned a, unsigned b) {
+    unsigned x = a * 0x9E3779B1u ^ (b + 0x7F4A7C15u);
+    x ^= x >> 16; x *= 0x85EBCA6Bu; x ^= x >> 13; x *= 0xC2B2AE35u; x ^= x >> 16;
+    return x;
+}
+__device__ __forceinline__ unsigned umi_stream_seed(const UmiAttnDrop& d) {
+    return d.seed_dev ? d.seed + d.seed_dev[0] * 0x9E3779B9u : d.seed;
+}
+// e: index of the probability in the dense [B * heads * N, N] tensor, ((b * heads + h) * N + i) * N + j, in 64 bits
+__device__ __forceinline__ bool umi_stream_keep(unsigned long e, unsigned seed, unsigned thr) {
+    return (umi_stream_hash32((unsigned)e, seed ^ (unsigned)(e >> 32)) >> 8) >= thr;
+}
+
 template <typename T> __device__ __forceinline__ float umi_ld(const T* p) { return (float)(*p); }
 template <typename T> __device__ __forceinline__ void umi_st(T* p, float v) { *p = (T)v; }
 

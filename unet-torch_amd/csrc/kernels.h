@@ -232,19 +232,20 @@ bool umi_ln_bwd_f16v(const void* dy, int lddy, const void* x, int ldx, const flo
 bool umi_bilinear2x_f16v(const void* x, int ldx, const void* tx, void* y, int ldy, int backward, int N, int H, int W, int C,
                          hipStream_t s);
 
+// (both matrix-core families: `drop` null = the kernels without dropout, else their DROP instantiations, common.h UmiAttnDrop)
 // ---- attention_mfma.hip ---------------------------------------------------------------------------------------------------------
 bool umi_attn_mfma_ok(int D, int ld, int ldo, int dtype, const void* a, const void* b, const void* c);
 int umi_attn_fwd_mfma(const void* q, const void* k, const void* v, int ld, void* o, int ldo, float* lse, int B, int N, int Hh,
-                      hipStream_t s);
+                      const UmiAttnDrop* drop, hipStream_t s);
 int umi_attn_bwd_mfma(const void* q, const void* k, const void* v, int ld, const void* o, const void* dO, int ldo,
                       const float* lse, void* dq, void* dk, void* dv, int ldd, float* delta, int B, int N, int Hh,
-                      hipStream_t s);
+                      const UmiAttnDrop* drop, hipStream_t s);
 
 // ---- attention_mfma_f32.hip: only under UMI_ATTN_F32_MFMA -----------------------------------------------------------------------
 // ptrs: the OR of every tensor address of the call (16-byte alignment); ldd = 0 in a forward call
 bool umi_attn_f32_mfma_ok(int D, int ld, int ldo, int ldd, int dtype, int flags, uintptr_t ptrs);
 int umi_attn_fwd_f32_mfma(const void* q, const void* k, const void* v, int ld, void* o, int ldo, float* lse, int B, int N, int Hh,
-                          hipStream_t s);
+                          const UmiAttnDrop* drop, hipStream_t s);
 int umi_attn_bwd_f32_mfma(const void* q, const void* k, const void* v, int ld, const void* o, const void* dO, int ldo,
                           const float* lse, void* dq, void* dk, void* dv, int ldd, float* delta, int B, int N, int Hh,
-                          hipStream_t s);
+                          const UmiAttnDrop* drop, hipStream_t s);

@@ -381,14 +381,21 @@ __global__ void dropout_kernel(const T* __restrict__ x, int ldx, T* __restrict__
 // ---------------------------------------------------------------------------------------------------------
 // Softmax attention, heads = channel slices of width D (vit_seg_modeling.py:73-91).  One thread = one query row of
 // one (batch, head); K/V tiles of 64 keys staged in LDS; online softmax; log-sum-exp saved for backward.
-template <typename T, int D>
+// DROP (all three kernels): attention-probability dropout, O = (P o Z) V with Z = keep / (1 - p).  The keep bit of P[i][j] is
+// regenerated from the stream (common.h: umi_stream_keep) wherever P is formed; the row statistics and lse are the undropped
+// softmax's.  DROP = the kernel was given a UmiAttnDrop (common.h: a trailing parameter pack, empty without dropout).
+template <typename T, int D, typename... DA>
 __global__ __launch_bounds__(64) void attn_fwd_kernel(const T* __restrict__ q, const T* __restrict__ k, const T* __restrict__ v,
                                                       int ld, T* __restrict__ o, int ldo, float* __restrict__ lse, int B,
-                                                      int N, int Hh, float scale) {
+                                                      int N, int Hh, float scale, DA... da) {
+    constexpr bool DROP = sizeof...(DA) != 0;
+    const UmiAttnDrop drop = umi_attn_drop_of(da...);
     __shared__ float ks[64][D + 1], vs[64][D + 1];
     const int bh = blockIdx.y, b = bh / Hh, h = bh % Hh;
     const int qi = blockIdx.x * 64 + threadIdx.x;
     const bool act = qi < N;
+    const unsigned dseed = DROP ? umi_stream_seed(drop) : 0u;
+    const unsigned long erow = DROP ? ((unsigned long)bh * N + qi) * N : 0ul;      // dense index of P[qi][0]
     float qr[D], acc[D];
 #pragma unroll
     for (int d = 0; d < D; ++d) { qr[d] = act ? (float)q[((long)b * N + qi) * ld + h * D + d] * scale : 0.f; acc[d] = 0.f; }
@@ -410,13 +417,14 @@ __global__ __launch_bounds__(64) void attn_fwd_kernel(const T* __restrict__ q, c
             float mn = fmaxf(mx, s);
             float corr = __expf(mx - mn), pr = __expf(s - mn);
             l = l * corr + pr;
+            if (DROP) pr = umi_stream_keep(erow + (k0 + kk), dseed, drop.thr) ? pr : 0.f;
 #pragma unroll
             for (int d = 0; d < D; ++d) acc[d] = fmaf(acc[d], corr, pr * vs[kk][d]);
             mx = mn;
         }
     }
     if (act) {
-        const float inv = 1.f / l;
+        const float inv = DROP ? drop.inv_keep / l : 1.f / l;
 #pragma unroll
         for (int d = 0; d < D; ++d) o[((long)b * N + qi) * ldo + h * D + d] = (T)(acc[d] * inv);
         lse[(long)bh * N + qi] = mx + __logf(l);
@@ -424,15 +432,20 @@ __global__ __launch_bounds__(64) void attn_fwd_kernel(const T* __restrict__ q, c
 }
 
 // backward, query side: delta = sum(dO*O); dQ[q] = scale * sum_k p*(dO.V_k - delta) K_k
-template <typename T, int D>
+template <typename T, int D, typename... DA>
 __global__ __launch_bounds__(64) void attn_bwd_q_kernel(const T* __restrict__ q, const T* __restrict__ k, const T* __restrict__ v,
                                                         int ld, const T* __restrict__ o, const T* __restrict__ dO, int ldo,
                                                         const float* __restrict__ lse, T* __restrict__ dq, int lddq,
-                                                        float* __restrict__ delta, int B, int N, int Hh, float scale) {
+                                                        float* __restrict__ delta, int B, int N, int Hh, float scale,
+                                                        DA... da) {
+    constexpr bool DROP = sizeof...(DA) != 0;
+    const UmiAttnDrop drop = umi_attn_drop_of(da...);
     __shared__ float ks[64][D + 1], vs[64][D + 1];
     const int bh = blockIdx.y, b = bh / Hh, h = bh % Hh;
     const int qi = blockIdx.x * 64 + threadIdx.x;
     const bool act = qi < N;
+    const unsigned dseed = DROP ? umi_stream_seed(drop) : 0u;
+    const unsigned long erow = DROP ? ((unsigned long)bh * N + qi) * N : 0ul;
     float qr[D], dor[D], acc[D];
     float dl = 0.f;
 #pragma unroll
@@ -458,6 +471,7 @@ __global__ __launch_bounds__(64) void attn_bwd_q_kernel(const T* __restrict__ q,
             float s = 0.f, dp = 0.f;
 #pragma unroll
             for (int d = 0; d < D; ++d) { s = fmaf(qr[d], ks[kk][d], s); dp = fmaf(dor[d], vs[kk][d], dp); }
+            if (DROP) dp = umi_stream_keep(erow + (k0 + kk), dseed, drop.thr) ? dp * drop.inv_keep : 0.f;   // Z o dP
             float ds = __expf(s - L) * (dp - dl);
 #pragma unroll
             for (int d = 0; d < D; ++d) acc[d] = fmaf(ds, ks[kk][d], acc[d]);
@@ -471,16 +485,20 @@ __global__ __launch_bounds__(64) void attn_bwd_q_kernel(const T* __restrict__ q,
 }
 
 // backward, key side: dV[k] = sum_q p*dO_q ; dK[k] = scale * sum_q p*(dO_q.V_k - delta_q) Q_q
-template <typename T, int D>
+template <typename T, int D, typename... DA>
 __global__ __launch_bounds__(64) void attn_bwd_kv_kernel(const T* __restrict__ q, const T* __restrict__ k, const T* __restrict__ v,
                                                          int ld, const T* __restrict__ dO, int ldo, const float* __restrict__ lse,
                                                          const float* __restrict__ delta, T* __restrict__ dk, T* __restrict__ dv,
-                                                         int lddk, int B, int N, int Hh, float scale) {
+                                                         int lddk, int B, int N, int Hh, float scale, DA... da) {
+    constexpr bool DROP = sizeof...(DA) != 0;
+    const UmiAttnDrop drop = umi_attn_drop_of(da...);
     __shared__ float qs[64][D + 1], ds_[64][D + 1];
     __shared__ float ls[64], dls[64];
     const int bh = blockIdx.y, b = bh / Hh, h = bh % Hh;
     const int ki = blockIdx.x * 64 + threadIdx.x;
     const bool act = ki < N;
+    const unsigned dseed = DROP ? umi_stream_seed(drop) : 0u;
+    const unsigned long ecol = DROP ? (unsigned long)bh * N * N + ki : 0ul;        // dense index of P[0][ki]
     float kr[D], vr[D], ak[D], av[D];
 #pragma unroll
     for (int d = 0; d < D; ++d) {
@@ -505,6 +523,15 @@ __global__ __launch_bounds__(64) void attn_bwd_kv_kernel(const T* __restrict__ q
 #pragma unroll
             for (int d = 0; d < D; ++d) { s = fmaf(qs[qq][d], kr[d], s); dp = fmaf(ds_[qq][d], vr[d], dp); }
             float p = __expf(s - ls[qq]);
+            if (DROP) {
+                const bool keep = umi_stream_keep(ecol + (unsigned long)(q0 + qq) * N, dseed, drop.thr);
+                dp = keep ? dp * drop.inv_keep : 0.f;
+                const float dsz = p * (dp - dls[qq]);
+                p = keep ? p * drop.inv_keep : 0.f;                                 // the dV operand is P o Z
+#pragma unroll
+                for (int d = 0; d < D; ++d) { av[d] = fmaf(p, ds_[qq][d], av[d]); ak[d] = fmaf(dsz, qs[qq][d], ak[d]); }
+                continue;
+            }
             float dsv = p * (dp - dls[qq]);
 #pragma unroll
             for (int d = 0; d < D; ++d) { av[d] = fmaf(p, ds_[qq][d], av[d]); ak[d] = fmaf(dsv, qs[qq][d], ak[d]); }
@@ -814,14 +841,14 @@ extern "C" int umi_dropout(const void* x, int ldx, void* y, int ldy, void* mask,
     return UMI_OK;
 }
 
-template <typename T>
+template <typename T, typename... DA>
 static int attn_fwd_t(const void* q, const void* k, const void* v, int ld, void* o, int ldo, float* lse, int B, int N, int Hh,
-                      int D, hipStream_t s) {
+                      int D, hipStream_t s, DA... drop) {
     const float scale = 1.f / sqrtf((float)D);
     dim3 grid((N + 63) / 64, B * Hh), block(64);
-    if (D == 64) hipLaunchKernelGGL((attn_fwd_kernel<T, 64>), grid, block, 0, s, (const T*)q, (const T*)k, (const T*)v, ld, (T*)o, ldo, lse, B, N, Hh, scale);
-    else if (D == 32) hipLaunchKernelGGL((attn_fwd_kernel<T, 32>), grid, block, 0, s, (const T*)q, (const T*)k, (const T*)v, ld, (T*)o, ldo, lse, B, N, Hh, scale);
-    else if (D == 16) hipLaunchKernelGGL((attn_fwd_kernel<T, 16>), grid, block, 0, s, (const T*)q, (const T*)k, (const T*)v, ld, (T*)o, ldo, lse, B, N, Hh, scale);
+    if (D == 64) hipLaunchKernelGGL((attn_fwd_kernel<T, 64>), grid, block, 0, s, (const T*)q, (const T*)k, (const T*)v, ld, (T*)o, ldo, lse, B, N, Hh, scale, drop...);
+    else if (D == 32) hipLaunchKernelGGL((attn_fwd_kernel<T, 32>), grid, block, 0, s, (const T*)q, (const T*)k, (const T*)v, ld, (T*)o, ldo, lse, B, N, Hh, scale, drop...);
+    else if (D == 16) hipLaunchKernelGGL((attn_fwd_kernel<T, 16>), grid, block, 0, s, (const T*)q, (const T*)k, (const T*)v, ld, (T*)o, ldo, lse, B, N, Hh, scale, drop...);
     else return UMI_ERR_UNSUPPORTED;
     return UMI_OK;
 }
@@ -841,63 +868,109 @@ extern "C" int umi_attn_plan(int N, int heads, int D, int ld, int ldo, int ldd, 
     return UMI_OK;
 }
 
-extern "C" int umi_attn_fwd_flags(const void* q, const void* k, const void* v, int ld, void* o, int ldo, float* lse, int B, int N,
-                                  int heads, int D, int dtype, int flags, umi_stream_t st) {
+// drop: null for the calls without dropout (the kernels as they were), else the dropout instantiation of the SAME family
+static int attn_fwd_any(const void* q, const void* k, const void* v, int ld, void* o, int ldo, float* lse, int B, int N,
+                        int heads, int D, int dtype, int flags, const UmiAttnDrop* drop, umi_stream_t st) {
     if (!q || !k || !v || !o || !lse || B <= 0 || N <= 0 || heads <= 0) return UMI_ERR_BADARG;
     const int kernel = attn_kernel_of(D, ld, ldo, 0, dtype, flags, q, k, v, (uintptr_t)o);
-    if (kernel == 1) return umi_attn_fwd_mfma(q, k, v, ld, o, ldo, lse, B, N, heads, (hipStream_t)st);
-    if (kernel == 2) return umi_attn_fwd_f32_mfma(q, k, v, ld, o, ldo, lse, B, N, heads, (hipStream_t)st);
+    if (kernel == 1) return umi_attn_fwd_mfma(q, k, v, ld, o, ldo, lse, B, N, heads, drop, (hipStream_t)st);
+    if (kernel == 2) return umi_attn_fwd_f32_mfma(q, k, v, ld, o, ldo, lse, B, N, heads, drop, (hipStream_t)st);
     int rc;
-    if (dtype == UMI_F32) rc = attn_fwd_t<float>(q, k, v, ld, o, ldo, lse, B, N, heads, D, (hipStream_t)st);
-    else if (dtype == UMI_F16) rc = attn_fwd_t<half_t>(q, k, v, ld, o, ldo, lse, B, N, heads, D, (hipStream_t)st);
+    if (dtype == UMI_F32)
+        rc = drop ? attn_fwd_t<float>(q, k, v, ld, o, ldo, lse, B, N, heads, D, (hipStream_t)st, *drop)
+                  : attn_fwd_t<float>(q, k, v, ld, o, ldo, lse, B, N, heads, D, (hipStream_t)st);
+    else if (dtype == UMI_F16)
+        rc = drop ? attn_fwd_t<half_t>(q, k, v, ld, o, ldo, lse, B, N, heads, D, (hipStream_t)st, *drop)
+                  : attn_fwd_t<half_t>(q, k, v, ld, o, ldo, lse, B, N, heads, D, (hipStream_t)st);
     else return UMI_ERR_BADARG;
     if (rc) return rc;
     UMI_LAUNCH_CHECK();
     return UMI_OK;
+}
+extern "C" int umi_attn_fwd_flags(const void* q, const void* k, const void* v, int ld, void* o, int ldo, float* lse, int B, int N,
+                                  int heads, int D, int dtype, int flags, umi_stream_t st) {
+    return attn_fwd_any(q, k, v, ld, o, ldo, lse, B, N, heads, D, dtype, flags, nullptr, st);
 }
 extern "C" int umi_attn_fwd(const void* q, const void* k, const void* v, int ld, void* o, int ldo, float* lse, int B, int N,
                             int heads, int D, int dtype, umi_stream_t st) {
     return umi_attn_fwd_flags(q, k, v, ld, o, ldo, lse, B, N, heads, D, dtype, 0, st);
 }
 
-template <typename T>
+template <typename T, typename... DA>
 static int attn_bwd_t(const void* q, const void* k, const void* v, int ld, const void* o, const void* dO, int ldo,
                       const float* lse, void* dq, void* dk, void* dv, int ldd, float* delta, int B, int N, int Hh, int D,
-                      hipStream_t s) {
+                      hipStream_t s, DA... drop) {
     const float scale = 1.f / sqrtf((float)D);
     dim3 grid((N + 63) / 64, B * Hh), block(64);
 #define GO(DD)                                                                                                              \
     hipLaunchKernelGGL((attn_bwd_q_kernel<T, DD>), grid, block, 0, s, (const T*)q, (const T*)k, (const T*)v, ld, (const T*)o, \
-                       (const T*)dO, ldo, lse, (T*)dq, ldd, delta, B, N, Hh, scale);                                         \
+                       (const T*)dO, ldo, lse, (T*)dq, ldd, delta, B, N, Hh, scale, drop...);                                   \
     hipLaunchKernelGGL((attn_bwd_kv_kernel<T, DD>), grid, block, 0, s, (const T*)q, (const T*)k, (const T*)v, ld, (const T*)dO, \
-                       ldo, lse, delta, (T*)dk, (T*)dv, ldd, B, N, Hh, scale)
+                       ldo, lse, delta, (T*)dk, (T*)dv, ldd, B, N, Hh, scale, drop...)
     if (D == 64) { GO(64); } else if (D == 32) { GO(32); } else if (D == 16) { GO(16); } else return UMI_ERR_UNSUPPORTED;
 #undef GO
     return UMI_OK;
 }
-extern "C" int umi_attn_bwd_flags(const void* q, const void* k, const void* v, int ld, const void* o, const void* dO, int ldo,
-                                  const float* lse, void* dq, void* dk, void* dv, int ldd, float* delta, int B, int N, int heads,
-                                  int D, int dtype, int flags, umi_stream_t st) {
+static int attn_bwd_any(const void* q, const void* k, const void* v, int ld, const void* o, const void* dO, int ldo,
+                        const float* lse, void* dq, void* dk, void* dv, int ldd, float* delta, int B, int N, int heads,
+                        int D, int dtype, int flags, const UmiAttnDrop* drop, umi_stream_t st) {
     if (!q || !k || !v || !o || !dO || !lse || !dq || !dk || !dv || !delta) return UMI_ERR_BADARG;
     const int kernel = attn_kernel_of(D, ld, ldo, ldd, dtype, flags, q, k, v,
                                       (uintptr_t)o | (uintptr_t)dO | (uintptr_t)dq | (uintptr_t)dk | (uintptr_t)dv);
-    if (kernel == 1) return umi_attn_bwd_mfma(q, k, v, ld, o, dO, ldo, lse, dq, dk, dv, ldd, delta, B, N, heads, (hipStream_t)st);
+    if (kernel == 1)
+        return umi_attn_bwd_mfma(q, k, v, ld, o, dO, ldo, lse, dq, dk, dv, ldd, delta, B, N, heads, drop, (hipStream_t)st);
     if (kernel == 2) {
         if (B <= 0 || N <= 0 || heads <= 0) return UMI_ERR_BADARG;
-        return umi_attn_bwd_f32_mfma(q, k, v, ld, o, dO, ldo, lse, dq, dk, dv, ldd, delta, B, N, heads, (hipStream_t)st);
+        return umi_attn_bwd_f32_mfma(q, k, v, ld, o, dO, ldo, lse, dq, dk, dv, ldd, delta, B, N, heads, drop, (hipStream_t)st);
     }
     int rc;
-    if (dtype == UMI_F32) rc = attn_bwd_t<float>(q, k, v, ld, o, dO, ldo, lse, dq, dk, dv, ldd, delta, B, N, heads, D, (hipStream_t)st);
-    else if (dtype == UMI_F16) rc = attn_bwd_t<half_t>(q, k, v, ld, o, dO, ldo, lse, dq, dk, dv, ldd, delta, B, N, heads, D, (hipStream_t)st);
+    if (dtype == UMI_F32)
+        rc = drop ? attn_bwd_t<float>(q, k, v, ld, o, dO, ldo, lse, dq, dk, dv, ldd, delta, B, N, heads, D, (hipStream_t)st, *drop)
+                  : attn_bwd_t<float>(q, k, v, ld, o, dO, ldo, lse, dq, dk, dv, ldd, delta, B, N, heads, D, (hipStream_t)st);
+    else if (dtype == UMI_F16)
+        rc = drop ? attn_bwd_t<half_t>(q, k, v, ld, o, dO, ldo, lse, dq, dk, dv, ldd, delta, B, N, heads, D, (hipStream_t)st, *drop)
+                  : attn_bwd_t<half_t>(q, k, v, ld, o, dO, ldo, lse, dq, dk, dv, ldd, delta, B, N, heads, D, (hipStream_t)st);
     else return UMI_ERR_BADARG;
     if (rc) return rc;
     UMI_LAUNCH_CHECK();
     return UMI_OK;
 }
+extern "C" int umi_attn_bwd_flags(const void* q, const void* k, const void* v, int ld, const void* o, const void* dO, int ldo,
+                                  const float* lse, void* dq, void* dk, void* dv, int ldd, float* delta, int B, int N, int heads,
+                                  int D, int dtype, int flags, umi_stream_t st) {
+    return attn_bwd_any(q, k, v, ld, o, dO, ldo, lse, dq, dk, dv, ldd, delta, B, N, heads, D, dtype, flags, nullptr, st);
+}
 extern "C" int umi_attn_bwd(const void* q, const void* k, const void* v, int ld, const void* o, const void* dO, int ldo,
                             const float* lse, void* dq, void* dk, void* dv, int ldd, float* delta, int B, int N, int heads,
                             int D, int dtype, umi_stream_t st) {
     return umi_attn_bwd_flags(q, k, v, ld, o, dO, ldo, lse, dq, dk, dv, ldd, delta, B, N, heads, D, dtype, 0, st);
+}
+
+// Attention-probability dropout (include/unetmi.h).  p is checked before anything else; p == 0 IS the call without dropout;
+// otherwise the family umi_attn_plan names runs its DROP instantiation -- dropout never changes the selection.
+static bool attn_drop_of(float p, unsigned seed, const unsigned* seed_dev, UmiAttnDrop* d) {
+    if (!(p >= 0.f && p <= 1.f)) return false;
+    d->thr = (unsigned)ceilf(p * 16777216.f);
+    d->inv_keep = p < 1.f ? 1.f / (1.f - p) : 0.f;
+    d->seed = seed;
+    d->seed_dev = seed_dev;
+    return true;
+}
+extern "C" int umi_attn_fwd_dropout(const void* q, const void* k, const void* v, int ld, void* o, int ldo, float* lse, int B,
+                                    int N, int heads, int D, int dtype, int flags, float p, unsigned seed,
+                                    const unsigned* seed_dev, umi_stream_t st) {
+    UmiAttnDrop d;
+    if (!attn_drop_of(p, seed, seed_dev, &d)) return UMI_ERR_BADARG;
+    return attn_fwd_any(q, k, v, ld, o, ldo, lse, B, N, heads, D, dtype, flags, p > 0.f ? &d : nullptr, st);
+}
+extern "C" int umi_attn_bwd_dropout(const void* q, const void* k, const void* v, int ld, const void* o, const void* dO, int ldo,
+                                    const float* lse, void* dq, void* dk, void* dv, int ldd, float* delta, int B, int N,
+                                    int heads, int D, int dtype, int flags, float p, unsigned seed, const unsigned* seed_dev,
+                                    umi_stream_t st) {
+    UmiAttnDrop d;
+    if (!attn_drop_of(p, seed, seed_dev, &d)) return UMI_ERR_BADARG;
+    return attn_bwd_any(q, k, v, ld, o, dO, ldo, lse, dq, dk, dv, ldd, delta, B, N, heads, D, dtype, flags,
+                        p > 0.f ? &d : nullptr, st);
 }
 
 extern "C" int umi_bilinear2x(const void* x, int ldx, const void* tx, void* y, int ldy, int backward, int N, int H, int W, int C,

@@ -46,6 +46,7 @@ class TUTape(Tape):
     def __init__(self, *a, **k):
         super().__init__(*a, **k)
         self.attn_flags = 0               # compute_dtype "fp32_mfma_attn": lib.UMI_ATTN_F32_MFMA, passed to the attention calls
+        self._attn_seed_dev = None        # this forward's snapshot of the device step counter (_attn_kw)
         d = self.deferred
         d.marks = True          # fills stay deferred under a gradient sink: flush_mark runs them group by group of layers
         # weight gradients of the token linears, run per SHAPE: one launch for the twelve encoder layers' fc1 weights, one for
@@ -469,28 +470,44 @@ class TUTape(Tape):
             self.steps.append(bwd)
         return o
 
-    def _attn_kw(self):
-        """The attention calls' keyword: none without a flag, so that a flag-less tape calls ops_tu.attn_fwd / attn_bwd exactly as
-        before (positional arguments only)."""
-        return {"flags": self.attn_flags} if self.attn_flags else {}
+    def _attn_kw(self, p=0.0):
+        """The attention calls' keywords: none without a flag and without dropout, so that such a tape calls ops_tu.attn_fwd /
+        attn_bwd exactly as before (positional arguments only).
 
-    def attention(self, q: Act, k: Act, v: Act, heads):
+        Attention-probability dropout (training, p > 0) stores no mask: forward, dQ and dK/dV kernels each regenerate it from
+        (seed, device counter), so the backward call gets the SAME dictionary.  The site takes its seed like the tape's other
+        dropout sites (`_drop_count` advances once per site in forward order; untouched for p = 0 or in eval mode).  The other
+        sites keep their mask bytes and do not care that dropout_seeds advances the device counter on every training forward;
+        a regenerating site does (forward A, forward B, backward A would rebuild A's mask with B's counter), so the tape
+        snapshots the counter ONCE per forward into a 4-byte device scalar of its own -- one device copy, capturable, made only
+        when an attention site drops -- and every layer's forward and backward read that snapshot."""
+        kw = {"flags": self.attn_flags} if self.attn_flags else {}
+        if not self.training or p <= 0.0:
+            return kw
+        if self._seed_dev is not None and self._attn_seed_dev is None:
+            self._attn_seed_dev = self._seed_dev.clone()
+        self._drop_count += 1
+        kw.update(p=float(p), seed=self._seed * 7919 + self._drop_count, seed_dev=self._attn_seed_dev)
+        return kw
+
+    def attention(self, q: Act, k: Act, v: Act, heads, p=0.0):
         out = torch.empty_like(q.raw)
-        lse = ops_tu.attn_fwd(q.raw, k.raw, v.raw, out, heads, **self._attn_kw())
+        kw = self._attn_kw(p)
+        lse = ops_tu.attn_fwd(q.raw, k.raw, v.raw, out, heads, **kw)
         o = Act(out, None)
         if self.record:
             def bwd():
                 if o.grad is None:
                     return
                 dq, dk, dv = torch.empty_like(q.raw), torch.empty_like(q.raw), torch.empty_like(q.raw)
-                ops_tu.attn_bwd(q.raw, k.raw, v.raw, out, o.grad, lse, dq, dk, dv, heads, **self._attn_kw())
+                ops_tu.attn_bwd(q.raw, k.raw, v.raw, out, o.grad, lse, dq, dk, dv, heads, **kw)
                 self._give(q, dq)
                 self._give(k, dk)
                 self._give(v, dv)
             self.steps.append(bwd)
         return o
 
-    def qkv_attention(self, a: Act, query, key, value, heads):
+    def qkv_attention(self, a: Act, query, key, value, heads, p=0.0):
         """softmax(QK^T/sqrt(d))V with the three projections of `a` (reference Attention.forward, vit_seg_modeling.py:73-91)
         run as ONE GEMM of width 3C: q/k/v are channel slices of one buffer, so the data gradient is one GEMM with
         K = 3C (no summing of three partial gradients) and the three weight / bias gradients come out of one launch each.
@@ -517,15 +534,15 @@ class TUTape(Tape):
         ops.conv_fwd(a.raw, a.tx, packed("conv_fwd"), bcat, qkv, 1, 1, 1, 0, flags=self._fk(1, 1, 1, 0, C, 3 * C))
         q, k, v = (qkv[..., i * C:(i + 1) * C] for i in range(3))
         out = self.alloc(N, H, W, C, device=a.raw.device)
-        lse = ops_tu.attn_fwd(q, k, v, out, heads, **self._attn_kw())
+        kw = self._attn_kw(p)                           # (with p > 0: this site's seed and the counter snapshot, see there)
+        lse = ops_tu.attn_fwd(q, k, v, out, heads, **kw)
         o = Act(out, None)
         if self.record:
             def bwd():
                 if o.grad is None:
                     return
                 dqkv = self.alloc(N, H, W, 3 * C, device=out.device)
-                ops_tu.attn_bwd(q, k, v, out, o.grad, lse, *(dqkv[..., i * C:(i + 1) * C] for i in range(3)), heads,
-                                **self._attn_kw())
+                ops_tu.attn_bwd(q, k, v, out, o.grad, lse, *(dqkv[..., i * C:(i + 1) * C] for i in range(3)), heads, **kw)
                 if self.grad_sink is not None:
                     # three items of the grouped launches, each writing its own bucket slot (the fused [3C, C] gradient would
                     # have to be copied into the three slots afterwards)

@@ -159,24 +159,35 @@ def linear_fused(x, wp8, bias, y, epi, p, seed, seed_dev, mask, aux=None, y2=Non
                        _dt(x), _stream())
 
 
-def attn_fwd(q, k, v, o, heads, flags=0):
-    """flags: lib.UMI_ATTN_F32_MFMA opts an fp32 / head-dim-64 call into the fp32 matrix-core kernels (ignored elsewhere)."""
+def attn_fwd(q, k, v, o, heads, flags=0, p=0.0, seed=0, seed_dev=None):
+    """flags: lib.UMI_ATTN_F32_MFMA opts an fp32 / head-dim-64 call into the fp32 matrix-core kernels (ignored elsewhere).
+    p > 0: attention-probability dropout (umi_attn_fwd_dropout), mask regenerated from (seed, seed_dev: optional int32 device
+    scalar); the backward must be given the same three.  p = 0 is the call without dropout, argument for argument."""
     B, _, N, C = q.shape
     D = C // heads
     ld = _nhwc(q)[4]
     assert _nhwc(k)[4] == ld and _nhwc(v)[4] == ld
     lse = torch.empty(B * heads * N, dtype=torch.float32, device=q.device)
+    if p > 0:
+        L.call("umi_attn_fwd_dropout", q.data_ptr(), k.data_ptr(), v.data_ptr(), ld, o.data_ptr(), _nhwc(o)[4], lse.data_ptr(),
+               B, N, heads, D, _dt(q), flags, p, seed & 0xFFFFFFFF, _ptr(seed_dev), _stream())
+        return lse
     L.call("umi_attn_fwd_flags", q.data_ptr(), k.data_ptr(), v.data_ptr(), ld, o.data_ptr(), _nhwc(o)[4], lse.data_ptr(), B,
            N, heads, D, _dt(q), flags, _stream())
     return lse
 
 
-def attn_bwd(q, k, v, o, dO, lse, dq, dk, dv, heads, flags=0):
+def attn_bwd(q, k, v, o, dO, lse, dq, dk, dv, heads, flags=0, p=0.0, seed=0, seed_dev=None):
     B, _, N, C = q.shape
     D = C // heads
     ld, ldo, ldd = _nhwc(q)[4], _nhwc(o)[4], _nhwc(dq)[4]
     assert _nhwc(dO)[4] == ldo and _nhwc(dk)[4] == ldd and _nhwc(dv)[4] == ldd
     delta = torch.empty_like(lse)
+    if p > 0:
+        L.call("umi_attn_bwd_dropout", q.data_ptr(), k.data_ptr(), v.data_ptr(), ld, o.data_ptr(), dO.data_ptr(), ldo,
+               lse.data_ptr(), dq.data_ptr(), dk.data_ptr(), dv.data_ptr(), ldd, delta.data_ptr(), B, N,
+               heads, D, _dt(q), flags, p, seed & 0xFFFFFFFF, _ptr(seed_dev), _stream())
+        return
     L.call("umi_attn_bwd_flags", q.data_ptr(), k.data_ptr(), v.data_ptr(), ld, o.data_ptr(), dO.data_ptr(), ldo,
            lse.data_ptr(), dq.data_ptr(), dk.data_ptr(), dv.data_ptr(), ldd, delta.data_ptr(), B, N,
            heads, D, _dt(q), flags, _stream())
