@@ -147,6 +147,17 @@ int umi_bn_finalize(const float* stat_part, int rows, int C, double count,
                     const float* gamma, const float* beta, float eps, float momentum,
                     float* running_mean, float* running_var,
                     void* tx_out, float* rstd_out, umi_stream_t stream);
+/* umi_bn_finalize in two steps, for a data-parallel group that normalises with the statistics of its WHOLE batch: the ranks add
+ * their sums (and pixel counts) between the two.
+ *   umi_bn_stat_sums      sums[2][C] (float64) = per-channel sum and sum of squares of stat_part[rows][2][C], added in the order
+ *                         umi_bn_finalize adds them (both of its reduction forms, chosen by the same rule);
+ *   umi_bn_finalize_sums  everything umi_bn_finalize does after its reduction, from such sums and a count.
+ * With count = this rank's pixels and its own sums the pair leaves the bits umi_bn_finalize leaves. */
+int umi_bn_stat_sums(const float* stat_part, int rows, int C, double* sums, umi_stream_t stream);
+int umi_bn_finalize_sums(const double* sums, int C, double count,
+                         const float* gamma, const float* beta, float eps, float momentum,
+                         float* running_mean, float* running_var,
+                         void* tx_out, float* rstd_out, umi_stream_t stream);
 
 /* MaxPool2d(2) of the transformed tensor (reference Model.py:36,42). Floor mode. */
 int umi_pool2_fwd(const void* x, int ldx, const void* tx, void* y, int ldy,
@@ -168,6 +179,12 @@ int umi_bn_bwd_reduce(const void* da, int ldda, const void* y, int ldy, const vo
 int umi_bn_bwd_apply(void* da, int ldda, const void* y, int ldy, const void* tx,
                      const float* rstd, const float* sum_dz, const float* sum_dzx,
                      long M, int C, int dtype, umi_stream_t stream);
+/* umi_bn_bwd_apply over M local rows whose two sums are those of `count` rows (a data-parallel group's whole batch: the sums added
+ * over the ranks, count = all their rows): dy = gamma*rstd * (dz - sum_dz/count - xhat*sum_dzx/count).  The quotient is formed on
+ * the device as in umi_bn_bwd_apply, which is this call with count = M. */
+int umi_bn_bwd_apply_count(void* da, int ldda, const void* y, int ldy, const void* tx,
+                           const float* rstd, const float* sum_dz, const float* sum_dzx,
+                           long M, long count, int C, int dtype, umi_stream_t stream);
 
 /* Fusion of the two previous steps for a DoubleConv's inner layer (reference Model.py:15-22): the 3x3 data gradient that
  * produces `da` = d(activated output) of a BatchNorm+ReLU layer also emits stage 1 of that layer's reduction
@@ -290,6 +307,13 @@ int umi_conv_wgrad_bnapply(const void* x, int ldx, const void* txa, const void* 
                            int lddz, float* dW, long s_co, long s_ci, long s_t, float out_scale, int N, int H, int W,
                            int Ci, int Co, int R, int S, int stride, int pad, int dtype, int flags, void* ws,
                            size_t ws_bytes, umi_stream_t stream);
+/* The same with the divisor of the two sums given separately, as umi_bn_bwd_apply_count takes it (umi_conv_wgrad_bnapply is this
+ * call with count = N * H * W). */
+int umi_conv_wgrad_bnapply_count(const void* x, int ldx, const void* txa, const void* da, int ldda, const void* y, int ldy,
+                                 const void* tx_bn, const float* rstd, const float* sum_dz, const float* sum_dzx, void* dz,
+                                 int lddz, float* dW, long s_co, long s_ci, long s_t, float out_scale, int N, int H, int W,
+                                 int Ci, int Co, int R, int S, int stride, int pad, int dtype, int flags, long count, void* ws,
+                                 size_t ws_bytes, umi_stream_t stream);
 
 /* Per-channel sum over pixels (bias gradients): out[c] = out_scale * sum_p x[p, c]. */
 size_t umi_colsum_ws_bytes(long M, int C);
@@ -465,6 +489,20 @@ int umi_dice_ce_fwd(const float* logits, const void* target, int target_dtype, i
                     size_t ws_bytes, umi_stream_t stream);
 int umi_dice_ce_bwd(const float* logits, const void* target, int target_dtype, const float* stats, const float* gout, int N,
                     int C, long HW, float* dlogits, umi_stream_t stream);
+/* The same loss of a data-parallel group's WHOLE batch, every rank holding N of its images:
+ *   umi_dice_ce_sums        sums[3*C + 1] (float64) = {sum p*t | sum p*p | sum t | CE sum} of this rank's pixels, added in
+ *                           umi_dice_ce_fwd's order; the ranks then add their sums and their pixel counts;
+ *   umi_dice_ce_finalize    stats[3*C + 2] as umi_dice_ce_fwd leaves them, from such sums and the pixel count they cover (with this
+ *                           rank's own sums and N * HW: the bits of umi_dice_ce_fwd);
+ *   umi_dice_ce_bwd_global  dlogits = gout[0] * scale * d(loss of the stats) / d(this rank's logits): the Dice coefficients from
+ *                           `stats`, the cross-entropy weight 0.5 / count.  scale = the group's size makes the AVERAGE of the ranks'
+ *                           parameter gradients the gradient of the group's loss.  umi_dice_ce_bwd is this call with scale = 1 and
+ *                           count = N * HW. */
+int umi_dice_ce_sums(const float* logits, const void* target, int target_dtype, int N, int C, long HW, double* sums, void* ws,
+                     size_t ws_bytes, umi_stream_t stream);
+int umi_dice_ce_finalize(const double* sums, int C, double count, float* stats, umi_stream_t stream);
+int umi_dice_ce_bwd_global(const float* logits, const void* target, int target_dtype, const float* stats, const float* gout,
+                           float scale, double count, int N, int C, long HW, float* dlogits, umi_stream_t stream);
 
 /* HausdorffDTLoss (reference loss.py:146-212) on fp32 logits `pred` and targets [B,C,H,W], C == 1, 1 <= H, W <= 4096,
  * B <= 65535:

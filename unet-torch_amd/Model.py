@@ -125,7 +125,8 @@ def _run_tape(module, inputs, build, tape_cls=None, dtype=None, enter=None):
         tape = tape_cls(dtype, training=module.training, record=record,
                         loss_scale=G.default_loss_scale(dtype, N * H * W),
                         grad_sink=getattr(module, "_umi_grad_sink", None) if record else None,
-                        pack_cache=G.pack_cache_of(module), seed=seed, seed_dev=seed_dev)
+                        pack_cache=G.pack_cache_of(module), seed=seed, seed_dev=seed_dev,
+                        batch_sync=getattr(module, "_umi_batch_sync", None))
         tape.conv3x3_flags, tape.conv1x1_flags = _resolve_conv_flags(getattr(module, "_compute_dtype", None))
         tape.convt_flags = _resolve_convt_flags(getattr(module, "_compute_dtype", None))
         tape.dyn_scale = getattr(module, "_umi_dyn_scale", None)          # umi.optim.GradGuard.attach(module)

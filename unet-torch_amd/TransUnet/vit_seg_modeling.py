@@ -396,7 +396,7 @@ class VisionTransformer(nn.Module):
             tape = TUTape(dtype, training=self.training, record=record, seed=step, seed_dev=seed_dev,
                           loss_scale=G.default_loss_scale(dtype, N * H * W),
                           grad_sink=getattr(self, "_umi_grad_sink", None) if record else None,
-                          pack_cache=G.pack_cache_of(self))
+                          pack_cache=G.pack_cache_of(self), batch_sync=getattr(self, "_umi_batch_sync", None))
             flags = _resolve_conv_flags(self._compute_dtype)
             tape.conv3x3_flags, tape.conv1x1_flags = flags if flags[1] else (0, 0)       # "fp32_mfma" sets no flag on this tape
             tape.attn_flags = _resolve_attn_flags(self._compute_dtype)

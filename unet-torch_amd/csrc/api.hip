@@ -347,18 +347,18 @@ extern "C" int umi_conv_wgrad_group(int n, const void* const* x, int ldx, const 
 // expression, bit for bit), is formed while dA is staged for the matrix cores and written to `dz` once for the
 // data-gradient kernel.  `da` is left untouched.  UMI_ERR_UNSUPPORTED where the warp-specialised 3x3 kernel does not apply:
 // the caller then runs umi_bn_bwd_apply + umi_conv_wgrad.
-extern "C" int umi_conv_wgrad_bnapply(const void* x, int ldx, const void* txa, const void* da, int ldda, const void* y, int ldy,
+extern "C" int umi_conv_wgrad_bnapply_count(const void* x, int ldx, const void* txa, const void* da, int ldda, const void* y, int ldy,
                                       const void* tx_bn, const float* rstd, const float* sum_dz, const float* sum_dzx,
                                       void* dz, int lddz, float* dW, long s_co, long s_ci, long s_t, float out_scale, int N,
                                       int H, int W, int Ci, int Co, int R, int S, int stride, int pad, int dtype, int flags,
-                                      void* ws, size_t ws_bytes, umi_stream_t stream) {
+                                      long count, void* ws, size_t ws_bytes, umi_stream_t stream) {
     if (!x || !da || !y || !tx_bn || !rstd || !sum_dz || !sum_dzx || !dW || !ws || N <= 0 || H <= 0 || W <= 0 || Ci <= 0 ||
-        Co <= 0 || ldx < Ci || ldda < Co || ldy < Co || (dz && (lddz < Co || dz == da || dz == y)))
+        Co <= 0 || count <= 0 || ldx < Ci || ldda < Co || ldy < Co || (dz && (lddz < Co || dz == da || dz == y)))
         return UMI_ERR_BADARG;
     const WgradProblem p = wgrad_problem(N, H, W, Ci, Co, R, S, stride, pad, H, W, ldx, ldda, dtype, flags, txa != nullptr, false);
     const WgradPath path = umi_conv_wgrad_path(p);
     const WgradOut o{dW, s_co, s_ci, s_t, out_scale, ws, ws_bytes, nullptr, nullptr};
-    const WgradBnApply bna{y, ldy, tx_bn, rstd, sum_dz, sum_dzx, dz, lddz};
+    const WgradBnApply bna{y, ldy, tx_bn, rstd, sum_dz, sum_dzx, dz, lddz, count};
     if (!dz) {
         // dz == NULL: nothing else needs dz (the layer's input takes no gradient: the network's first conv) -- the narrow-input
         // weight-gradient kernel forms it on the fly and never stores it
@@ -368,4 +368,15 @@ extern "C" int umi_conv_wgrad_bnapply(const void* x, int ldx, const void* txa, c
     if (path != WGRAD_MFMA3X3 || ldy % 8 || lddz % 8 || (long)H * W * (ldy > lddz ? ldy : lddz) * 2 >= 0x7FFFFFF0L)
         return UMI_ERR_UNSUPPORTED;
     return umi_wgrad3x3_mfma(p, x, txa, da, o, (hipStream_t)stream, &bna);
+}
+
+extern "C" int umi_conv_wgrad_bnapply(const void* x, int ldx, const void* txa, const void* da, int ldda, const void* y, int ldy,
+                                      const void* tx_bn, const float* rstd, const float* sum_dz, const float* sum_dzx,
+                                      void* dz, int lddz, float* dW, long s_co, long s_ci, long s_t, float out_scale, int N,
+                                      int H, int W, int Ci, int Co, int R, int S, int stride, int pad, int dtype, int flags,
+                                      void* ws, size_t ws_bytes, umi_stream_t stream) {
+    if (N <= 0 || H <= 0 || W <= 0) return UMI_ERR_BADARG;
+    return umi_conv_wgrad_bnapply_count(x, ldx, txa, da, ldda, y, ldy, tx_bn, rstd, sum_dz, sum_dzx, dz, lddz, dW, s_co, s_ci, s_t,
+                                        out_scale, N, H, W, Ci, Co, R, S, stride, pad, dtype, flags, (long)N * H * W, ws, ws_bytes,
+                                        stream);
 }

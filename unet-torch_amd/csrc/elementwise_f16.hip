@@ -182,7 +182,7 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_v8(half_t* __restrict__ da, 
                                                        int ldy, const float4* __restrict__ tx,
                                                        const float* __restrict__ rstd,
                                                        const float* __restrict__ sum_dz,
-                                                       const float* __restrict__ sum_dzx, long M, int C, int RPW) {
+                                                       const float* __restrict__ sum_dzx, long M, long count, int C, int RPW) {
     __shared__ float4 s_t[8][BNA_GB];
     __shared__ float s_k[3][8][BNA_GB];
     const int tid = threadIdx.x;
@@ -191,7 +191,7 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_v8(half_t* __restrict__ da, 
     const int PL = 256 / Gb;
     const int cgl = tid & (Gb - 1), pl = tid / Gb;
     const int cb = blockIdx.y * (Gb * 8);                      // first channel of this workgroup
-    const float invM = 1.f / (float)M;
+    const float invM = 1.f / (float)count;                     // count = M, or the rows of the whole data-parallel batch
     for (int i = tid; i < Gb * 8; i += 256) {
         const int c = cb + i;
         s_t[i & 7][i >> 3] = tx[c];
@@ -467,13 +467,13 @@ bool umi_bn_bwd_reduce1_f16v(const void* da, int ldda, const void* y, int ldy, c
 }
 
 bool umi_bn_bwd_apply_f16v(void* da, int ldda, const void* y, int ldy, const void* tx, const float* rstd,
-                           const float* sum_dz, const float* sum_dzx, long M, int C, hipStream_t s) {
+                           const float* sum_dz, const float* sum_dzx, long M, long count, int C, hipStream_t s) {
     if (!vec_ok(C, ldda, ldy, da, y)) return false;
     const int G = C / 8, Gb = G < BNA_GB ? G : BNA_GB, PL = 256 / Gb, gy = G / Gb;
     const int rpw = bna_rows_per_lane(M, PL, gy) * PL;
     if ((long)rpw * (ldda > ldy ? ldda : ldy) >= (1L << 30)) return false;      // 32-bit offsets inside a workgroup
     hipLaunchKernelGGL(bn_bwd_apply_v8, dim3((unsigned)((M + rpw - 1) / rpw), gy), dim3(256), 0, s, (half_t*)da, ldda,
-                       (const half_t*)y, ldy, (const float4*)tx, rstd, sum_dz, sum_dzx, M, C, rpw);
+                       (const half_t*)y, ldy, (const float4*)tx, rstd, sum_dz, sum_dzx, M, count, C, rpw);
     return true;
 }
 

@@ -364,11 +364,9 @@ __device__ __forceinline__ void bn_finalize_channel(int c, double sum, double su
 // ------------------------------------------------------------------------------------------
 // BatchNorm statistics finalize: fixed-order double reduction (one block per channel, or the 2-D form above).
 // ------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void bn_finalize_kernel(const float* __restrict__ part, int rows, int C, double count,
-                                                          const float* __restrict__ gamma, const float* __restrict__ beta,
-                                                          float eps, float momentum, float* __restrict__ rmean,
-                                                          float* __restrict__ rvar, float4* __restrict__ tx_out,
-                                                          float* __restrict__ rstd_out) {
+// Sum and sum of squares of channel c = blockIdx.x over the partial rows, by one workgroup of 256 threads: the totals are
+// returned in thread 0 (true there).  Shared by the finalize and by umi_bn_stat_sums, so both add in the same order.
+__device__ __forceinline__ bool bn_rows_channel(const float* __restrict__ part, int rows, int C, double& s_out, double& q_out) {
     __shared__ double sh[2][256];
     const int c = blockIdx.x, tid = threadIdx.x;
     double s = 0.0, q = 0.0;
@@ -396,7 +394,30 @@ __global__ __launch_bounds__(256) void bn_finalize_kernel(const float* __restric
         if (tid < o) { sh[0][tid] += sh[0][tid + o]; sh[1][tid] += sh[1][tid + o]; }
         __syncthreads();
     }
-    if (tid == 0) bn_finalize_channel(c, sh[0][0], sh[1][0], count, gamma, beta, eps, momentum, rmean, rvar, tx_out, rstd_out);
+    s_out = sh[0][0];
+    q_out = sh[1][0];
+    return tid == 0;
+}
+
+__global__ __launch_bounds__(256) void bn_finalize_kernel(const float* __restrict__ part, int rows, int C, double count,
+                                                          const float* __restrict__ gamma, const float* __restrict__ beta,
+                                                          float eps, float momentum, float* __restrict__ rmean,
+                                                          float* __restrict__ rvar, float4* __restrict__ tx_out,
+                                                          float* __restrict__ rstd_out) {
+    double s, q;
+    if (bn_rows_channel(part, rows, C, s, q))
+        bn_finalize_channel(blockIdx.x, s, q, count, gamma, beta, eps, momentum, rmean, rvar, tx_out, rstd_out);
+}
+
+// the same reduction, stopped at the float64 sums: sums[0][C] = sum, sums[1][C] = sum of squares (what ranks of a data-parallel
+// group add up before umi_bn_finalize_sums)
+__global__ __launch_bounds__(256) void bn_stat_sums_kernel(const float* __restrict__ part, int rows, int C,
+                                                           double* __restrict__ sums) {
+    double s, q;
+    if (bn_rows_channel(part, rows, C, s, q)) {
+        sums[blockIdx.x] = s;
+        sums[C + blockIdx.x] = q;
+    }
 }
 
 __global__ __launch_bounds__(256) void bn_finalize2d_kernel(const float* __restrict__ part, int rows, int C, double count,
@@ -411,6 +432,44 @@ __global__ __launch_bounds__(256) void bn_finalize2d_kernel(const float* __restr
     const double q = __shfl(tot, (lane & 31) + 32, 64);
     const int c = blockIdx.x * 32 + lane;
     if (lane < 32 && c < C) bn_finalize_channel(c, tot, q, count, gamma, beta, eps, momentum, rmean, rvar, tx_out, rstd_out);
+}
+
+__global__ __launch_bounds__(256) void bn_stat_sums2d_kernel(const float* __restrict__ part, int rows, int C,
+                                                             double* __restrict__ sums, int region) {
+    double tot = 0.0;
+    if (!red2d_block(part, rows, C, true, region, tot)) return;
+    const int lane = threadIdx.x & 63, c = blockIdx.x * 32 + (lane & 31);
+    if (c < C) sums[(lane >> 5) * C + c] = tot;
+}
+
+__global__ __launch_bounds__(256) void bn_finalize_sums_kernel(const double* __restrict__ sums, int C, double count,
+                                                               const float* __restrict__ gamma, const float* __restrict__ beta,
+                                                               float eps, float momentum, float* __restrict__ rmean,
+                                                               float* __restrict__ rvar, float4* __restrict__ tx_out,
+                                                               float* __restrict__ rstd_out) {
+    const int c = blockIdx.x * 256 + threadIdx.x;
+    if (c < C) bn_finalize_channel(c, sums[c], sums[C + c], count, gamma, beta, eps, momentum, rmean, rvar, tx_out, rstd_out);
+}
+
+extern "C" int umi_bn_stat_sums(const float* stat_part, int rows, int C, double* sums, umi_stream_t stream) {
+    if (!stat_part || !sums || rows <= 0 || C <= 0) return UMI_ERR_BADARG;
+    if (red2d_ok(rows, C))
+        hipLaunchKernelGGL(bn_stat_sums2d_kernel, dim3((C + 31) / 32, (rows + RED_RPS - 1) / RED_RPS), dim3(256), 0,
+                           (hipStream_t)stream, stat_part, rows, C, sums, red2d_region());
+    else
+        hipLaunchKernelGGL(bn_stat_sums_kernel, dim3(C), dim3(256), 0, (hipStream_t)stream, stat_part, rows, C, sums);
+    UMI_LAUNCH_CHECK();
+    return UMI_OK;
+}
+
+extern "C" int umi_bn_finalize_sums(const double* sums, int C, double count, const float* gamma, const float* beta, float eps,
+                                    float momentum, float* running_mean, float* running_var, void* tx_out, float* rstd_out,
+                                    umi_stream_t stream) {
+    if (!sums || !tx_out || C <= 0 || !(count > 0)) return UMI_ERR_BADARG;
+    hipLaunchKernelGGL(bn_finalize_sums_kernel, dim3((C + 255) / 256), dim3(256), 0, (hipStream_t)stream, sums, C, count, gamma,
+                       beta, eps, momentum, running_mean, running_var, (float4*)tx_out, rstd_out);
+    UMI_LAUNCH_CHECK();
+    return UMI_OK;
 }
 
 extern "C" int umi_bn_finalize(const float* stat_part, int rows, int C, double count, const float* gamma,
@@ -664,8 +723,9 @@ void umi_launch_reduce_rows2(const float* ws, int rows, int C, float* out0, floa
 template <typename T>
 __global__ void bn_bwd_apply_kernel(T* __restrict__ da, int ldda, const T* __restrict__ y, int ldy,
                                     const float4* __restrict__ tx, const float* __restrict__ rstd,
-                                    const float* __restrict__ sum_dz, const float* __restrict__ sum_dzx, long M, int C) {
-    const float invM = 1.f / (float)M;
+                                    const float* __restrict__ sum_dz, const float* __restrict__ sum_dzx, long M, long count,
+                                    int C) {
+    const float invM = 1.f / (float)count;                  // count = M, or the rows of the whole data-parallel batch
     long total = M * C;
     for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
         int c = (int)(i % C);
@@ -704,23 +764,30 @@ extern "C" int umi_bn_bwd_reduce(const void* da, int ldda, const void* y, int ld
     return UMI_OK;
 }
 
-extern "C" int umi_bn_bwd_apply(void* da, int ldda, const void* y, int ldy, const void* tx, const float* rstd,
-                                const float* sum_dz, const float* sum_dzx, long M, int C, int dtype,
-                                umi_stream_t stream) {
-    if (!da || !y || !tx || !rstd || M <= 0 || C <= 0) return UMI_ERR_BADARG;
+extern "C" int umi_bn_bwd_apply_count(void* da, int ldda, const void* y, int ldy, const void* tx, const float* rstd,
+                                      const float* sum_dz, const float* sum_dzx, long M, long count, int C, int dtype,
+                                      umi_stream_t stream) {
+    if (!da || !y || !tx || !rstd || !sum_dz || !sum_dzx || M <= 0 || count <= 0 || C <= 0) return UMI_ERR_BADARG;
     long total = M * C;
     int grid = (int)((total + 255) / 256);
     if (grid > 16384) grid = 16384;
     hipStream_t s = (hipStream_t)stream;
-    if (dtype == UMI_F16 && umi_bn_bwd_apply_f16v(da, ldda, y, ldy, tx, rstd, sum_dz, sum_dzx, M, C, s)) {
+    if (dtype == UMI_F16 && umi_bn_bwd_apply_f16v(da, ldda, y, ldy, tx, rstd, sum_dz, sum_dzx, M, count, C, s)) {
         UMI_LAUNCH_CHECK();
         return UMI_OK;
     }
-    if (dtype == UMI_F32) hipLaunchKernelGGL(bn_bwd_apply_kernel<float>, dim3(grid), dim3(256), 0, s, (float*)da, ldda, (const float*)y, ldy, (const float4*)tx, rstd, sum_dz, sum_dzx, M, C);
-    else if (dtype == UMI_F16) hipLaunchKernelGGL(bn_bwd_apply_kernel<half_t>, dim3(grid), dim3(256), 0, s, (half_t*)da, ldda, (const half_t*)y, ldy, (const float4*)tx, rstd, sum_dz, sum_dzx, M, C);
+    if (dtype == UMI_F32) hipLaunchKernelGGL(bn_bwd_apply_kernel<float>, dim3(grid), dim3(256), 0, s, (float*)da, ldda, (const float*)y, ldy, (const float4*)tx, rstd, sum_dz, sum_dzx, M, count, C);
+    else if (dtype == UMI_F16) hipLaunchKernelGGL(bn_bwd_apply_kernel<half_t>, dim3(grid), dim3(256), 0, s, (half_t*)da, ldda, (const half_t*)y, ldy, (const float4*)tx, rstd, sum_dz, sum_dzx, M, count, C);
     else return UMI_ERR_BADARG;
     UMI_LAUNCH_CHECK();
     return UMI_OK;
+}
+
+extern "C" int umi_bn_bwd_apply(void* da, int ldda, const void* y, int ldy, const void* tx, const float* rstd,
+                                const float* sum_dz, const float* sum_dzx, long M, int C, int dtype,
+                                umi_stream_t stream) {
+    if (!da || !y || !tx || !rstd || M <= 0 || C <= 0) return UMI_ERR_BADARG;
+    return umi_bn_bwd_apply_count(da, ldda, y, ldy, tx, rstd, sum_dz, sum_dzx, M, M, C, dtype, stream);
 }
 
 // ------------------------------------------------------------------------------------------

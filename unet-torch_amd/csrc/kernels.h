@@ -113,7 +113,8 @@ struct WgradOut {
 };
 // stage 3 of the BatchNorm(+ReLU) backward formed while the gradient operand is staged (umi_conv_wgrad_bnapply): `dy` is then
 // the gradient of the ACTIVATED output
-struct WgradBnApply { const void* y; int ldy; const void* tx_bn; const float *rstd, *sum_dz, *sum_dzx; void* dz; int lddz; };
+struct WgradBnApply { const void* y; int ldy; const void* tx_bn; const float *rstd, *sum_dz, *sum_dzx; void* dz; int lddz;
+                      long count; };   // count: the divisor of the two sums (N * H * W, or the rows of the whole data-parallel batch)
 enum WgradPath { WGRAD_MFMA3X3_F32, WGRAD_GEMM_F32, WGRAD_CONVT_F32, WGRAD_MFMA3X3, WGRAD_MFMA1X1, WGRAD_T, WGRAD_GATHER, WGRAD_STEM, WGRAD_HEAD, WGRAD_ROOT, WGRAD_HEAD3, WGRAD_GENERIC };
 
 bool umi_wgrad3x3_f32_mfma_ok(const WgradProblem& p);   // conv_mfma_f32.hip: only under UMI_CONV_F32_MFMA
@@ -198,7 +199,7 @@ bool umi_bn_stats_f16v(const void* x, int ldx, float* part, long M, int C, hipSt
 bool umi_bn_bwd_reduce1_f16v(const void* da, int ldda, const void* y, int ldy, const void* tx, const float* rstd, float* ws,
                              long M, int C, hipStream_t s);
 bool umi_bn_bwd_apply_f16v(void* da, int ldda, const void* y, int ldy, const void* tx, const float* rstd,
-                           const float* sum_dz, const float* sum_dzx, long M, int C, hipStream_t s);
+                           const float* sum_dz, const float* sum_dzx, long M, long count, int C, hipStream_t s);
 bool umi_pool2_fwd_f16v(const void* x, int ldx, const void* tx, void* y, int ldy, int N, int H, int W, int C,
                         hipStream_t s);
 bool umi_pool2_bwd_f16v(const void* dp, int lddp, const void* x, int ldx, const void* tx, void* da, int ldda,

@@ -72,13 +72,11 @@ __global__ __launch_bounds__(256) void dice_ce_stats_kernel(const float* __restr
             red[0][threadIdx.x] + red[1][threadIdx.x] + red[2][threadIdx.x] + red[3][threadIdx.x];
 }
 
-// stats out: [A | B | T | ce_sum | loss]  (3*NC + 2 floats).  1,024 threads = 32 columns x 32 row lanes; lane l sums rows
-// l, l+32, ... in fp64, then the 32 lane sums are added in lane order (deterministic).
-__global__ __launch_bounds__(1024) void dice_ce_finalize_kernel(const float* __restrict__ part, int rows, int NC, long total,
-                                                                float* __restrict__ stats) {
+// Column sums of the partial rows by one workgroup of 1,024 threads = 32 columns x 32 row lanes; lane l sums rows l, l+32, ... in
+// fp64, then the 32 lane sums are added in lane order (deterministic).  sums[col] is valid in threads < 32 on return, and in
+// every thread after the next barrier.
+__device__ __forceinline__ void dice_ce_col_sums(const float* __restrict__ part, int rows, int K, double* sums) {
     __shared__ double lanes[32][33];
-    __shared__ double sums[32];
-    const int K = 3 * NC + 1;
     const int col = threadIdx.x & 31, lane = threadIdx.x >> 5;
     double s = 0.0;
     if (col < K)
@@ -89,23 +87,54 @@ __global__ __launch_bounds__(1024) void dice_ce_finalize_kernel(const float* __r
         double t = 0.0;
         for (int l = 0; l < 32; ++l) t += lanes[l][threadIdx.x];
         sums[threadIdx.x] = t;
-        if ((int)threadIdx.x < K) stats[threadIdx.x] = (float)t;
     }
+}
+
+// the loss from the fp64 sums [A | B | T | ce_sum] over `total` pixels
+__device__ __forceinline__ float dice_ce_loss(const double* sums, int NC, double total) {
+    double dice = 0.0;
+    for (int c = 0; c < NC; ++c)
+        dice += 1.0 - (2.0 * sums[c] + (double)DICE_EPS) / (sums[NC + c] + sums[2 * NC + c] + (double)DICE_EPS);
+    return (float)(0.5 * sums[3 * NC] / total + 0.5 * dice / NC);
+}
+
+// stats out: [A | B | T | ce_sum | loss]  (3*NC + 2 floats).
+__global__ __launch_bounds__(1024) void dice_ce_finalize_kernel(const float* __restrict__ part, int rows, int NC, long total,
+                                                                float* __restrict__ stats) {
+    __shared__ double sums[32];
+    const int K = 3 * NC + 1;
+    dice_ce_col_sums(part, rows, K, sums);
+    if ((int)threadIdx.x < K) stats[threadIdx.x] = (float)sums[threadIdx.x];
     __syncthreads();
-    if (threadIdx.x == 0) {
-        double dice = 0.0;
-        for (int c = 0; c < NC; ++c)
-            dice += 1.0 - (2.0 * sums[c] + (double)DICE_EPS) / (sums[NC + c] + sums[2 * NC + c] + (double)DICE_EPS);
-        stats[K] = (float)(0.5 * sums[3 * NC] / (double)total + 0.5 * dice / NC);
-    }
+    if (threadIdx.x == 0) stats[K] = dice_ce_loss(sums, NC, (double)total);
+}
+
+// the two halves of the kernel above, for a data-parallel group that adds the sums of its ranks in between: the fp64 sums
+// [A | B | T | ce_sum] (3*NC + 1 doubles) ...
+__global__ __launch_bounds__(1024) void dice_ce_sums_kernel(const float* __restrict__ part, int rows, int NC,
+                                                            double* __restrict__ out) {
+    __shared__ double sums[32];
+    const int K = 3 * NC + 1;
+    dice_ce_col_sums(part, rows, K, sums);
+    if ((int)threadIdx.x < K) out[threadIdx.x] = sums[threadIdx.x];
+}
+
+// ... and the stats from (global) sums and the (global) pixel count
+__global__ __launch_bounds__(64) void dice_ce_from_sums_kernel(const double* __restrict__ sums, int NC, double total,
+                                                               float* __restrict__ stats) {
+    const int K = 3 * NC + 1;
+    if ((int)threadIdx.x < K) stats[threadIdx.x] = (float)sums[threadIdx.x];
+    if (threadIdx.x == 0) stats[K] = dice_ce_loss(sums, NC, total);
 }
 
 template <int NC>
 __global__ __launch_bounds__(256) void dice_ce_bwd_kernel(const float* __restrict__ logits, const void* __restrict__ target,
                                                           int tdtype, const float* __restrict__ stats,
-                                                          const float* __restrict__ gout, long HW, long total,
-                                                          float* __restrict__ dlogits) {
-    const float g = gout ? gout[0] : 1.f;
+                                                          const float* __restrict__ gout, float scale, long HW, long total,
+                                                          double ce_count, float* __restrict__ dlogits) {
+    // scale = 1, ce_count = total: the loss of these pixels.  A data-parallel rank passes the group's statistics, its pixel count
+    // and scale = world size: its gradient of the GROUP's loss, times world so that the average over the ranks is that gradient
+    const float g = (gout ? gout[0] : 1.f) * scale;
     float k1[NC], k2[NC];                              // d loss_dice / d p_c = k1_c * [t==c] + k2_c * p_c
 #pragma unroll
     for (int c = 0; c < NC; ++c) {
@@ -113,7 +142,7 @@ __global__ __launch_bounds__(256) void dice_ce_bwd_kernel(const float* __restric
         k1[c] = -0.5f / NC * 2.f / D;
         k2[c] = 0.5f / NC * (2.f * stats[c] + DICE_EPS) * 2.f / (D * D);
     }
-    const float ce_w = 0.5f / (float)total;
+    const float ce_w = 0.5f / (float)ce_count;
     for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
         const long n = i / HW, hw = i - n * HW;
         const float* x = logits + n * NC * HW + hw;
@@ -150,6 +179,14 @@ extern "C" size_t umi_dice_ce_ws_bytes(int N, int C, long HW) {
     return (size_t)blocks_for((long)N * HW) * (3 * C + 1) * sizeof(float);
 }
 
+static void launch_dice_ce_stats(const float* logits, const void* target, int target_dtype, int C, long HW, long total, int rows,
+                                 void* ws, hipStream_t s) {
+#define GO(NC) hipLaunchKernelGGL(dice_ce_stats_kernel<NC>, dim3(rows), dim3(256), 0, s, logits, target, target_dtype, HW, total, (float*)ws)
+    switch (C) { case 1: GO(1); break; case 2: GO(2); break; case 3: GO(3); break; case 4: GO(4); break;
+                 case 5: GO(5); break; case 6: GO(6); break; case 7: GO(7); break; default: GO(8); }
+#undef GO
+}
+
 extern "C" int umi_dice_ce_fwd(const float* logits, const void* target, int target_dtype, int N, int C, long HW, float* stats,
                                void* ws, size_t ws_bytes, umi_stream_t st) {
     if (!logits || !target || !stats || !ws || N <= 0 || HW <= 0 || target_dtype < 0 || target_dtype > 3) return UMI_ERR_BADARG;
@@ -158,27 +195,56 @@ extern "C" int umi_dice_ce_fwd(const float* logits, const void* target, int targ
     const long total = (long)N * HW;
     const int rows = blocks_for(total);
     hipStream_t s = (hipStream_t)st;
-#define GO(NC) hipLaunchKernelGGL(dice_ce_stats_kernel<NC>, dim3(rows), dim3(256), 0, s, logits, target, target_dtype, HW, total, (float*)ws)
-    switch (C) { case 1: GO(1); break; case 2: GO(2); break; case 3: GO(3); break; case 4: GO(4); break;
-                 case 5: GO(5); break; case 6: GO(6); break; case 7: GO(7); break; default: GO(8); }
-#undef GO
+    launch_dice_ce_stats(logits, target, target_dtype, C, HW, total, rows, ws, s);
     UMI_LAUNCH_CHECK();
     hipLaunchKernelGGL(dice_ce_finalize_kernel, dim3(1), dim3(1024), 0, s, (const float*)ws, rows, C, total, stats);
     UMI_LAUNCH_CHECK();
     return UMI_OK;
 }
 
-extern "C" int umi_dice_ce_bwd(const float* logits, const void* target, int target_dtype, const float* stats, const float* gout,
-                               int N, int C, long HW, float* dlogits, umi_stream_t st) {
-    if (!logits || !target || !stats || !dlogits || N <= 0 || HW <= 0 || target_dtype < 0 || target_dtype > 3) return UMI_ERR_BADARG;
+extern "C" int umi_dice_ce_sums(const float* logits, const void* target, int target_dtype, int N, int C, long HW, double* sums,
+                                void* ws, size_t ws_bytes, umi_stream_t st) {
+    if (!logits || !target || !sums || !ws || N <= 0 || HW <= 0 || target_dtype < 0 || target_dtype > 3) return UMI_ERR_BADARG;
+    if (C < 1 || C > 8) return UMI_ERR_UNSUPPORTED;
+    if (ws_bytes < umi_dice_ce_ws_bytes(N, C, HW)) return UMI_ERR_WORKSPACE;
+    const long total = (long)N * HW;
+    const int rows = blocks_for(total);
+    hipStream_t s = (hipStream_t)st;
+    launch_dice_ce_stats(logits, target, target_dtype, C, HW, total, rows, ws, s);
+    UMI_LAUNCH_CHECK();
+    hipLaunchKernelGGL(dice_ce_sums_kernel, dim3(1), dim3(1024), 0, s, (const float*)ws, rows, C, sums);
+    UMI_LAUNCH_CHECK();
+    return UMI_OK;
+}
+
+extern "C" int umi_dice_ce_finalize(const double* sums, int C, double count, float* stats, umi_stream_t st) {
+    if (!sums || !stats || !(count > 0)) return UMI_ERR_BADARG;
+    if (C < 1 || C > 8) return UMI_ERR_UNSUPPORTED;
+    hipLaunchKernelGGL(dice_ce_from_sums_kernel, dim3(1), dim3(64), 0, (hipStream_t)st, sums, C, count, stats);
+    UMI_LAUNCH_CHECK();
+    return UMI_OK;
+}
+
+extern "C" int umi_dice_ce_bwd_global(const float* logits, const void* target, int target_dtype, const float* stats,
+                                      const float* gout, float scale, double count, int N, int C, long HW, float* dlogits,
+                                      umi_stream_t st) {
+    if (!logits || !target || !stats || !dlogits || N <= 0 || HW <= 0 || target_dtype < 0 || target_dtype > 3 || !(scale > 0.f) ||
+        !(count > 0))
+        return UMI_ERR_BADARG;
     if (C < 1 || C > 8) return UMI_ERR_UNSUPPORTED;
     const long total = (long)N * HW;
     const int grid = blocks_for(total);
     hipStream_t s = (hipStream_t)st;
-#define GO(NC) hipLaunchKernelGGL(dice_ce_bwd_kernel<NC>, dim3(grid), dim3(256), 0, s, logits, target, target_dtype, stats, gout, HW, total, dlogits)
+#define GO(NC) hipLaunchKernelGGL(dice_ce_bwd_kernel<NC>, dim3(grid), dim3(256), 0, s, logits, target, target_dtype, stats, gout, scale, HW, total, count, dlogits)
     switch (C) { case 1: GO(1); break; case 2: GO(2); break; case 3: GO(3); break; case 4: GO(4); break;
                  case 5: GO(5); break; case 6: GO(6); break; case 7: GO(7); break; default: GO(8); }
 #undef GO
     UMI_LAUNCH_CHECK();
     return UMI_OK;
+}
+
+extern "C" int umi_dice_ce_bwd(const float* logits, const void* target, int target_dtype, const float* stats, const float* gout,
+                               int N, int C, long HW, float* dlogits, umi_stream_t st) {
+    if (N <= 0 || HW <= 0) return UMI_ERR_BADARG;
+    return umi_dice_ce_bwd_global(logits, target, target_dtype, stats, gout, 1.f, (double)((long)N * HW), N, C, HW, dlogits, st);
 }

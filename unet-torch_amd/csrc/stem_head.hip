@@ -128,7 +128,7 @@ __global__ __launch_bounds__(256) void stem3x3_fwd_kernel(const half_t* __restri
 // xhat*c2), umi_bn_dz (common.h), rounded to fp16 exactly as bn_bwd_apply_v8 stores it -- is formed on the fly from (dA, y).  The stem's
 // input needs no gradient, so nothing else reads dz: the apply pass over the layer's 537 MB tensors (read dA, read y, write dz) and
 // this kernel's read of dz become one read of dA and y.
-struct StemBna { const half_t* y; int ldy; const float4* tx; const float* rstd; const float* sum_dz; const float* sum_dzx; long M; };
+struct StemBna { const half_t* y; int ldy; const float4* tx; const float* rstd; const float* sum_dz; const float* sum_dzx; long count; };
 
 // dW[co][ci][tap] partials: grid = (pixel blocks, Ci); thread = (pixel lane, 8 output channels)
 template <bool BNA>
@@ -152,7 +152,7 @@ __global__ __launch_bounds__(256) void stem3x3_wgrad_kernel(const half_t* __rest
     float4 tb[BNA ? 8 : 1];
     float rsb[BNA ? 8 : 1], c1[BNA ? 8 : 1], c2[BNA ? 8 : 1];
     if (BNA) {
-        const float invM = 1.f / (float)ba.M;            // on the device, as the standalone kernels compute it
+        const float invM = 1.f / (float)ba.count;           // on the device, as the standalone kernels compute it
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
             const int c = cg * 8 + j;
@@ -528,7 +528,7 @@ int umi_stem_wgrad(const WgradProblem& p, const void* x, const void* txa, const 
         hipLaunchKernelGGL(stem3x3_wgrad_kernel<false>, dim3(blocks, Ci), dim3(256), 0, s, (const half_t*)x, p.ldx, (const float4*)txa,
                            (const half_t*)dy, p.lddy, (float*)o.ws, N, H, W, Ci, Co, StemBna{});
     else {
-        const StemBna ba{(const half_t*)bna->y, bna->ldy, (const float4*)bna->tx_bn, bna->rstd, bna->sum_dz, bna->sum_dzx, (long)N * H * W};
+        const StemBna ba{(const half_t*)bna->y, bna->ldy, (const float4*)bna->tx_bn, bna->rstd, bna->sum_dz, bna->sum_dzx, bna->count};
         hipLaunchKernelGGL(stem3x3_wgrad_kernel<true>, dim3(blocks, Ci), dim3(256), 0, s, (const half_t*)x, p.ldx, (const float4*)txa,
                            (const half_t*)dy, p.lddy, (float*)o.ws, N, H, W, Ci, Co, ba);
     }

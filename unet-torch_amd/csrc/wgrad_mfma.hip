@@ -281,7 +281,7 @@ constexpr int WS_SMEM = 2 * SMEM;        // 84,992 B (dynamic LDS)
 // rounding to fp16) -- by the producer waves while they stage the tile; the workgroups of the first input-channel tile also
 // write it out (`dz`) for the data-gradient kernel.  Replaces a standalone pass that read y and dA and re-wrote dA in place.
 struct BnApply {
-    const half_t* y; int ldy; const float4* tx; const float* rstd; const float* sum_dz; const float* sum_dzx; long M;
+    const half_t* y; int ldy; const float4* tx; const float* rstd; const float* sum_dz; const float* sum_dzx; long count;
     half_t* dz; int lddz;
 };
 
@@ -360,7 +360,7 @@ __global__ __launch_bounds__(512, 1) void wgrad3x3_ws_kernel(
         const int ybo0 = BNA ? (bcol * ba.ldy + co0 + sub * 8) * 2 : 0;
         const bool dz_writer = BNA && ci0 == 0;
         if (BNA) {
-            const float invM = 1.f / (float)ba.M;          // on the device, as the standalone kernels compute it
+            const float invM = 1.f / (float)ba.count;         // on the device, as the standalone kernels compute it
 #pragma unroll
             for (int j = 0; j < 8; ++j) {
                 const int c = co0 + sub * 8 + j;
@@ -1206,7 +1206,7 @@ int umi_wgrad3x3_mfma(const WgradProblem& p, const void* x, const void* txa, con
         if (attr_rc) return attr_rc;
         dim3 block_ws(512);
         const BnApply ba = bna ? BnApply{(const half_t*)bna->y, bna->ldy, (const float4*)bna->tx_bn, bna->rstd, bna->sum_dz, bna->sum_dzx,
-                                         (long)N * H * W, (half_t*)bna->dz, bna->lddz}
+                                         bna->count, (half_t*)bna->dz, bna->lddz}
                                : BnApply{nullptr, 0, nullptr, nullptr, nullptr, nullptr, 1, nullptr, 0};
 #define GO_WS(HT, BN_)                                                                                              \
         hipLaunchKernelGGL((wgrad3x3_ws_kernel<HT, BN_>), grid, block_ws, dyn, s, (const half_t*)x, ldx, (const float4*)txa,   \

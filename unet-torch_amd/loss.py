@@ -33,6 +33,12 @@ and read 2 B integers (and the labelling's fault word) back once; CPU tensors ru
 component count is cv2.connectedComponents' / scipy.ndimage.label's with a full 3x3 structure; the same Python expression on the
 same integers gives the reference's float.
 
+Under `umi.ddp.GradReducer(model, world, global_batch=True)` 'dice_bce_mc' is the loss of the data-parallel group's WHOLE batch on
+every rank: the float64 sums of the fused kernels (`umi_dice_ce_sums`) or of a torch composite (CPU tensors) are all-reduced with
+the pixel count before the quotients are formed, and the backward is world x the gradient of that loss w.r.t. this rank's logits,
+so that the averaged parameter gradients are those of the global loss.  Shards must be equal; 'Tversky', 'TopK' and 'BCE_HEM',
+which couple the batch in ways this does not cover, raise NotImplementedError while the switch is on.
+
 The remaining names raise NotImplementedError: 'dice', 'dice_score', 'dice_score_mc' and 'log_cosh_dice_loss' call
 DiceLoss() without n_classes, 'FL' names an undefined BinaryFocalLoss, HausdorffERLoss has no gradient and
 ActiveContourLoss hard-codes 512x512 tensors on cuda:0 in the reference itself.
@@ -102,6 +108,70 @@ class _FusedDiceCE(torch.autograd.Function):
         L.call("umi_dice_ce_bwd", pred.data_ptr(), target.data_ptr(), _TARGET_DTYPES[target.dtype], stats.data_ptr(),
                g.data_ptr(), N, C, HW, dl.data_ptr(), ops._stream())
         return dl, None
+
+
+class _FusedDiceCEGlobal(torch.autograd.Function):
+    """'dice_bce_mc' of a data-parallel group's whole batch (umi.ddp.GradReducer(global_batch=True)): this rank's float64 sums,
+    one all-reduce of [sums | pixel count], the loss from the global sums; the backward is world x the gradient of that loss
+    w.r.t. this rank's logits, so that the averaged parameter gradients are those of the global loss."""
+
+    @staticmethod
+    def forward(ctx, pred, target, sync):
+        from umi import lib as L, ops
+        N, C = pred.shape[0], pred.shape[1]
+        HW = pred[0, 0].numel()
+        sums = torch.full((3 * C + 2,), float(N * HW), dtype=torch.float64, device=pred.device)     # [A | B | T | CE sum | count]
+        stats = torch.empty(3 * C + 2, dtype=torch.float32, device=pred.device)
+        ws = ops.workspace(L.fn("umi_dice_ce_ws_bytes")(N, C, HW), pred.device)
+        L.call("umi_dice_ce_sums", pred.data_ptr(), target.data_ptr(), _TARGET_DTYPES[target.dtype], N, C, HW,
+               sums.data_ptr(), ws.data_ptr(), ws.numel(), ops._stream())
+        ctx.count = sync.reduce_counted(sums, N * HW)
+        ctx.world = sync.world
+        L.call("umi_dice_ce_finalize", sums.data_ptr(), C, float(ctx.count), stats.data_ptr(), ops._stream())
+        ctx.save_for_backward(pred, target, stats)
+        return stats[3 * C + 1].clone()
+
+    @staticmethod
+    def backward(ctx, gout):
+        from umi import lib as L, ops
+        pred, target, stats = ctx.saved_tensors
+        N, C = pred.shape[0], pred.shape[1]
+        HW = pred[0, 0].numel()
+        g = gout.detach().to(torch.float32).contiguous()
+        dl = torch.empty_like(pred)
+        L.call("umi_dice_ce_bwd_global", pred.data_ptr(), target.data_ptr(), _TARGET_DTYPES[target.dtype], stats.data_ptr(),
+               g.data_ptr(), float(ctx.world), float(ctx.count), N, C, HW, dl.data_ptr(), ops._stream())
+        return dl, None, None
+
+
+def dice_bce_mc_global_composite(pred, target, sync):
+    """The same loss as torch ops (CPU tensors, any float dtype): the sums of `DiceLoss` and of the cross entropy are added over
+    the group before the quotients are formed.  Value: the global loss.  Gradient: world x d(global loss) / d(local logits)."""
+    C = CLASS_NUMBER
+    if pred.shape[1] != C or pred.shape[0] != target.shape[0] or pred.shape[2:] != target.shape[1:]:
+        raise AssertionError(f"predict {tuple(pred.shape)} & target {tuple(target.shape)} shape do not match")
+    t = target.long()
+    p = torch.softmax(pred, dim=1)
+    onehot = F.one_hot(t, C).movedim(-1, 1).to(pred.dtype)
+    dims = [0] + list(range(2, pred.dim()))
+    count = t.numel()
+    local = torch.cat([(p * onehot).sum(dims), (p * p).sum(dims), onehot.sum(dims),
+                       F.cross_entropy(pred, t, reduction="sum").reshape(1), pred.new_full((1,), float(count))])
+    total = sync.all_reduce(local.detach().clone())
+    count = sync.check_count(total[-1], count)
+    # value = the all-reduced sums; derivative = world x d/d(local sums): every rank's sums enter the global ones with weight 1
+    S = total + sync.world * (local - local.detach())
+    A, B, T, ce = S[:C], S[C:2 * C], S[2 * C:3 * C], S[3 * C]
+    dice = (1 - (2 * A + 1e-5) / (B + T + 1e-5)).sum() / C
+    return 0.5 * ce / count + 0.5 * dice
+
+
+def _batch_sync():
+    from umi import ddp
+    return ddp.active_batch_sync()
+
+
+_BATCH_COUPLED = {"Tversky", "TopK", "BCE_HEM"}
 
 
 def _fused_ok(pred, target):
@@ -484,6 +554,14 @@ def MRAccuracy(pred, target):
 
 
 def calc_loss(pred, target, bce_weight=0.5, loss_type='mse'):
+    sync = _batch_sync()              # umi.ddp.GradReducer(global_batch=True): losses are those of the group's whole batch
+    if sync is not None and loss_type in _BATCH_COUPLED:
+        raise NotImplementedError(f"loss_type {loss_type!r} couples the batch in a way global_batch does not cover; it would "
+                                  "silently stay per-replica")
+    if loss_type == 'dice_bce_mc' and sync is not None:
+        if _fused_ok(pred, target):
+            return _FusedDiceCEGlobal.apply(pred, target, sync)
+        return dice_bce_mc_global_composite(pred, target, sync)
     if loss_type == 'dice_bce_mc':
         if _fused_ok(pred, target):
             return _FusedDiceCE.apply(pred, target)

@@ -2,7 +2,26 @@
 
 The reference has no multi-GPU path; this is new functionality with standard
 DDP semantics: every rank holds a full replica, the global batch is split evenly, gradients are
-averaged, BatchNorm statistics and the Dice sums stay per-replica.
+averaged.  By default BatchNorm statistics and the Dice sums stay per-replica, as in torch DDP -- which makes N ranks
+x B/N images a different model from one process on the B images.  `GradReducer(..., global_batch=True)` closes that gap:
+
+  * training-mode BatchNorm layers (all go through Tape.conv_bn) normalise with the statistics of the WHOLE batch: each
+    rank reduces its partial rows to float64 sums, ONE all-reduce per layer carries [sums | sums of squares | pixel count],
+    and the finalize kernel runs from the global sums and the global count (running statistics included);
+  * their backward adds the two sums sum(dz), sum(dz * xhat) over the ranks (carried as float64) and applies them with the global
+    count.  The gradients of gamma and beta that go into the buckets stay the LOCAL sums: the bucket all-reduce with its
+    1 / world already turns them into the gradient of the global loss;
+  * `loss.calc_loss(..., 'dice_bce_mc')` becomes the loss of the whole batch (global Dice sums and pixel count), reported on
+    every rank, and its backward is world x the gradient of that loss w.r.t. this rank's logits, so the AVERAGED parameter
+    gradient is the gradient of the global loss.
+
+With the switch on, equal shards are required (a rank whose count is not 1 / world of the total raises), the batch-coupled
+losses 'Tversky', 'TopK' and 'BCE_HEM' raise NotImplementedError instead of silently staying per-replica, and a sync
+collective cannot be captured into a HIP graph: deferred / GraphedStep mode raises RuntimeError (a group of one launches no
+collective and is exempt).  Eval mode is untouched.  The switch is per process: the loss has no model argument, so it asks
+`active_batch_sync()`; `GradReducer.close()` turns it off again.  Cost: 2 small launches more per BatchNorm layer forward, a
+launch and a collective more per layer each way when world > 1; the latency of those collectives over xGMI is unmeasured
+on hardware.
 
 Overlap: the tape's hand-written backward (umi/graph.py) writes each parameter gradient straight
 into its slot of a flat fp32 bucket and tells the reducer; buckets are filled in reverse execution
@@ -26,8 +45,71 @@ class _Bucket:
         self.flat, self.views, self.pending, self.work, self.params = None, {}, 0, None, []
 
 
+_ACTIVE_SYNC = None
+
+
+def active_batch_sync():
+    """The BatchSync of the GradReducer(global_batch=True) of this process, or None."""
+    return _ACTIVE_SYNC
+
+
+def set_active_batch_sync(sync):
+    """Which BatchSync loss.calc_loss uses (None: per-replica losses).  GradReducer(global_batch=True) and close() call this; a
+    process that holds several reducers (an A/B measurement) switches by hand."""
+    global _ACTIVE_SYNC
+    _ACTIVE_SYNC = sync
+
+
+class BatchSync:
+    """The collectives of global-batch mode: the hook Tape.conv_bn reads from the model (`_umi_batch_sync`) and
+    loss.calc_loss from active_batch_sync().  A group of one launches nothing."""
+
+    def __init__(self, reducer):
+        self.reducer, self.world, self.group = reducer, reducer.world, reducer.group
+
+    def all_reduce(self, vec):
+        """In-place SUM of a small statistics vector over the group."""
+        if self.world == 1:
+            return vec
+        if self.reducer.deferred or (vec.is_cuda and torch.cuda.is_current_stream_capturing()):
+            raise RuntimeError("global_batch: a statistics all-reduce cannot run in deferred / GraphedStep mode (collectives are "
+                               "not captured into a HIP graph); use the eager step with global_batch=True")
+        dist.all_reduce(vec, op=dist.ReduceOp.SUM, group=self.group)
+        return vec
+
+    def check_count(self, total, local):
+        """Equal shards only: `total` (the all-reduced count) must be world x this rank's count.  Returns the global count."""
+        want = self.world * int(local)
+        if self.world > 1:
+            got = float(total)                                     # one host read
+            if got != float(want):
+                raise RuntimeError(f"global_batch needs equal shards: this rank holds {int(local)} of {got:.0f} rows, "
+                                   f"not 1/{self.world} of them")
+        return want
+
+    def reduce_counted(self, vec, local, tape=None):
+        """All-reduce [sums ... | count] in place; returns the global count.  The count is read back (a host sync) for the first
+        layer of a tape only: every layer of one forward sees the same split of the batch."""
+        self.all_reduce(vec)
+        if tape is not None and tape._shards_checked:
+            return self.world * int(local)
+        if tape is not None:
+            tape._shards_checked = True
+        return self.check_count(vec[-1] if self.world > 1 else None, local)
+
+    def reduce_bn_bwd(self, sum_dz, sum_dzx, local):
+        """The group's (sum dz, sum dz * xhat, count) for stage 3 of a BatchNorm backward.  The inputs are left alone (they are
+        the LOCAL gradients of beta and gamma); the sums travel as float64."""
+        if self.world == 1:
+            return sum_dz, sum_dzx, int(local)
+        C = sum_dz.numel()
+        g = torch.cat([sum_dz.reshape(-1), sum_dzx.reshape(-1)]).double()
+        g = self.all_reduce(g).float()
+        return g[:C], g[C:], self.world * int(local)
+
+
 class GradReducer:
-    def __init__(self, model, world_size=None, bucket_mb=32.0, group=None):
+    def __init__(self, model, world_size=None, bucket_mb=32.0, group=None, global_batch=False):
         self.group = group
         self.world = world_size if world_size is not None else dist.get_world_size(group)
         params = [p for p in model.parameters() if p.requires_grad]
@@ -52,8 +134,21 @@ class GradReducer:
         self.deferred = False
         self.reset()
         model._umi_grad_sink = self
+        self.model = model
+        self.batch_sync = None
+        if global_batch:
+            self.batch_sync = model._umi_batch_sync = BatchSync(self)
+            set_active_batch_sync(self.batch_sync)
         if self.world > 1:
             self.broadcast_parameters(model)
+
+    def close(self):
+        """Detach from the model (and turn global-batch mode off for this process)."""
+        for name, mine in (("_umi_grad_sink", self), ("_umi_batch_sync", self.batch_sync)):
+            if mine is not None and self.model.__dict__.get(name) is mine:
+                delattr(self.model, name)
+        if self.batch_sync is not None and _ACTIVE_SYNC is self.batch_sync:
+            set_active_batch_sync(None)
 
     def _seal(self, b, numel):
         p0 = b.params[0]

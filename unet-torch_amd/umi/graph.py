@@ -65,8 +65,11 @@ class Act:
 
 
 class Tape:
-    def __init__(self, dtype, training, record, loss_scale=1.0, grad_sink=None, pack_cache=None, seed=0, seed_dev=None):
+    def __init__(self, dtype, training, record, loss_scale=1.0, grad_sink=None, pack_cache=None, seed=0, seed_dev=None,
+                 batch_sync=None):
         self.dtype = dtype
+        self.batch_sync = batch_sync      # umi.ddp.BatchSync (the model's `_umi_batch_sync`) or None: training-mode BatchNorm
+                                          # layers then use the sums of the data-parallel group's whole batch, both directions
         self._seed = int(seed)            # dropout streams: host part of the seed (per model, from torch's generator) ...
         self._seed_dev = seed_dev         # ... plus an int32 device counter the kernel adds in, so a step replayed from a
         self._drop_count = 0              # captured HIP graph (host part frozen) still draws fresh masks
@@ -78,6 +81,8 @@ class Tape:
         # parameter gradients leave the kernels multiplied by `inv`: undoes the loss scale and, under
         # data parallelism, pre-divides by the world size so the all-reduce is a plain SUM
         self.inv = (grad_sink.grad_scale if grad_sink is not None else 1.0) / self.loss_scale
+        self._shards_checked = False      # batch_sync: the all-reduced count of the first BatchNorm layer was compared with
+                                          # world x the local count (umi.ddp.BatchSync.reduce_counted: one host read per tape)
         self.steps = []
         self.param_grads = {}             # id(param) -> (param, grad tensor)
         self._deferred_unscale = []       # BatchNorm parameter gradients still carrying the loss scale
@@ -262,9 +267,19 @@ class Tape:
             raise RuntimeError("conv_bn: no BatchNorm statistics were produced for this layer")
         if self.training:
             mom = bn.momentum if bn.momentum is not None else 0.1
-            tx, rstd = ops.bn_finalize(part, Co, N * Ho * Wo, bn.weight.detach(), bn.bias.detach(), bn.eps, mom,
-                                       bn.running_mean if bn.track_running_stats else None,
-                                       bn.running_var if bn.track_running_stats else None)
+            sync = self.batch_sync
+            count = N * Ho * Wo
+            if sync is None:
+                tx, rstd = ops.bn_finalize(part, Co, count, bn.weight.detach(), bn.bias.detach(), bn.eps, mom,
+                                           bn.running_mean if bn.track_running_stats else None,
+                                           bn.running_var if bn.track_running_stats else None)
+            else:
+                # the group's batch: rows -> float64 sums (+ this rank's count), ONE all-reduce, finalize from the global sums
+                sums = ops.bn_stat_sums(part, Co, count)
+                count = sync.reduce_counted(sums, count, self)
+                tx, rstd = ops.bn_finalize_sums(sums, Co, count, bn.weight.detach(), bn.bias.detach(), bn.eps, mom,
+                                                bn.running_mean if bn.track_running_stats else None,
+                                                bn.running_var if bn.track_running_stats else None)
             if bn.track_running_stats and bn.num_batches_tracked is not None:
                 self._nbt.append(bn.num_batches_tracked)          # += 1 for all layers in one launch (finish_forward)
             if bias is not None and bn.track_running_stats:
@@ -294,8 +309,11 @@ class Tape:
                 # narrow-input kernel forms it on the fly (no apply pass, dz never stored)
                 stem_fuse = (not fuse and self.dtype == torch.float16 and (R, S, stride, pad) == (3, 3, 1, 1) and Ci <= 4
                              and Co % 8 == 0 and not _wants_grad(a) and os.environ.get("UMI_NO_STEM_BNAPPLY") != "1")
-                dbeta, dgamma = ops.bn_bwd(o.grad, out, tx, rstd, partials=partials, apply=not (fuse or stem_fuse))
+                dbeta, dgamma = ops.bn_bwd(o.grad, out, tx, rstd, partials=partials,
+                                           apply=not (fuse or stem_fuse or self.batch_sync is not None))
                 o.bn_part = None
+                # (these two stay this rank's own sums under a batch sync: the bucket all-reduce with its 1 / world turns them
+                #  into the gradient of the group's loss; handing it the group's sums would count every rank world times)
                 if self.grad_sink is None and inv != 1.0:
                     # un-scale all BatchNorm parameter gradients with one batched multiply at the end of the backward
                     # pass (36 tiny launches otherwise); with a gradient sink they must be final before they are handed over
@@ -306,19 +324,26 @@ class Tape:
                     self._set_pgrad_scaled(bn.weight, dgamma, inv)
                     self._set_pgrad_scaled(bn.bias, dbeta, inv)
                 gw = self._new_pgrad(weight)
+                cnt = None
+                if self.batch_sync is not None:
+                    # stage 3 with the group's sums over the group's rows (separate tensors: the parameter gradients above may
+                    # still be read, or rescaled, in place)
+                    dbeta, dgamma, cnt = self.batch_sync.reduce_bn_bwd(dbeta, dgamma, N * Ho * Wo)
+                if not (fuse or stem_fuse) and cnt is not None:
+                    ops.bn_bwd_apply(o.grad, out, tx, rstd, dbeta, dgamma, count=cnt)
                 if fuse:
                     dz = self.alloc(N, Ho, Wo, Co, device=out.device)
                     if ops.conv_wgrad_bnapply(a.raw, a.tx, o.grad, out, tx, rstd, dbeta, dgamma, dz, gw, Ci * R * S, R * S, 1,
-                                              inv, R, S, stride, pad):
+                                              inv, R, S, stride, pad, count=cnt):
                         o.grad = dz
                     else:
                         fuse = False
-                        ops.bn_bwd_apply(o.grad, out, tx, rstd, dbeta, dgamma)
+                        ops.bn_bwd_apply(o.grad, out, tx, rstd, dbeta, dgamma, count=cnt)
                 if stem_fuse:
                     if not ops.conv_wgrad_bnapply(a.raw, a.tx, o.grad, out, tx, rstd, dbeta, dgamma, None, gw, Ci * R * S, R * S, 1,
-                                                  inv, R, S, stride, pad):
+                                                  inv, R, S, stride, pad, count=cnt):
                         stem_fuse = False
-                        ops.bn_bwd_apply(o.grad, out, tx, rstd, dbeta, dgamma)
+                        ops.bn_bwd_apply(o.grad, out, tx, rstd, dbeta, dgamma, count=cnt)
                 if not fuse and not stem_fuse:
                     ops.conv_wgrad(a.raw, a.tx, o.grad, None, gw, Ci * R * S, R * S, 1, inv, R, S, stride, pad,
                                    flags=self._fk(R, S, stride, pad, Ci, Co), defer=self.deferred.open("wgrad_reduce", fills=(gw,)))

@@ -463,6 +463,25 @@ def bn_finalize(part, C, count, gamma, beta, eps, momentum, running_mean, runnin
     return tx, rstd
 
 
+def bn_stat_sums(part, C, count):
+    """The statistics rows as the float64 vector a data-parallel group all-reduces: [sums[C] | sums of squares[C] | count]
+    (umi_bn_stat_sums adds the rows in bn_finalize's order; the last element is this rank's pixel count)."""
+    rows = part.numel() // (2 * C)
+    v = torch.full((2 * C + 1,), float(count), dtype=torch.float64, device=part.device)
+    L.call("umi_bn_stat_sums", part.data_ptr(), rows, C, v.data_ptr(), _stream())
+    return v
+
+
+def bn_finalize_sums(sums, C, count, gamma, beta, eps, momentum, running_mean, running_var):
+    """bn_finalize from float64 sums [2][C] (a longer vector's head) over `count` pixels."""
+    assert sums.dtype == torch.float64 and sums.is_contiguous() and sums.numel() >= 2 * C
+    tx = torch.empty(C, 4, dtype=torch.float32, device=sums.device)
+    rstd = torch.empty(C, dtype=torch.float32, device=sums.device)
+    L.call("umi_bn_finalize_sums", sums.data_ptr(), C, float(count), _ptr(gamma), _ptr(beta), eps, momentum,
+           _ptr(running_mean), _ptr(running_var), tx.data_ptr(), rstd.data_ptr(), _stream())
+    return tx, rstd
+
+
 def pool2_fwd(x, tx, y):
     N, H, W, C, ldx = _nhwc(x)
     _, Ho, Wo, _, ldy = _nhwc(y)
@@ -615,15 +634,21 @@ def bn_bwd(da, y, tx, rstd, partials=None, apply=True):
     return sums[0], sums[1]
 
 
-def bn_bwd_apply(da, y, tx, rstd, sum_dz, sum_dzx):
+def bn_bwd_apply(da, y, tx, rstd, sum_dz, sum_dzx, count=None):
+    """count: the rows the two sums cover when they are not this tensor's own N * H * W (a data-parallel group's whole batch)."""
     N, H, W, C, ldy = _nhwc(y)
+    if count is not None:
+        L.call("umi_bn_bwd_apply_count", da.data_ptr(), _nhwc(da)[4], y.data_ptr(), ldy, tx.data_ptr(), rstd.data_ptr(),
+               sum_dz.data_ptr(), sum_dzx.data_ptr(), N * H * W, int(count), C, _dt(y), _stream())
+        return
     L.call("umi_bn_bwd_apply", da.data_ptr(), _nhwc(da)[4], y.data_ptr(), ldy, tx.data_ptr(), rstd.data_ptr(),
            sum_dz.data_ptr(), sum_dzx.data_ptr(), N * H * W, C, _dt(y), _stream())
 
 
-def conv_wgrad_bnapply(x, txa, da, y, tx_bn, rstd, sum_dz, sum_dzx, dz, dW, s_co, s_ci, s_t, out_scale, R, S, stride, pad):
+def conv_wgrad_bnapply(x, txa, da, y, tx_bn, rstd, sum_dz, sum_dzx, dz, dW, s_co, s_ci, s_t, out_scale, R, S, stride, pad,
+                       count=None):
     """Weight gradient fused with stage 3 of the following BatchNorm's backward (umi_conv_wgrad_bnapply); False where the
-    fused kernel does not apply (nothing was launched)."""
+    fused kernel does not apply (nothing was launched).  count: as in bn_bwd_apply."""
     N, H, W, Ci, ldx = _nhwc(x)
     _, Ho, Wo, Co, ldda = _nhwc(da)
     if (Ho, Wo) != (H, W) or da.dtype != torch.float16:
@@ -633,6 +658,11 @@ def conv_wgrad_bnapply(x, txa, da, y, tx_bn, rstd, sum_dz, sum_dzx, dz, dW, s_co
     ws = workspace(nb, x.device)
     # dz None: the layer's input takes no gradient, nothing else reads dz (the network's first conv: formed on the fly, never stored)
     # UMI_ERR_UNSUPPORTED: not an error, the caller runs the two passes
+    if count is not None:
+        return L.supported("umi_conv_wgrad_bnapply_count", x.data_ptr(), ldx, _ptr(txa), da.data_ptr(), ldda, y.data_ptr(),
+                           _nhwc(y)[4], tx_bn.data_ptr(), rstd.data_ptr(), sum_dz.data_ptr(), sum_dzx.data_ptr(),
+                           _ptr(dz), _nhwc(dz)[4] if dz is not None else 0, dW.data_ptr(), s_co, s_ci, s_t, out_scale,
+                           N, H, W, Ci, Co, R, S, stride, pad, _dt(x), 0, int(count), ws.data_ptr(), ws.numel(), _stream())
     return L.supported("umi_conv_wgrad_bnapply", x.data_ptr(), ldx, _ptr(txa), da.data_ptr(), ldda, y.data_ptr(), _nhwc(y)[4],
                        tx_bn.data_ptr(), rstd.data_ptr(), sum_dz.data_ptr(), sum_dzx.data_ptr(),
                        _ptr(dz), _nhwc(dz)[4] if dz is not None else 0, dW.data_ptr(), s_co, s_ci, s_t, out_scale,
