@@ -9,9 +9,8 @@
 //   backward dQ  : the same decomposition; also writes delta = rowsum(dO * O).
 //   backward dKV : workgroup = 128 keys (4 waves x 32) of one (batch, head); Q / dO streamed in 32-query tiles.
 //
-// Operand maps of the 32x32x2 form (lane l): A[i = l & 31][k = l >> 5], B[k = l >> 5][j = l & 31], one VGPR each;
-// D[row = (reg & 3) + 8 * (reg >> 2) + 4 * (l >> 5)][col = l & 31], 16 VGPRs.
-//   scores   S^T[key][query] = K . Q^T: a lane owns ONE query column, so the row statistics are register reductions plus one
+// With the operand maps A[i][k], B[k][j], D[row][col] of the 32x32x2 form (mfma_f32.h):
+//   scores  S^T[key][query] = K . Q^T: a lane owns ONE query column, so the row statistics are register reductions plus one
 //            exchange with lane ^ 32.  B = the lane's own (pre-scaled) Q row in 32 VGPRs; the contraction runs over the head
 //            dimension in the order d = 32 * (l >> 5) + t for step t, so that a lane loads 32 consecutive floats.  A =
 //            K[key = l & 31][d] from a row-major LDS tile of 65 dwords per row: the 32 lanes of a half stride by one row and
@@ -27,10 +26,9 @@
 // Independent accumulators in flight per wave: forward 2 (the score chain is split in two halves of the head dimension, the two
 // 32-channel halves of O), backward 2 (S and dP) and 2 / 4 (dQ halves; dK and dV halves).
 #include "kernels.h"
+#include "mfma_f32.h"
 
 namespace {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 constexpr int D = 64;
 constexpr int PITCH = D + 1;       // dwords per LDS row
@@ -38,17 +36,7 @@ constexpr int KC = 64;             // keys per staged chunk (query-side kernels)
 constexpr int QT = 32;             // queries per staged tile (key-side kernel)
 constexpr int TILE = 128;          // queries / keys per workgroup
 
-__device__ __forceinline__ f32x16 mfma32(float a, float b, f32x16 c) {
-    return __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, c, 0, 0, 0);
-}
-__device__ __forceinline__ int d_row(int reg, int kh) { return (reg & 3) + 8 * (reg >> 2) + 4 * kh; }
 __device__ __forceinline__ float lane_xchg32(float v) { return __shfl_xor(v, 32); }
-__device__ __forceinline__ f32x16 zero16() {
-    f32x16 z;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) z[r] = 0.f;
-    return z;
-}
 
 // ROWS rows of one head slice of a token tensor -> a [ROWS][PITCH] LDS tile; rows at or past row_limit enter as zeros
 template <int ROWS>

@@ -102,9 +102,9 @@ __device__ __forceinline__ umi_half8 umi_tx8(umi_half8 v, const float4* t) {
     return __builtin_elementwise_max(__builtin_bit_cast(umi_half8, out), lo);
 }
 
-// The dropout stream of include/unetmi.h (umi_dropout) for kernels that REGENERATE their mask instead of storing it: the three
-// attention families (transformer_kernels.hip, attention_mfma.hip, attention_mfma_f32.hip).  One definition; the kernels that
-// store mask bytes (dropout_kernel, dropout8*_kernel, the conv1x1 epilogue) keep their own, older copies of the same rule.
+// The dropout stream of include/unetmi.h (umi_dropout).  One definition of the hash, for the kernels that store mask bytes
+// (dropout_kernel, dropout8*_kernel, the conv1x1 epilogue) and for those that REGENERATE their mask instead of storing it: the
+// three attention families (transformer_kernels.hip, attention_mfma.hip, attention_mfma_f32.hip).
 //   keep(e) = u >= p,  u = (hash32(e_lo, seed' ^ e_hi) >> 8) * 2^-24,  seed' = seed + seed_dev[0] * 0x9E3779B9
 // u is a multiple of 2^-24 and p * 2^24 is exact in fp32, so u >= p is the integer comparison (x >> 8) >= ceil(p * 2^24).
 struct UmiAttnDrop {
@@ -129,6 +129,13 @@ __device__ __forceinline__ unsigned umi_stream_seed(const UmiAttnDrop& d) {
 // e: index of the probability in the dense [B * heads * N, N] tensor, ((b * heads + h) * N + i) * N + j, in 64 bits
 __device__ __forceinline__ bool umi_stream_keep(unsigned long e, unsigned seed, unsigned thr) {
     return (umi_stream_hash32((unsigned)e, seed ^ (unsigned)(e >> 32)) >> 8) >= thr;
+}
+
+// Exact GELU (F.gelu's default) and its derivative: one definition, because umi_linear_fused's epilogue is promised bit-identical
+// to the linear followed by the elementwise kernels.
+__device__ __forceinline__ float umi_gelu(float u) { return 0.5f * u * (1.f + erff(u * 0.70710678118654752f)); }
+__device__ __forceinline__ float umi_gelu_d(float u) {
+    return 0.5f * (1.f + erff(u * 0.70710678118654752f)) + u * 0.3989422804014327f * __expf(-0.5f * u * u);
 }
 
 template <typename T> __device__ __forceinline__ float umi_ld(const T* p) { return (float)(*p); }

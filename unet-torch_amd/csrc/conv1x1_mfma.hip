@@ -58,13 +58,6 @@ struct Geo {                  // geometry of the (optionally strided) source / d
     const float4* bn_tx; const float* bn_rstd; float* bn_part;
 };
 
-__device__ __forceinline__ float c1_gelu(float u) { return 0.5f * u * (1.f + erff(u * 0.70710678118654752f)); }
-__device__ __forceinline__ unsigned c1_hash32(unsigned a, unsigned b) {            // == elementwise_tu_f16.hip hash32
-    unsigned x = a * 0x9E3779B1u ^ (b + 0x7F4A7C15u);
-    x ^= x >> 16; x *= 0x85EBCA6Bu; x ^= x >> 13; x *= 0xC2B2AE35u; x ^= x >> 16;
-    return x;
-}
-
 // Workgroups per CU: the 128 x 64 tiles keep 32 accumulators and fit 128 VGPRs, so FOUR of their workgroups share a CU (4 x 33 KB
 // of LDS): the counters of the 4,704-token linears (tools/experiments/pmc_gemm.py) show waves parked at s_waitcnt / barriers
 // for half of their cycles with two resident workgroups, MFMA pipes 21 % and LDS 33 % busy -- a synchronisation-bound loop
@@ -407,11 +400,11 @@ __global__ __launch_bounds__(256, (P == 128 && BN == 64) ? UMI_C1_OCC128 : 2) vo
 #pragma unroll
                 for (int jj = 0; jj < 8; ++jj) {
                     const long e = e0 + jj;
-                    const float u = (c1_hash32((unsigned)e, seed ^ (unsigned)(e >> 32)) >> 8) * (1.f / 16777216.f);
+                    const float u = (umi_stream_hash32((unsigned)e, seed ^ (unsigned)(e >> 32)) >> 8) * (1.f / 16777216.f);
                     const unsigned k = u >= geo.drop_p;
                     mk |= (unsigned long long)k << (8 * jj);
                     float f = (float)xv[jj];
-                    if (geo.epi == 1) f = c1_gelu(f);
+                    if (geo.epi == 1) f = umi_gelu(f);
                     f = k ? f * scale : 0.f;
                     if (geo.epi == 2) f += (float)av[jj];
                     o[jj] = (half_t)f;

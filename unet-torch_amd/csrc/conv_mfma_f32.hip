@@ -11,19 +11,10 @@
 //   weight gradient: k runs over pixels; a split owns a contiguous range of (image, row, 32-column segment) items in that order,
 //     inside an item columns ascend.  One accumulator per (tap, ci, co) and split; the splits' slabs [split][tap][ci][co] are
 //     then summed by umi_launch_wgrad_reduce in its fixed order (lane l of 8 sums splits l, l + 8, ..., lanes added in order).
-//
-// Operand maps of the 32x32x2 form (lane l): A[i = l & 31][k = l >> 5], B[k = l >> 5][j = l & 31], one VGPR each;
-// D[row = (reg & 3) + 8 * (reg >> 2) + 4 * (l >> 5)][col = l & 31], 16 VGPRs.
 #include "kernels.h"
+#include "mfma_f32.h"
 
 namespace {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
-__device__ __forceinline__ f32x16 mfma32(float a, float b, f32x16 c) {
-    return __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, c, 0, 0, 0);
-}
-__device__ __forceinline__ int d_row(int reg, int kh) { return (reg & 3) + 8 * (reg >> 2) + 4 * kh; }
 
 // ---- forward ------------------------------------------------------------------------------------------------------------------
 // D[co][pixel] += W[co][k] * X[k][pixel].  A workgroup (4 waves) owns 8 rows x 32 columns of one image and 64 output channels; a

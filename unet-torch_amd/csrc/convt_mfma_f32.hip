@@ -16,28 +16,16 @@
 //     (tap, ci, co) and split, pixels ascending inside the split (pixels past its end enter as zeros); the splits' slabs
 //     [split][4][Ci][Co] are then summed by umi_launch_wgrad_reduce in its fixed order.
 // Tail rows, K chunks and channel tiles are masked by loads that do not happen.
-//
-// Operand maps of the 32x32x2 form (lane l): A[i = l & 31][k = l >> 5], B[k = l >> 5][j = l & 31], one VGPR each;
-// D[row = (reg & 3) + 8 * (reg >> 2) + 4 * (l >> 5)][col = l & 31], 16 VGPRs.
 #include "kernels.h"
+#include "mfma_f32.h"
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
-__device__ __forceinline__ f32x16 mfma32(float a, float b, f32x16 c) {
-    return __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, c, 0, 0, 0);
-}
-__device__ __forceinline__ int d_row(int reg, int kh) { return (reg & 3) + 8 * (reg >> 2) + 4 * kh; }
-
 // ---- forward and data gradient ------------------------------------------------------------------------------------------------
-// The 128-row tile of gemm_mfma_f32.hip: a workgroup (4 waves, WM x WN) owns 128 rows and TN = 128 or 64 output channels, the x
-// tile is staged [row][k] with 33 dwords per row (the A operand's 32 lanes stride by one row: 32 distinct banks), the weights
-// [k][co] as packed, and the next chunk's global loads are in flight while the current one is multiplied.
-//   UP  (forward):       a row is an INPUT pixel, a column tile lies inside one tap, the epilogue scatters.
+// The 128-row forward tile of mfma_f32.h, staged as gemm_mfma_f32.hip stages it.
+//   UP  (forward):      a row is an INPUT pixel, a column tile lies inside one tap, the epilogue scatters.
 //   !UP (data gradient): a row is an OUTPUT pixel, the A operand is gathered from the pixels of the four taps in turn.
 // Workgroups that share a row tile are neighbours in the grid (the column tile is the fast index), so x is read from memory once.
-constexpr int P_TM = 128, P_KC = 32, P_XS = P_KC + 1;
 
 struct CtGeo { int H, W, out_H, out_W, off_h, off_w; };      // H x W: the grid the rows run over (UP: input, !UP: output pixels)
 
@@ -145,18 +133,7 @@ __global__ __launch_bounds__(256) void convt_f32_mfma_kernel(const float* __rest
         ci0 += P_KC;
         if (ci0 >= K) { ci0 = 0; ++t; }                   // the next chunk: the same tap's next channels, or the next tap's first
         if (t < t_end) load_chunk(t, ci0);
-#pragma unroll
-        for (int kk = 0; kk < P_KC / 2; ++kk) {
-            float av[MT], bv[NT];
-#pragma unroll
-            for (int a = 0; a < MT; ++a) av[a] = pa[a * 32 * P_XS + 2 * kk];
-#pragma unroll
-            for (int b = 0; b < NT; ++b) bv[b] = pb[2 * kk * TN + b * 32];
-#pragma unroll
-            for (int a = 0; a < MT; ++a)
-#pragma unroll
-                for (int b = 0; b < NT; ++b) acc[a][b] = mfma32(av[a], bv[b], acc[a][b]);
-        }
+        fwd_tile_multiply<TN>(acc, pa, pb);
         __syncthreads();
     }
 
@@ -178,11 +155,8 @@ __global__ __launch_bounds__(256) void convt_f32_mfma_kernel(const float* __rest
 
 // ---- weight gradient ----------------------------------------------------------------------------------------------------------
 // dW[t][ci][co] = sum over output pixels p = (n, ho, wo) of txa(x)[n][2 ho + r][2 wo + s][ci] * txb(dy)[p][co], t = 2 r + s: the
-// row-split GEMM of gemm_mfma_f32.hip once per tap, with the x rows gathered.  A workgroup (2 x 2 waves) owns one tap and TI x TJ =
-// 64 or 128 input and output channels over the pixels of one split (blockIdx.y), in chunks of 32 pixels; both operands are read
-// straight from [pixel][channel] LDS tiles.
-constexpr int Q_KC = 32;
-
+// channel-lane weight-gradient tile of mfma_f32.h once per tap, with the x rows gathered.  A workgroup owns one tap and the pixels
+// of one split (blockIdx.y).
 template <int MT, int NT>
 __global__ __launch_bounds__(256) void convt_wgrad_f32_mfma_kernel(const float* __restrict__ x, int ldx, const float4* __restrict__ txa,
                                                                    const float* __restrict__ dy, int lddy,
@@ -257,18 +231,7 @@ __global__ __launch_bounds__(256) void convt_wgrad_f32_mfma_kernel(const float* 
         store_chunk();
         __syncthreads();
         if (r1 - r > Q_KC) load_chunk(r + Q_KC);
-#pragma unroll
-        for (int kk = 0; kk < Q_KC / 2; ++kk) {
-            float av[MT], bv[NT];
-#pragma unroll
-            for (int a = 0; a < MT; ++a) av[a] = pa[2 * kk * TI + a * 32];
-#pragma unroll
-            for (int b = 0; b < NT; ++b) bv[b] = pb[2 * kk * TJ + b * 32];
-#pragma unroll
-            for (int a = 0; a < MT; ++a)
-#pragma unroll
-                for (int b = 0; b < NT; ++b) acc[a][b] = mfma32(av[a], bv[b], acc[a][b]);
-        }
+        wgrad_tile_multiply(acc, pa, pb);
         __syncthreads();
     }
     // slab [split][tap][ci][co]: lanes along co
@@ -284,24 +247,6 @@ __global__ __launch_bounds__(256) void convt_wgrad_f32_mfma_kernel(const float* 
                 if (ci < Ci) ws[(((long)blockIdx.y * 4 + tap) * Ci + ci) * Co + co] = acc[a][b][q];
             }
     }
-}
-
-// 64-wide tiles where the channel count fits one, or where 128-wide ones would leave most compute units without a workgroup
-bool fwd_narrow(long M, int Nn, int taps) { return Nn <= 64 || (long)umi_cdiv(M, P_TM) * umi_cdiv(Nn, 128) * taps < 512; }
-
-// the split of the pixels: a function of the shape alone (umi_conv_wgrad_ws_bytes must give the same answer)
-void wgrad_plan(long M, int Ci, int Co, int* ti, int* tj, int* splits, long* rps) {
-    *ti = Ci <= 64 ? 64 : 128;
-    *tj = Co <= 64 ? 64 : 128;
-    const long tiles = 4L * umi_cdiv(Ci, *ti) * umi_cdiv(Co, *tj);
-    long want = (512 + tiles - 1) / tiles;               // aim for >= 512 workgroups ...
-    const long chunks = (M + Q_KC - 1) / Q_KC;
-    const long most = (chunks + 3) / 4;                  // ... of at least 4 chunks of 32 pixels each
-    if (want > most) want = most;
-    if (want < 1) want = 1;
-    const long cps = (chunks + want - 1) / want;
-    *rps = cps * Q_KC;
-    *splits = (int)((chunks + cps - 1) / cps);
 }
 
 bool flags_ok(int flags) {
@@ -367,7 +312,7 @@ size_t umi_wgrad_convt_f32_mfma_ws_bound(const WgradProblem& facts) {
     if (!umi_wgrad_convt_f32_mfma_ok(p)) return 0;
     int ti, tj, splits;
     long rps;
-    wgrad_plan((long)p.N * p.Ho * p.Wo, p.Ci, p.Co, &ti, &tj, &splits, &rps);
+    wgrad_plan((long)p.N * p.Ho * p.Wo, p.Ci, p.Co, 4, &ti, &tj, &splits, &rps);
     return (size_t)splits * 4 * p.Ci * p.Co * sizeof(float);
 }
 
@@ -376,7 +321,7 @@ int umi_wgrad_convt_f32_mfma(const WgradProblem& p, const void* x, const void* t
     const long M = (long)p.N * p.Ho * p.Wo;
     int ti, tj, splits;
     long rps;
-    wgrad_plan(M, p.Ci, p.Co, &ti, &tj, &splits, &rps);
+    wgrad_plan(M, p.Ci, p.Co, 4, &ti, &tj, &splits, &rps);
     if (o.ws_bytes < (size_t)splits * 4 * p.Ci * p.Co * sizeof(float)) return UMI_ERR_WORKSPACE;
     if (((uintptr_t)x | (uintptr_t)dy | (uintptr_t)txa | (uintptr_t)txb) & 15) return UMI_ERR_BADARG;
     const int tiles_co = umi_cdiv(p.Co, tj), tiles = umi_cdiv(p.Ci, ti) * tiles_co;

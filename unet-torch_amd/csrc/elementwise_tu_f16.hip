@@ -16,15 +16,6 @@ inline int grid8(long vecs) {
     return (int)(g < 1 ? 1 : (g > 16384 ? 16384 : g));
 }
 
-__device__ __forceinline__ float gelu_f(float u) { return 0.5f * u * (1.f + erff(u * 0.70710678118654752f)); }
-__device__ __forceinline__ float gelu_df(float u) {
-    return 0.5f * (1.f + erff(u * 0.70710678118654752f)) + u * 0.3989422804014327f * __expf(-0.5f * u * u);
-}
-__device__ __forceinline__ unsigned hash32(unsigned a, unsigned b) {
-    unsigned x = a * 0x9E3779B1u ^ (b + 0x7F4A7C15u);
-    x ^= x >> 16; x *= 0x85EBCA6Bu; x ^= x >> 13; x *= 0xC2B2AE35u; x ^= x >> 16;
-    return x;
-}
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
@@ -45,8 +36,8 @@ __global__ __launch_bounds__(256) void ew8_kernel(const half_t* __restrict__ x, 
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
             float f = (float)xv[j], v;
-            if (MODE == 0) v = gelu_f(f);
-            else if (MODE == 1) v = (float)gv[j] * gelu_df(f);
+            if (MODE == 0) v = umi_gelu(f);
+            else if (MODE == 1) v = (float)gv[j] * umi_gelu_d(f);
             else v = f + (float)gv[j];
             o[j] = (half_t)v;
         }
@@ -76,7 +67,7 @@ __global__ __launch_bounds__(256) void dropout8_kernel(const half_t* __restrict_
             if (bwd) k = (unsigned)(mk >> (8 * j)) & 0xFFu;
             else {
                 const long e = e0 + j;
-                float u = (hash32((unsigned)e, seed ^ (unsigned)(e >> 32)) >> 8) * (1.f / 16777216.f);
+                float u = (umi_stream_hash32((unsigned)e, seed ^ (unsigned)(e >> 32)) >> 8) * (1.f / 16777216.f);
                 k = u >= p;
                 mk |= (unsigned long long)k << (8 * j);
             }
@@ -117,18 +108,18 @@ __global__ __launch_bounds__(256) void dropout8_fused_kernel(const half_t* __res
             if (bwd) k = (unsigned)(mk >> (8 * j)) & 0xFFu;
             else {
                 const long e = e0 + j;
-                float u = (hash32((unsigned)e, seed ^ (unsigned)(e >> 32)) >> 8) * (1.f / 16777216.f);
+                float u = (umi_stream_hash32((unsigned)e, seed ^ (unsigned)(e >> 32)) >> 8) * (1.f / 16777216.f);
                 k = u >= p;
                 mk |= (unsigned long long)k << (8 * j);
             }
             float v = (float)xv[j];
             if (!bwd) {
-                if (GELU) v = gelu_f(v);
+                if (GELU) v = umi_gelu(v);
                 v = k ? v * scale : 0.f;
                 if (AUX) v += (float)av[j];
             } else {
                 v = k ? v * scale : 0.f;
-                if (GELU) v *= gelu_df((float)av[j]);
+                if (GELU) v *= umi_gelu_d((float)av[j]);
             }
             o[j] = (half_t)v;
         }

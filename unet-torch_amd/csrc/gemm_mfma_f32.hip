@@ -11,28 +11,14 @@
 //     fixed order.
 //   statistics: one row of part[rows][2][Co] per 128 consecutive output rows; per channel the stored values are summed in a lane
 //     over its rows in ascending register order, the two half waves are added, then the waves in wave order.
-//
-// Operand maps of the 32x32x2 form (lane l): A[i = l & 31][k = l >> 5], B[k = l >> 5][j = l & 31], one VGPR each;
-// D[row = (reg & 3) + 8 * (reg >> 2) + 4 * (l >> 5)][col = l & 31], 16 VGPRs.
 #include "kernels.h"
+#include "mfma_f32.h"
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
-__device__ __forceinline__ f32x16 mfma32(float a, float b, f32x16 c) {
-    return __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, c, 0, 0, 0);
-}
-__device__ __forceinline__ int d_row(int reg, int kh) { return (reg & 3) + 8 * (reg >> 2) + 4 * kh; }
-
 // ---- forward ------------------------------------------------------------------------------------------------------------------
-// D[m][co] += X[m][k] * W[k][co]: the A operand's lanes run along the rows of x, the B operand's and D's along co, so a store
-// instruction writes 128 contiguous bytes of two output rows.  A workgroup (4 waves, WM x WN) owns 128 rows and TN = 128 or 64
-// output channels; a wave owns MT x NT tiles of 32 x 32 = 4 (TN = 128) or 2 (TN = 64) independent accumulators.  Per chunk of 32
-// input channels the x tile ([row][k], 33 dwords per row: the A operand's 32 lanes stride by one row and so fall on 32 distinct
-// banks) and the weights ([k][co] as packed) are staged in LDS; the next chunk's global loads are in flight while the current
-// one is multiplied.
-constexpr int P_TM = 128, P_KC = 32, P_XS = P_KC + 1;
+// The 128-row forward tile of mfma_f32.h with the identity row map: D's lanes run along co, so a store instruction writes 128
+// contiguous bytes of two output rows.  The next chunk's global loads are in flight while the current one is multiplied.
 
 template <int WM, int WN, int MT, int NT, bool HAS_TX>
 __global__ __launch_bounds__(256) void gemm_f32_mfma_kernel(const float* __restrict__ x, int ldx, const float4* __restrict__ tx,
@@ -111,18 +97,7 @@ __global__ __launch_bounds__(256) void gemm_f32_mfma_kernel(const float* __restr
         store_chunk();
         __syncthreads();
         if (ci0 + P_KC < Ci) load_chunk(ci0 + P_KC);
-#pragma unroll
-        for (int kk = 0; kk < P_KC / 2; ++kk) {
-            float av[MT], bv[NT];
-#pragma unroll
-            for (int a = 0; a < MT; ++a) av[a] = pa[a * 32 * P_XS + 2 * kk];
-#pragma unroll
-            for (int b = 0; b < NT; ++b) bv[b] = pb[2 * kk * TN + b * 32];
-#pragma unroll
-            for (int a = 0; a < MT; ++a)
-#pragma unroll
-                for (int b = 0; b < NT; ++b) acc[a][b] = mfma32(av[a], bv[b], acc[a][b]);
-        }
+        fwd_tile_multiply<TN>(acc, pa, pb);
         __syncthreads();
     }
 
@@ -170,11 +145,8 @@ __global__ __launch_bounds__(256) void gemm_f32_mfma_kernel(const float* __restr
 }
 
 // ---- weight gradient ----------------------------------------------------------------------------------------------------------
-// dW[ci][co] = sum over rows of tx(x)[m][ci] * dy[m][co]: M = ci, N = co, K = rows.  Lanes run along the channels for both
-// operands, so both are read straight from [row][channel] LDS tiles.  A workgroup (2 x 2 waves) owns TI x TJ = 64 or 128 input
-// and output channels over the rows of one split (blockIdx.y), in chunks of 32 rows; a wave carries MT x NT accumulators.
-constexpr int Q_KC = 32;
-
+// dW[ci][co] = sum over rows of tx(x)[m][ci] * dy[m][co]: the channel-lane weight-gradient tile of mfma_f32.h over the contiguous
+// rows of one split (blockIdx.y).
 template <int MT, int NT, bool HAS_TX>
 __global__ __launch_bounds__(256) void wgrad_gemm_f32_mfma_kernel(const float* __restrict__ x, int ldx, const float4* __restrict__ tx,
                                                                   const float* __restrict__ dy, int lddy, float* __restrict__ ws,
@@ -237,18 +209,7 @@ __global__ __launch_bounds__(256) void wgrad_gemm_f32_mfma_kernel(const float* _
         store_chunk();
         __syncthreads();
         if (r + Q_KC < r1) load_chunk(r + Q_KC);
-#pragma unroll
-        for (int kk = 0; kk < Q_KC / 2; ++kk) {
-            float av[MT], bv[NT];
-#pragma unroll
-            for (int a = 0; a < MT; ++a) av[a] = pa[2 * kk * TI + a * 32];
-#pragma unroll
-            for (int b = 0; b < NT; ++b) bv[b] = pb[2 * kk * TJ + b * 32];
-#pragma unroll
-            for (int a = 0; a < MT; ++a)
-#pragma unroll
-                for (int b = 0; b < NT; ++b) acc[a][b] = mfma32(av[a], bv[b], acc[a][b]);
-        }
+        wgrad_tile_multiply(acc, pa, pb);
         __syncthreads();
     }
     // slab [split][ci][co]: lanes along co
@@ -264,24 +225,6 @@ __global__ __launch_bounds__(256) void wgrad_gemm_f32_mfma_kernel(const float* _
                 if (ci < Ci) ws[((long)blockIdx.y * Ci + ci) * Co + co] = acc[a][b][q];
             }
     }
-}
-
-// 64-wide tiles where the channel count fits one, or where 128-wide ones would leave most compute units without a workgroup
-bool fwd_narrow(long M, int Co) { return Co <= 64 || (long)umi_cdiv(M, P_TM) * umi_cdiv(Co, 128) < 512; }
-
-// the split of the rows: a function of the shape alone (umi_conv_wgrad_ws_bytes must give the same answer)
-void wgrad_plan(long M, int Ci, int Co, int* ti, int* tj, int* splits, long* rps) {
-    *ti = Ci <= 64 ? 64 : 128;
-    *tj = Co <= 64 ? 64 : 128;
-    const long tiles = (long)umi_cdiv(Ci, *ti) * umi_cdiv(Co, *tj);
-    long want = (512 + tiles - 1) / tiles;               // aim for >= 512 workgroups ...
-    const long chunks = (M + Q_KC - 1) / Q_KC;
-    const long most = (chunks + 3) / 4;                  // ... of at least 4 chunks of 32 rows each
-    if (want > most) want = most;
-    if (want < 1) want = 1;
-    const long cps = (chunks + want - 1) / want;
-    *rps = cps * Q_KC;
-    *splits = (int)((chunks + cps - 1) / cps);
 }
 
 bool flags_ok(int flags) {
@@ -307,7 +250,7 @@ int umi_gemm_f32_mfma(const ConvFwdProblem& p, const void* x, const void* tx, co
                       float* stat_part, hipStream_t s) {
     if (((uintptr_t)x | (uintptr_t)y | (uintptr_t)wp | (uintptr_t)tx) & 15) return UMI_ERR_BADARG;
     const long M = (long)p.N * p.H * p.W;
-    const bool narrow = fwd_narrow(M, p.Co);
+    const bool narrow = fwd_narrow(M, p.Co, 1);
     dim3 grid((unsigned)umi_cdiv(M, P_TM), (unsigned)umi_cdiv(p.Co, narrow ? 64 : 128)), block(256);
 #define UMI_GEMM_F32(WM, WN, MT, NT, TX)                                                                                      \
     hipLaunchKernelGGL((gemm_f32_mfma_kernel<WM, WN, MT, NT, TX>), grid, block, 0, s, (const float*)x, p.ldx, (const float4*)tx, \
@@ -339,7 +282,7 @@ size_t umi_wgrad_gemm_f32_mfma_ws_bound(const WgradProblem& facts) {
     if (!umi_wgrad_gemm_f32_mfma_ok(p)) return 0;
     int ti, tj, splits;
     long rps;
-    wgrad_plan((long)p.N * p.H * p.W, p.Ci, p.Co, &ti, &tj, &splits, &rps);
+    wgrad_plan((long)p.N * p.H * p.W, p.Ci, p.Co, 1, &ti, &tj, &splits, &rps);
     return (size_t)splits * p.Ci * p.Co * sizeof(float);
 }
 
@@ -347,7 +290,7 @@ int umi_wgrad_gemm_f32_mfma(const WgradProblem& p, const void* x, const void* tx
     const long M = (long)p.N * p.H * p.W;
     int ti, tj, splits;
     long rps;
-    wgrad_plan(M, p.Ci, p.Co, &ti, &tj, &splits, &rps);
+    wgrad_plan(M, p.Ci, p.Co, 1, &ti, &tj, &splits, &rps);
     if (o.ws_bytes < (size_t)splits * p.Ci * p.Co * sizeof(float)) return UMI_ERR_WORKSPACE;
     if (((uintptr_t)x | (uintptr_t)dy | (uintptr_t)txa) & 15) return UMI_ERR_BADARG;
     const int tiles_co = umi_cdiv(p.Co, tj);

@@ -325,11 +325,6 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(const T* __restrict__ dy, i
 
 // ---------------------------------------------------------------------------------------------------------
 // elementwise: exact GELU (F.gelu default, vit_seg_modeling.py:102,115), add, broadcast add, dropout
-__device__ __forceinline__ float gelu_f(float u) { return 0.5f * u * (1.f + erff(u * 0.70710678118654752f)); }
-__device__ __forceinline__ float gelu_df(float u) {
-    return 0.5f * (1.f + erff(u * 0.70710678118654752f)) + u * 0.3989422804014327f * __expf(-0.5f * u * u);
-}
-
 // mode 0: y = gelu(x) ; 1: y = g * gelu'(x) (x = pre-activation, g = upstream grad) ; 2: y = x + g ; 3: y = x + g[bcast over rows]
 template <typename T>
 __global__ void ew_kernel(int mode, const T* __restrict__ x, int ldx, const T* __restrict__ g, int ldg, T* __restrict__ y,
@@ -339,19 +334,14 @@ __global__ void ew_kernel(int mode, const T* __restrict__ x, int ldx, const T* _
         int c = (int)(i % C);
         long r = i / C;
         float xv = (float)x[r * ldx + c], o;
-        if (mode == 0) o = gelu_f(xv);
-        else if (mode == 1) o = (float)g[r * ldg + c] * gelu_df(xv);
+        if (mode == 0) o = umi_gelu(xv);
+        else if (mode == 1) o = (float)g[r * ldg + c] * umi_gelu_d(xv);
         else if (mode == 2) o = xv + (float)g[r * ldg + c];
         else o = xv + (float)g[(r % bcast_rows) * ldg + c];
         y[r * ldy + c] = (T)o;
     }
 }
 
-__device__ __forceinline__ unsigned hash32(unsigned a, unsigned b) {           // counter-based RNG (own stream)
-    unsigned x = a * 0x9E3779B1u ^ (b + 0x7F4A7C15u);
-    x ^= x >> 16; x *= 0x85EBCA6Bu; x ^= x >> 13; x *= 0xC2B2AE35u; x ^= x >> 16;
-    return x;
-}
 // fwd (g == nullptr): keep = u >= p ; y = keep ? x/(1-p) : 0 ; mask byte written.   bwd: y = g * mask/(1-p)
 // p == 1 (nn.Dropout(1.0)): u < 1 always, so nothing is kept and the infinite scale is never multiplied in (a select, not
 // a product with the mask): zeros forward and backward
@@ -368,7 +358,7 @@ __global__ void dropout_kernel(const T* __restrict__ x, int ldx, T* __restrict__
         unsigned char k;
         if (bwd) k = mask[i];
         else {
-            float u = (hash32((unsigned)i, seed ^ (unsigned)(i >> 32)) >> 8) * (1.f / 16777216.f);
+            float u = (umi_stream_hash32((unsigned)i, seed ^ (unsigned)(i >> 32)) >> 8) * (1.f / 16777216.f);
             k = u >= p;
             mask[i] = k;
         }
