@@ -669,6 +669,20 @@ int umi_optim_adam_multi_guarded(const void* descs, int n_desc, int total_blocks
                                  double beta1, double beta2, double bc2_sqrt, double eps, double weight_decay,
                                  const double* guard, umi_stream_t stream);
 
+/* Replica fingerprint (data parallel: every rank must hold bit-identical parameters).  One 64-bit word over the tensors of a
+ * umi_optim_desc table; only `p`, `n` and `blk0` are read (blocks of umi_optim_block_elems() words, as for the optimizer), the
+ * tensors are viewed as 32-bit words and are only read.  All arithmetic mod 2^64, G = 0x9E3779B97F4A7C15:
+ *   mix(z):  z ^= z >> 30; z *= 0xBF58476D1CE4E5B9; z ^= z >> 27; z *= 0x94D049BB133111EB; z ^= z >> 31
+ *   H_t = sum_i mix(w_i + G (i + 1))  over the words w_0 .. w_{n-1} of tensor t (in table order);  F = sum_t mix(H_t + G (t + 1))
+ * so a changed bit, two words swapped within a tensor and two tensors swapped all change F, and the order of summation does
+ * not (wrapping addition): the result is the same bits on every device and in NumPy (umi.ddp.fingerprint_numpy).
+ * `ws`: 8-byte aligned device scratch of umi_fingerprint_ws_bytes(total_blocks) bytes (one partial word per block), else
+ * UMI_ERR_WORKSPACE; `out`: one 8-byte aligned device word.  n_desc == 0 writes 0; total_blocks == 0 (only empty tensors) needs
+ * no `ws`.  No atomics; every store is a vector store of a partial or of the result. */
+size_t umi_fingerprint_ws_bytes(int total_blocks);
+int umi_fingerprint_multi(const void* descs, int n_desc, int total_blocks, void* ws, size_t ws_bytes, unsigned long long* out,
+                          umi_stream_t stream);
+
 /* umi_pack_kn / umi_pack_kn8 of many weight tensors in one launch (all the convolution weights of a model after an
  * optimizer step).  `descs`: DEVICE array sorted by blk0; an entry owns ceil(T*Kpad*Npad / umi_pack_block_elems()) blocks. */
 typedef struct umi_pack_desc {

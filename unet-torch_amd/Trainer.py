@@ -8,9 +8,9 @@ zero_grad -> backward -> step -> poly-LR with the pre-increment `iter_num` (:719
 selection on `val_score < best_val_score` (:752); early stop on `counter > patience` (:768);
 files `logs.txt`, `models/{epochN,best,last_epoch}.pt`, `total.png`.
 
-Differences, all host-side: the step body is factored into `train_step` (reused by the
-data-parallel runner, umi/ddp.py) and the running loss is accumulated on the device and read
-back once per epoch instead of a `.item()` sync every step (Trainer.py:727).
+Differences, all host-side: the step body is factored into `train_step` and the running loss is
+accumulated on the device and read back once per epoch instead of a `.item()` sync every step
+(Trainer.py:727).
 `Trainer(..., graph=True)` (keyword-only, or env UMI_TRAINER_GRAPH=1) replays the whole step from a captured HIP graph
 (umi.graphs.GraphedStep) when the model runs on the MI355X and the optimizer is a `umi.optim` one: the first step of a batch
 shape runs eagerly, the second is captured and replayed, ragged last batches run eagerly.  The poly learning-rate rule
@@ -37,6 +37,24 @@ step skips on a non-finite gradient, clips to `max_norm` and follows a dynamic l
 graph mode alike).  Adam then runs on its device schedule in eager mode too (a skipped step must not advance its step count).
 One line per epoch goes to `logs.txt`: `Guard on epoch N: skipped S, clipped C, loss scale X` (S and C count that epoch's
 steps).  A skipped step's loss still counts in the epoch mean.
+`Trainer(..., data_parallel=...)` (keyword-only): None / False = one process, the path above, unchanged; True, a dict of
+`umi.ddp.GradReducer` arguments (which may also hold `check_replicas`, default True), or a ready GradReducer = one run over the
+ranks of a process group (one process per GPU; `dict(world_size=1)` needs no group).  The reducer is built at the start of
+train() and closed by it if it built it; `data_parallel` with a user-set `grad_sync` raises ValueError, True without an
+initialised process group RuntimeError, unequal `len(dataloader['train'])` over the ranks ValueError on every rank before the
+first step.  Covers singe_train and multi_task_train (multi_task_trainRatio raises NotImplementedError).  Step: backward,
+`reducer.sync()`, `optimizer.step()`; with graph=True and more than one rank the graph holds forward + loss + backward captured in
+the reducer's deferred mode, and `reducer.flush()` + `optimizer.step()` follow each replay (under `global_batch=True` the step
+stays eager, one log line says why: collectives are not captured).  Once per phase the ranks all-reduce one float64 vector (loss
+sum, score sum, step count, per-task sums): epoch figures are global sums over global step counts -- validation shards may be
+unequal or empty --, every rank holds the same floats and takes the same best-model and early-stop decisions.  Validation runs on
+rank 0's BatchNorm running statistics (broadcast before the phase; under `global_batch` they agree anyway) and each rank's own
+batches (no collective inside a validation step).  Rank 0 alone writes `logs.txt`, checkpoints and `total.png`, prints and shows
+the progress bar; `best_model` is kept on every rank, so train() returns the best weights everywhere.  With `check_replicas`
+the parameters' device fingerprint (`umi.ddp.check_replicas`) is compared across the ranks after the reducer's broadcast and at
+the end of every training phase (buffers included under `global_batch`): one read of the parameters and 8 bytes read back per
+epoch; RuntimeError on every rank if they differ.  The Trainer does not reseed: augmentation and dropout seeds are the caller's
+business, and the same seed on every rank gives the same masks on every rank.
 `lr_scheduler=True` (what the reference's train.py passes) crashes the reference in its first validation after epoch 5
 (`True.step`); here train() raises NotImplementedError before the first step whenever the run would reach that point.
 The remaining epoch loops of the reference (uncertainty-weighted multi-task, CLTR, Topo losses) are out of scope and raise.
@@ -62,7 +80,7 @@ _OTHER = ('CLTR',)
 class Trainer():
     def __init__(self, model, model_type, dtype, device, output_save_dir, dataloaders, batch_size, optimizer,
                  patience, num_epochs, loss_function, accuracy_metric, lr_scheduler=None, start_epoch=1, *, graph=None,
-                 batch_transform=None, grad_guard=None):
+                 batch_transform=None, grad_guard=None, data_parallel=None):
         self.model = model
         self.model_type = model_type
         self.dtype = dtype
@@ -96,6 +114,11 @@ class Trainer():
         # multi_task_trainRatio: epoch > 5 (host, and in graph mode a device flag), ratioAccuracy of the last step
         self._ratio_gate, self._gate_dev, self._ratio = False, None, None
         self.alpha, self.alpha_list = None, []
+        # data parallel (see the module docstring): the spec, then -- from the start of train() -- the umi.ddp.GradReducer,
+        # whether this Trainer built it, the replica check, this rank, and a line for the log
+        self._dp_spec = None if data_parallel is False else data_parallel
+        self._dp, self._dp_own, self._dp_check, self._rank, self._dp_note = None, False, False, 0, None
+        self._dp_built = None         # the reducer train() built, kept for a later train(): captured graphs hold its addresses
 
         self.save_dir_model = os.path.join(self.output_save_dir, 'models/')
         os.makedirs(self.save_dir_model, exist_ok=True)
@@ -132,8 +155,118 @@ class Trainer():
             % (epoch, r["skipped"] - self._guard_seen[0], r["clipped"] - self._guard_seen[1], r["scale"]))
         self._guard_seen = (r["skipped"], r["clipped"])
 
+    # ---- data parallel ------------------------------------------------------------------
+    @property
+    def _main(self):
+        """Rank 0 (or no data parallel): the rank that writes files and prints."""
+        return self._rank == 0
+
+    def _dp_device(self):
+        p = next(self.model.parameters(), None)
+        return p.device if p is not None else torch.device("cpu")
+
+    def _dp_begin(self):
+        """Start of train(): argument checks, equal step counts, the reducer (whose constructor broadcasts rank 0's replica), the
+        first replica check."""
+        import torch.distributed as dist
+        from umi import ddp
+        spec = self._dp_spec
+        if self.grad_sync is not None:
+            raise ValueError("Trainer(data_parallel=...) runs the gradient exchange itself; do not set trainer.grad_sync as well")
+        if self._ratio_loop():
+            raise NotImplementedError("multi_task_trainRatio under data_parallel: its alpha and count-ratio sums are not reduced "
+                                      "over the ranks")
+        if isinstance(spec, ddp.GradReducer):
+            kw, check, world, group = None, True, spec.world, spec.group
+        else:
+            if spec is not True and not isinstance(spec, dict):
+                raise TypeError("data_parallel takes None / False, True, a dict of umi.ddp.GradReducer arguments (plus "
+                                f"check_replicas) or a GradReducer, not {spec!r}")
+            kw = {} if spec is True else dict(spec)
+            check, world, group = bool(kw.pop("check_replicas", True)), kw.get("world_size"), kw.get("group")
+            if world is None or world > 1:
+                if not (dist.is_available() and dist.is_initialized()):
+                    raise RuntimeError("Trainer(data_parallel=...) over more than one rank needs an initialised process group "
+                                       "(torch.distributed.init_process_group, one process per GPU)")
+                world = dist.get_world_size(group) if world is None else world
+        self._rank = dist.get_rank(group) if world > 1 else 0
+        if world > 1:                         # before anything is touched: a rank with fewer steps would leave the others waiting
+            mine = torch.tensor([len(self.dataloader['train'])], dtype=torch.int64, device=self._dp_device())
+            lens = [torch.empty_like(mine) for _ in range(world)]
+            dist.all_gather(lens, mine, group=group)
+            lens = [int(t.item()) for t in lens]
+            if len(set(lens)) > 1:
+                raise ValueError(f"data_parallel needs the same number of training steps on every rank, got {lens} (per rank); "
+                                 "use a DistributedSampler with drop_last, or equal shards")
+        if kw is None:
+            self._dp, self._dp_own = spec, False
+        elif self._dp_built is not None:
+            self._dp, self._dp_own = self._dp_built.reopen(), True
+        else:
+            self._dp = self._dp_built = ddp.GradReducer(self.model, **kw)
+            self._dp_own = True
+        self._dp_check = check and world > 1
+        self.grad_sync = self._dp.sync
+        if self.graph and world > 1 and self._dp.batch_sync is not None:
+            self._dp_note = ("data_parallel: graph=True runs eagerly under global_batch=True (the statistics all-reduce of "
+                             "every BatchNorm layer and of the loss is a collective, and collectives are not captured)")
+        self._dp_verify()
+
+    def _dp_verify(self):
+        if self._dp_check:
+            from umi import ddp
+            ddp.check_replicas(self.model, self._dp.group, buffers=self._dp.batch_sync is not None)
+
+    def _dp_end(self):
+        """End of train(), also on an error: hand the model back as it came (a reducer built here is closed, so the
+        global-batch switch does not leak into later code)."""
+        if self._dp is None:
+            return
+        if self.grad_sync == self._dp.sync:
+            self.grad_sync = None
+        if self._dp_own:
+            self._dp.close()
+        elif self._dp.batch_sync is not None:
+            from umi import ddp
+            ddp.set_active_batch_sync(self._dp.batch_sync)         # as the caller's reducer had it (validation turns it off)
+        self._dp, self._dp_own = None, False
+
+    def _dp_phase(self, train):
+        """Before a phase.  Validation: what is validated is what rank 0 saves -- without global_batch the BatchNorm running
+        statistics differ per rank, so rank 0's buffers are broadcast; and the loss is each rank's own (the shards may be unequal
+        or empty, so no collective may sit inside a validation step), reduced once afterwards."""
+        if self._dp is None:
+            return
+        import torch.distributed as dist
+        from umi import ddp
+        if self._dp.batch_sync is not None:
+            ddp.set_active_batch_sync(self._dp.batch_sync if train else None)
+        elif not train and self._dp.world > 1:
+            with torch.no_grad():
+                for b in self.model.buffers():
+                    dist.broadcast(b, 0, group=self._dp.group)
+
+    def _dp_reduce(self, sums):
+        """One all-reduce per phase: the float64 sums (losses, score, step count) of all ranks, so every rank derives the same
+        epoch figures and the same model selection and early stop from them."""
+        if self._dp is None or self._dp.world == 1:
+            return sums
+        import torch.distributed as dist
+        vec = torch.tensor(sums, dtype=torch.float64, device=self._dp_device())
+        dist.all_reduce(vec, op=dist.ReduceOp.SUM, group=self._dp.group)
+        return vec.tolist()
+
     # ------------------------------------------------------------------------------------
     def train(self):
+        if self._dp_spec is None:
+            return self._train()
+        try:
+            self._dp_begin()
+            return self._train()
+        finally:
+            self._dp_end()
+
+    def _train(self):
         if self.model_type in _SINGLE:
             if self.loss_function in _TOPO:
                 raise NotImplementedError("Topo-loss warm-up loop (reference singe_train_wup) is out of scope")
@@ -185,18 +318,24 @@ class Trainer():
             out = F.relu(out)
         return out, calc_loss(out, labels, loss_type=self.loss_function)
 
-    def _step_body(self, inputs, labels):
+    def _step_body(self, inputs, labels, deferred=False):
         with torch.set_grad_enabled(True):
             _, loss = self._forward_loss(inputs, labels)
             self.optimizer.zero_grad()
             loss.backward()
+            if deferred:                      # captured data-parallel step: flush() and optimizer.step() follow each replay
+                return loss
             if self.grad_sync is not None:
                 self.grad_sync()
             self.optimizer.step()
         return loss
 
     def _graph_capable(self, inputs):
-        return (self.graph and self.grad_sync is None and inputs.is_cuda and hasattr(self.optimizer, "device_schedule"))
+        if not (self.graph and inputs.is_cuda and hasattr(self.optimizer, "device_schedule")):
+            return False
+        if self._dp is not None:              # collectives are never captured: global-batch statistics need the eager step
+            return self._dp.world == 1 or self._dp.batch_sync is None
+        return self.grad_sync is None
 
     def train_step(self, inputs, labels):
         """One optimisation step (reference Trainer.py:700-726).  Returns the detached loss tensor."""
@@ -227,16 +366,30 @@ class Trainer():
         if ratio and self._gate_dev is None:       # the gate as a device flag: a captured kernel argument would freeze it
             self._gate_dev = torch.full((), float(self._ratio_gate), dtype=torch.float32, device=inputs.device)
 
-        def body(x, *ys):
-            loss = self._step_body(x, tuple(ys) if multi else ys[0])
+        # data parallel over more than one rank: the graph holds forward + loss + backward with the reducer in deferred mode (the
+        # tape fills the gradient buckets and launches no collective); the all-reduce and the optimizer step follow each replay
+        deferred = self._dp is not None and self._dp.world > 1
+
+        def body(x, *ys, deferred=False):
+            loss = self._step_body(x, tuple(ys) if multi else ys[0], deferred)
             extra = (self._task_losses if multi else []) + ([self._ratio] if ratio else [])
             return (loss.detach(),) + tuple(t.detach() for t in extra)
 
         gs = self._graphs.get(key)
         if gs is None and key in self._seen_shapes:
-            gs = self._graphs[key] = GraphedStep(body, flat, warmup=0, optimizers=[self.optimizer])   # 2nd step of a shape: capture, replay
+            if deferred:
+                self._dp.deferred = True
+            try:                                                    # 2nd step of a shape: capture, replay
+                gs = self._graphs[key] = GraphedStep((lambda *a: body(*a, deferred=True)) if deferred else body, flat, warmup=0,
+                                                     optimizers=[self.optimizer])
+            finally:
+                if deferred:
+                    self._dp.deferred = False                       # first steps of other shapes and ragged batches stay eager
         if gs is not None:
             outs = gs(*flat)
+            if deferred:
+                self._dp.flush()
+                self.optimizer.step()
         else:
             # first step of a batch shape (allocations, weight-pack caches) or a ragged batch: eager, on the side stream; its
             # outputs are detached, so no autograd graph of it survives into a later capture (umi/graphs.py)
@@ -377,12 +530,16 @@ class Trainer():
     def singe_train(self):
         multi = self.model_type in _MULTI
         os.makedirs(self.output_save_dir, exist_ok=True)
-        log = open(os.path.join(self.output_save_dir, "logs.txt"), 'a')
+        main = self._main                     # data parallel: rank 0 alone writes files, prints and shows the progress bar
+        log = open(os.path.join(self.output_save_dir, "logs.txt") if main else os.devnull, 'a')
 
         def say(msg, echo=True):
-            if echo:
+            if echo and main:
                 print(msg)
             log.write(msg + "\n")
+
+        if self._dp_note:
+            say(self._dp_note)
 
         use_cuda = torch.cuda.is_available()
         total_mem = f'{torch.cuda.get_device_properties(0).total_memory / 1E9 if use_cuda else 0:.3g}G'
@@ -396,14 +553,16 @@ class Trainer():
                     if self._dev_sched:
                         self.optimizer.sync_host()          # the LR lives on the device in graph mode
                     for group in self.optimizer.param_groups:
-                        print("LR", group['lr'])
+                        if main:
+                            print("LR", group['lr'])
                         log.write(f"LR {group['lr']}\n")
                     since = time.time()
                 self.model.train(train)
+                self._dp_phase(train)
 
                 loss_sum, score_sum, steps = None, None, 0
                 task_sums = [0.0, 0.0]
-                with tqdm(self.dataloader[phase], unit="batch") as bar:
+                with tqdm(self.dataloader[phase], unit="batch", disable=not main) as bar:
                     for inputs, labels in bar:
                         bar.set_description(f"Epoch {epoch}")
                         steps += 1
@@ -418,6 +577,11 @@ class Trainer():
                         if steps % 50 == 0 or not use_cuda:     # avoid a device sync on every step
                             mem = f'{torch.cuda.memory_reserved() / 1E9 if use_cuda else 0:.3g}G/' + total_mem
                             bar.set_postfix(loss=float(loss_sum) / steps, memory=mem)
+                if self._dp is not None:
+                    # global sums over global step counts (a rank's validation shard may be shorter, or empty)
+                    loss_sum, score_sum, steps, *task_sums = self._dp_reduce(
+                        [float(loss_sum) if steps else 0.0, float(score_sum) if score_sum is not None else 0.0, float(steps),
+                         float(task_sums[0]), float(task_sums[1])])
                 epoch_loss = float(loss_sum) / steps
 
                 if train:
@@ -433,7 +597,9 @@ class Trainer():
                     self.meanTimePerEpoch = total_time / epoch
                     say('Curent mean training time per epoch: {:.0f}m {:.0f}s\n'.format(
                         self.meanTimePerEpoch // 60, self.meanTimePerEpoch % 60))
-                    torch.save(self.model.state_dict(), os.path.join(self.save_dir_model, 'last_epoch.pt'))
+                    if main:
+                        torch.save(self.model.state_dict(), os.path.join(self.save_dir_model, 'last_epoch.pt'))
+                    self._dp_verify()                       # the replicas still agree, bit for bit (one word per rank)
                     continue
 
                 val_score = float(score_sum) / steps
@@ -450,9 +616,10 @@ class Trainer():
                     self.best_val_score = selector
                     self.best_loss = epoch_loss
                     say("saving best model")
-                    self.best_model = copy.deepcopy(self.model.state_dict())
-                    torch.save(self.best_model, os.path.join(self.save_dir_model, 'epoch{}.pt'.format(epoch)))
-                    torch.save(self.best_model, os.path.join(self.save_dir_model, 'best.pt'))
+                    self.best_model = copy.deepcopy(self.model.state_dict())      # on every rank: train() returns it everywhere
+                    if main:
+                        torch.save(self.best_model, os.path.join(self.save_dir_model, 'epoch{}.pt'.format(epoch)))
+                        torch.save(self.best_model, os.path.join(self.save_dir_model, 'best.pt'))
                 else:
                     self.early_stop_counter += 1
                 if self.early_stop_counter > self.patience:
@@ -467,7 +634,9 @@ class Trainer():
         say('Best val loss: {:4f}'.format(self.best_loss))
         say('Best val score: {:4f}'.format(self.best_val_score))
         log.close()
-        self.plot_loss_functions('total')
+        if self._main:
+            self.plot_loss_functions('total')
+        self._dp_end()
         if self.best_model:
             self.model.load_state_dict(self.best_model)     # load best model weights
         return self.model

@@ -31,6 +31,10 @@ the decoder buckets travel over xGMI while the encoder backward is still computi
 makes the compute stream wait for the outstanding collectives (no host sync).  The 1/world factor
 is folded into the wgrad kernels' output scale, so the collective is a plain SUM.
 
+`Trainer(..., data_parallel=...)` (Trainer.py) drives all of this behind the reference's Trainer API.  The scheme rests on the
+replicas being bit-identical: `check_replicas(model)` folds the parameters into one 64-bit word on the device
+(`fingerprint`, umi_fingerprint_multi; `fingerprint_numpy` is the definition) and compares the words of the ranks.
+
 `sync()` also supports models that do not use the tape (e.g. the CPU oracle in the gloo tests):
 it then reduces `p.grad` through the same buckets after backward.
 """
@@ -150,6 +154,19 @@ class GradReducer:
         if self.batch_sync is not None and _ACTIVE_SYNC is self.batch_sync:
             set_active_batch_sync(None)
 
+    def reopen(self):
+        """Attach again after close(), with the same buckets: gradient addresses a captured HIP graph holds stay valid (a
+        Trainer whose train() is called a second time).  Rank 0's replica is broadcast again, as at construction."""
+        self.model._umi_grad_sink = self
+        if self.batch_sync is not None:
+            self.model._umi_batch_sync = self.batch_sync
+            set_active_batch_sync(self.batch_sync)
+        self.deferred = False
+        self.reset()
+        if self.world > 1:
+            self.broadcast_parameters(self.model)
+        return self
+
     def _seal(self, b, numel):
         p0 = b.params[0]
         b.flat = torch.zeros(numel, dtype=torch.float32, device=p0.device)
@@ -247,3 +264,114 @@ class GradReducer:
                 if p.grad is not None:
                     p.grad.copy_(b.views[id(p)])
         self.reset()
+
+
+# ---- replica fingerprint ---------------------------------------------------------------------------------------------------
+# The scheme rests on every rank holding bit-identical parameters.  fingerprint() folds a list of tensors into one 64-bit word
+# (umi_fingerprint_multi, include/unetmi.h: one read of the tensors, 8 bytes read back); check_replicas() compares the words
+# of the ranks.  fingerprint_numpy() is the definition, in NumPy.
+_FP_G = 0x9E3779B97F4A7C15
+_FP_MASK = (1 << 64) - 1
+
+
+def _fp_mix(z):
+    """mix() of include/unetmi.h on a Python int (mod 2^64)."""
+    z &= _FP_MASK
+    z ^= z >> 30
+    z = z * 0xBF58476D1CE4E5B9 & _FP_MASK
+    z ^= z >> 27
+    z = z * 0x94D049BB133111EB & _FP_MASK
+    return z ^ (z >> 31)
+
+
+def _fp_words(a):
+    import numpy as np
+    a = np.ascontiguousarray(a)
+    if a.nbytes % 4:
+        raise ValueError(f"fingerprint: a tensor of {a.nbytes} bytes is not a whole number of 32-bit words")
+    return a.reshape(-1).view(np.uint8).view(np.uint32)
+
+
+def fingerprint_numpy(arrays, chunk=1 << 22):
+    """F = sum_t mix(H_t + G (t + 1)),  H_t = sum_i mix(w_i + G (i + 1)) over the 32-bit words of array t; all mod 2^64."""
+    import numpy as np
+    G = np.uint64(_FP_G)
+    F = 0
+    with np.errstate(over="ignore"):
+        for t, a in enumerate(arrays):
+            w, H = _fp_words(a), 0
+            for i0 in range(0, w.size, chunk):
+                part = w[i0:i0 + chunk].astype(np.uint64)
+                z = part + G * np.arange(i0 + 1, i0 + 1 + part.size, dtype=np.uint64)
+                z ^= z >> np.uint64(30)
+                z *= np.uint64(0xBF58476D1CE4E5B9)
+                z ^= z >> np.uint64(27)
+                z *= np.uint64(0x94D049BB133111EB)
+                z ^= z >> np.uint64(31)
+                H = (H + int(z.sum(dtype=np.uint64))) & _FP_MASK
+            F = (F + _fp_mix(H + _FP_G * (t + 1))) & _FP_MASK
+    return F
+
+
+class FingerprintPlan:
+    """The launch of umi_fingerprint_multi over a fixed list of device tensors: descriptor table, scratch and result word are
+    allocated once; launch() only enqueues (two kernels on the current stream), word() reads the 8 bytes back."""
+
+    def __init__(self, tensors):
+        import numpy as np
+        from . import lib as L, ops
+        if not tensors or not all(t.is_cuda and t.device == tensors[0].device for t in tensors):
+            raise ValueError("fingerprint: needs device tensors that live on one device")
+        self.tensors = [t.detach().contiguous() for t in tensors]                 # (a copy of a non-contiguous one is kept alive)
+        blk = L.fn("umi_optim_block_elems")()
+        arr = np.zeros(len(self.tensors), dtype=ops.OPTIM_DESC)
+        b0 = 0
+        for i, t in enumerate(self.tensors):
+            nbytes = t.numel() * t.element_size()
+            if nbytes % 4:
+                raise ValueError(f"fingerprint: a tensor of {nbytes} bytes is not a whole number of 32-bit words")
+            arr[i] = (t.data_ptr(), 0, 0, 0, nbytes // 4, b0, 0)
+            b0 += (nbytes // 4 + blk - 1) // blk
+        self.device, self.blocks, self.bytes = self.tensors[0].device, b0, 4 * int(arr["n"].sum())
+        with torch.cuda.device(self.device):
+            self.table = torch.from_numpy(arr.view(np.uint8).reshape(-1).copy()).to(self.device)
+            self.ws = torch.empty(max(b0, 1), dtype=torch.int64, device=self.device)
+            self.out = torch.empty(1, dtype=torch.int64, device=self.device)
+
+    def launch(self):
+        from . import lib as L, ops
+        with torch.cuda.device(self.device):
+            L.call("umi_fingerprint_multi", self.table.data_ptr(), len(self.tensors), self.blocks, self.ws.data_ptr(),
+                   self.ws.numel() * 8, self.out.data_ptr(), ops._stream())
+        return self
+
+    def word(self):
+        return int(self.out.item()) & _FP_MASK
+
+
+def fingerprint(tensors):
+    """The fingerprint of a list of tensors: device tensors through the HIP kernel (all on one device), CPU tensors through the
+    NumPy statement.  The same bits either way."""
+    tensors = list(tensors)
+    if not any(t.is_cuda for t in tensors):
+        return fingerprint_numpy([t.detach().contiguous().numpy() for t in tensors])
+    return FingerprintPlan(tensors).launch().word()
+
+
+def check_replicas(model, group=None, buffers=False):
+    """Every rank fingerprints its parameters (and buffers, when they are meant to be identical too: global_batch), the words
+    are all-gathered, and EVERY rank raises RuntimeError when they differ.  Returns this rank's word."""
+    tensors = list(model.parameters()) + (list(model.buffers()) if buffers else [])
+    word = fingerprint(tensors)
+    world = dist.get_world_size(group) if dist.is_available() and dist.is_initialized() else 1
+    if world == 1:
+        return word
+    dev = tensors[0].device if tensors else torch.device("cpu")
+    mine = torch.tensor([word - (1 << 64) if word >> 63 else word], dtype=torch.int64, device=dev)
+    got = [torch.empty_like(mine) for _ in range(world)]
+    dist.all_gather(got, mine, group=group)
+    words = [int(g.item()) & _FP_MASK for g in got]
+    if len(set(words)) > 1:
+        raise RuntimeError("data parallel: the replicas differ (fingerprint of the parameters%s per rank: %s)"
+                           % (" and buffers" if buffers else "", ", ".join(f"{r}: {w:#018x}" for r, w in enumerate(words))))
+    return word
