@@ -489,6 +489,16 @@ int umi_dice_ce_fwd(const float* logits, const void* target, int target_dtype, i
                     size_t ws_bytes, umi_stream_t stream);
 int umi_dice_ce_bwd(const float* logits, const void* target, int target_dtype, const float* stats, const float* gout, int N,
                     int C, long HW, float* dlogits, umi_stream_t stream);
+/* The forward of `items` independent losses in one pass (a validation group: per-item figures from one batched forward).
+ * logits [items*n, C, HW] and target [items*n, HW] hold `items` consecutive groups of n images; stats is [items][3*C + 2], and row i
+ * holds the bits umi_dice_ce_fwd leaves for N = n on the i-th slice: the same block decomposition per item (grid = items x that
+ * call's grid), the same float64 fixed-order sums (one finalize block per item), no atomics.  Forward only.
+ * ws: umi_dice_ce_items_ws_bytes(items, n, C, HW) bytes = items x umi_dice_ce_ws_bytes(n, C, HW); nothing else is written.
+ * UMI_ERR_BADARG (nothing launched): a null pointer, items, n or HW <= 0, items > 65535, an unknown target_dtype;
+ * UMI_ERR_UNSUPPORTED: C outside 1..8; UMI_ERR_WORKSPACE: ws_bytes too small. */
+size_t umi_dice_ce_items_ws_bytes(int items, int n, int C, long HW);
+int umi_dice_ce_fwd_items(const float* logits, const void* target, int target_dtype, int items, int n, int C, long HW,
+                          float* stats, void* ws, size_t ws_bytes, umi_stream_t stream);
 /* The same loss of a data-parallel group's WHOLE batch, every rank holding N of its images:
  *   umi_dice_ce_sums        sums[3*C + 1] (float64) = {sum p*t | sum p*p | sum t | CE sum} of this rank's pixels, added in
  *                           umi_dice_ce_fwd's order; the ranks then add their sums and their pixel counts;

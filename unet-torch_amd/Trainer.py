@@ -55,6 +55,23 @@ the parameters' device fingerprint (`umi.ddp.check_replicas`) is compared across
 the end of every training phase (buffers included under `global_batch`): one read of the parameters and 8 bytes read back per
 epoch; RuntimeError on every rank if they differ.  The Trainer does not reseed: augmentation and dropout seeds are the caller's
 business, and the same seed on every rank gives the same masks on every rank.
+`Trainer(..., val_batch=k)` (keyword-only, after `data_parallel`): None = the validation loop above, one `eval_step` per loader
+item, untouched; an int k >= 1 = in singe_train's validation phase (multi_task_train included) loader items go through
+`_to_device(train=False)` one by one as before (`batch_transform` included) and are gathered into groups of up to k CONSECUTIVE
+items of EQUAL shapes -- a shape change or the end of the loader closes a group early.  One eval-mode forward runs over the
+concatenated group; loss and score are then evaluated per item on that item's slice (`loss.calc_loss_items`: the loop over
+`calc_loss`, or one `umi_dice_ce_fwd_items` pass for 'dice_bce_mc' on the fused kernels' inputs, same bits; the regression ReLU
+and the two heads / per-task losses as in `_forward_loss`; computed once when loss_function == accuracy_metric), and the rows are
+added to the running sums [loss, score, task 1, task 2] -- one device vector of the losses' dtype -- by k sequential adds in
+item order.  `steps` counts loader items, so the epoch figures, the per-task lists, model selection, early stop, the log lines and
+the data-parallel phase reduction see what the item-by-item loop gives them.  With graph=True and device inputs a FULL group
+replays from a `umi.graphs.GraphedEval` kept in `_eval_graphs` by group shapes (`_graphs` stays the training graphs): the first
+full group of a shape runs eagerly, the second is captured (forward, per-item values, the adds into the running sums), short groups stay eager.
+The eval graph holds no weight-pack node: GraphedEval refreshes the model's `ops.PackCache` eagerly before the capture and before
+every replay, keyed on the parameter versions the cache tracks, so a replay after a training phase or a `load_state_dict` reads
+current weights; BatchNorm running statistics are device tensors the captured kernels re-read.  `multi_task_trainRatio` with
+`val_batch` raises NotImplementedError at train() (its validation bookkeeping is its own); a `val_batch` that is not None or a
+positive int raises ValueError.
 `lr_scheduler=True` (what the reference's train.py passes) crashes the reference in its first validation after epoch 5
 (`True.step`); here train() raises NotImplementedError before the first step whenever the run would reach that point.
 The remaining epoch loops of the reference (uncertainty-weighted multi-task, CLTR, Topo losses) are out of scope and raise.
@@ -68,7 +85,7 @@ import torch
 import torch.nn.functional as F
 from tqdm import tqdm
 
-from loss import calc_loss, multi_task_ratio_loss
+from loss import calc_loss, calc_loss_items, multi_task_ratio_loss
 
 _SINGLE = ('single', 'TransUnet', 'regression', 'regression_t', 'attention')
 _TOPO = ('TopoCount', 'TopoCount2', 'TopoLoss', 'TopoLoss2', 'MyTopoLoss1', 'MyTopoLoss2', 'MyTopoLossGraph',
@@ -80,7 +97,7 @@ _OTHER = ('CLTR',)
 class Trainer():
     def __init__(self, model, model_type, dtype, device, output_save_dir, dataloaders, batch_size, optimizer,
                  patience, num_epochs, loss_function, accuracy_metric, lr_scheduler=None, start_epoch=1, *, graph=None,
-                 batch_transform=None, grad_guard=None, data_parallel=None):
+                 batch_transform=None, grad_guard=None, data_parallel=None, val_batch=None):
         self.model = model
         self.model_type = model_type
         self.dtype = dtype
@@ -119,6 +136,13 @@ class Trainer():
         self._dp_spec = None if data_parallel is False else data_parallel
         self._dp, self._dp_own, self._dp_check, self._rank, self._dp_note = None, False, False, 0, None
         self._dp_built = None         # the reducer train() built, kept for a later train(): captured graphs hold its addresses
+        # batched validation (see the module docstring): the group size, the eval graphs by group shapes (`_graphs` stays the
+        # training graphs), the shapes that ran eagerly once, and the running sums [loss, score, task 1, task 2] (one vector of
+        # the losses' dtype, where the model runs)
+        if val_batch is not None and (isinstance(val_batch, bool) or not isinstance(val_batch, int) or val_batch < 1):
+            raise ValueError(f"val_batch takes None or a positive int, not {val_batch!r}")
+        self.val_batch = val_batch
+        self._eval_graphs, self._eval_seen, self._val_sums = {}, set(), None
 
         self.save_dir_model = os.path.join(self.output_save_dir, 'models/')
         os.makedirs(self.save_dir_model, exist_ok=True)
@@ -275,6 +299,9 @@ class Trainer():
             if self.loss_function == 'multi_task_loss':
                 raise NotImplementedError("uncertainty-weighted multi-task loop (reference multi_task_uc_train) is out of scope")
             if self.loss_function == 'multi_task_loss_ratio':
+                if self.val_batch is not None:
+                    raise NotImplementedError("multi_task_trainRatio with val_batch: its validation bookkeeping (alpha, the "
+                                              "count-ratio sums) is its own and is not batched")
                 return self.multi_task_trainRatio()
             return self.multi_task_train()
         if self.model_type in _OTHER:
@@ -413,6 +440,98 @@ class Trainer():
                 return loss.detach(), torch.zeros((), device=loss.device)
             score = calc_loss(out, labels, loss_type=self.accuracy_metric)
         return loss.detach(), score.detach()
+
+    # ---- batched validation (val_batch=k) ------------------------------------------------
+    def _val_group_fn(self, items):
+        """The function of one validation group of `items` loader items laid end to end: f(x, *labels) runs ONE eval-mode
+        forward, evaluates loss and score per item on that item's slice (loss.calc_loss_items), adds the rows [loss, score,
+        task 1, task 2] to the running sums `self._val_sums` by `items` sequential adds in item order, and returns the
+        [items, 4] rows.  No host synchronisation, one stream: it is what a umi.graphs.GraphedEval captures."""
+        multi = self.model_type in _MULTI
+        relu = self.model_type in ('regression', 'regression_t')
+
+        def group(x, *ys):
+            with torch.no_grad():
+                if multi:                                        # as _forward_loss / eval_step: no validation score there
+                    outs = tuple(F.relu(o) for o in self.model(x))
+                    t1, t2 = (calc_loss_items(o, l, items, loss_type=self.loss_function) for o, l in zip(outs, ys))
+                    loss, score = t1 + t2, torch.zeros_like(t1)
+                else:
+                    out = self.model(x)
+                    if relu:
+                        out = F.relu(out)
+                    loss = calc_loss_items(out, ys[0], items, loss_type=self.loss_function)
+                    score = loss if self.accuracy_metric == self.loss_function else \
+                        calc_loss_items(out, ys[0], items, loss_type=self.accuracy_metric)
+                    t1 = t2 = torch.zeros_like(loss)
+                rows = torch.stack([v.detach() for v in (loss, score, t1, t2)], dim=1)
+                if self._val_sums is None or (self._val_sums.dtype, self._val_sums.device) != (rows.dtype, rows.device):
+                    # the first group ever (always an eager one): sums of the losses' own dtype, as `loss_sum + loss` keeps them
+                    self._val_sums = torch.zeros_like(rows[0])
+                    self._eval_graphs, self._eval_seen = {}, set()       # (graphs hold the old vector's address)
+                for i in range(items):                           # item order, one add each: the sums of the item-by-item loop
+                    self._val_sums.add_(rows[i])
+            return rows
+        return group
+
+    def _run_val_group(self, group):
+        """group: [(inputs, labels)] of equal shapes, already through _to_device(train=False)."""
+        items = len(group)
+        multi = isinstance(group[0][1], (list, tuple))
+        x = torch.cat([g[0] for g in group]) if items > 1 else group[0][0]
+        if multi:
+            ys = [torch.cat([g[1][j] for g in group]) if items > 1 else group[0][1][j] for j in range(len(group[0][1]))]
+        else:
+            ys = [torch.cat([g[1] for g in group]) if items > 1 else group[0][1]]
+        flat, key = [x] + ys, None
+        if self.graph and x.is_cuda and items == self.val_batch:
+            key = tuple(tuple(t.shape) for t in flat)
+            ge = self._eval_graphs.get(key)
+            if ge is None and key in self._eval_seen:            # 2nd full group of a shape: capture (nothing executes), replay
+                from umi.graph import pack_cache_of
+                from umi.graphs import GraphedEval
+                ge = self._eval_graphs[key] = GraphedEval(self._val_group_fn(items), flat, pack_cache=pack_cache_of(self.model))
+            if ge is not None:
+                ge(*flat)
+                return
+        self._val_group_fn(items)(*flat)                         # 1st full group of a shape (allocations, pack entries), short
+        if key is not None:                                      # groups, graph=False, CPU models: eager
+            self._eval_seen.add(key)
+
+    def _validate_batched(self, bar, epoch, use_cuda, total_mem):
+        """The validation phase under val_batch=k: loader items gathered into groups of up to k consecutive items of equal
+        shapes (a shape change or the end of the loader closes a group early).  Returns (loss_sum, score_sum, steps,
+        task_sums) as the item-by-item loop keeps them; `steps` counts loader items."""
+        group, shapes, steps = [], None, 0
+        if self._val_sums is not None:
+            self._val_sums.zero_()
+
+        def flush():
+            if group:
+                self._run_val_group(group)
+                del group[:]
+
+        for inputs, labels in bar:
+            bar.set_description(f"Epoch {epoch}")
+            steps += 1
+            inputs, labels = self._to_device(inputs, labels, train=False)
+            ls = labels if isinstance(labels, (list, tuple)) else (labels,)
+            sh = (tuple(inputs.shape),) + tuple(tuple(l.shape) for l in ls)
+            if group and sh != shapes:
+                flush()
+            shapes = sh
+            group.append((inputs, labels))
+            if len(group) == self.val_batch:
+                flush()
+                if not use_cuda or steps // 50 > (steps - self.val_batch) // 50:    # no device sync on every group
+                    mem = f'{torch.cuda.memory_reserved() / 1E9 if use_cuda else 0:.3g}G/' + total_mem
+                    bar.set_postfix(loss=float(self._val_sums[0]) / steps, memory=mem)
+        flush()
+        if not steps:
+            return None, None, 0, [0.0, 0.0]
+        sums = self._val_sums.clone()
+        multi = self.model_type in _MULTI
+        return sums[0], sums[1], steps, ([sums[2], sums[3]] if multi else [0.0, 0.0])
 
     # ------------------------------------------------------------------------------------
     def _check_ratio_scheduler(self):
@@ -563,6 +682,9 @@ class Trainer():
                 loss_sum, score_sum, steps = None, None, 0
                 task_sums = [0.0, 0.0]
                 with tqdm(self.dataloader[phase], unit="batch", disable=not main) as bar:
+                    if not train and self.val_batch is not None:
+                        loss_sum, score_sum, steps, task_sums = self._validate_batched(bar, epoch, use_cuda, total_mem)
+                        bar = ()
                     for inputs, labels in bar:
                         bar.set_description(f"Epoch {epoch}")
                         steps += 1

@@ -18,14 +18,16 @@ __device__ __forceinline__ int load_target(const void* t, int tdtype, long i) {
 }
 
 // part row layout: [A_0..A_{NC-1}, B_0.., T_0.., ce_sum]
+// One block's partial row: block `bx` of `gx` walks the pixels bx*256 + tid, + gx*256, ... of `total`.  Shared by the whole-batch
+// kernel and the per-item one below, so that an item's rows are the bits a whole-batch call on that item's slice leaves.
 template <int NC>
-__global__ __launch_bounds__(256) void dice_ce_stats_kernel(const float* __restrict__ logits, const void* __restrict__ target,
-                                                            int tdtype, long HW, long total, float* __restrict__ part) {
+__device__ __forceinline__ void dice_ce_stats_block(const float* __restrict__ logits, const void* __restrict__ target, int tdtype,
+                                                    long HW, long total, long bx, long gx, float* __restrict__ part) {
     __shared__ float red[4][3 * NC + 1];
     float a[NC], b[NC], tt[NC], ce = 0.f;
 #pragma unroll
     for (int c = 0; c < NC; ++c) a[c] = b[c] = tt[c] = 0.f;
-    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
+    for (long i = bx * 256 + threadIdx.x; i < total; i += gx * 256) {
         const long n = i / HW, hw = i - n * HW;
         const float* x = logits + n * NC * HW + hw;
         float v[NC], m = -INFINITY;
@@ -68,8 +70,28 @@ __global__ __launch_bounds__(256) void dice_ce_stats_kernel(const float* __restr
     }
     __syncthreads();
     if (threadIdx.x < 3 * NC + 1)
-        part[(long)blockIdx.x * (3 * NC + 1) + threadIdx.x] =
+        part[bx * (3 * NC + 1) + threadIdx.x] =
             red[0][threadIdx.x] + red[1][threadIdx.x] + red[2][threadIdx.x] + red[3][threadIdx.x];
+}
+
+template <int NC>
+__global__ __launch_bounds__(256) void dice_ce_stats_kernel(const float* __restrict__ logits, const void* __restrict__ target,
+                                                            int tdtype, long HW, long total, float* __restrict__ part) {
+    dice_ce_stats_block<NC>(logits, target, tdtype, HW, total, (long)blockIdx.x, (long)gridDim.x, part);
+}
+
+// bytes of one target element, by target_dtype
+__device__ __forceinline__ long target_elem_bytes(int tdtype) { return tdtype == 0 ? 8 : (tdtype == 2 ? 1 : 4); }
+
+// `items` independent groups of `total` = n*HW pixels each, laid end to end: blockIdx.y = the item, blockIdx.x of gridDim.x = the
+// block of the whole-batch kernel on that item's slice.  part: [items][gridDim.x][3*NC + 1].
+template <int NC>
+__global__ __launch_bounds__(256) void dice_ce_stats_items_kernel(const float* __restrict__ logits, const void* __restrict__ target,
+                                                                  int tdtype, long HW, long total, float* __restrict__ part) {
+    const long item = blockIdx.y;
+    dice_ce_stats_block<NC>(logits + item * total * NC,
+                            reinterpret_cast<const char*>(target) + item * total * target_elem_bytes(tdtype), tdtype, HW, total,
+                            (long)blockIdx.x, (long)gridDim.x, part + item * (long)gridDim.x * (3 * NC + 1));
 }
 
 // Column sums of the partial rows by one workgroup of 1,024 threads = 32 columns x 32 row lanes; lane l sums rows l, l+32, ... in
@@ -103,6 +125,19 @@ __global__ __launch_bounds__(1024) void dice_ce_finalize_kernel(const float* __r
                                                                 float* __restrict__ stats) {
     __shared__ double sums[32];
     const int K = 3 * NC + 1;
+    dice_ce_col_sums(part, rows, K, sums);
+    if ((int)threadIdx.x < K) stats[threadIdx.x] = (float)sums[threadIdx.x];
+    __syncthreads();
+    if (threadIdx.x == 0) stats[K] = dice_ce_loss(sums, NC, (double)total);
+}
+
+// one workgroup per item: the kernel above on that item's rows, into that item's stats row
+__global__ __launch_bounds__(1024) void dice_ce_finalize_items_kernel(const float* __restrict__ part, int rows, int NC, long total,
+                                                                      float* __restrict__ stats) {
+    __shared__ double sums[32];
+    const int K = 3 * NC + 1;
+    part += (long)blockIdx.x * rows * K;
+    stats += (long)blockIdx.x * (K + 1);
     dice_ce_col_sums(part, rows, K, sums);
     if ((int)threadIdx.x < K) stats[threadIdx.x] = (float)sums[threadIdx.x];
     __syncthreads();
@@ -198,6 +233,30 @@ extern "C" int umi_dice_ce_fwd(const float* logits, const void* target, int targ
     launch_dice_ce_stats(logits, target, target_dtype, C, HW, total, rows, ws, s);
     UMI_LAUNCH_CHECK();
     hipLaunchKernelGGL(dice_ce_finalize_kernel, dim3(1), dim3(1024), 0, s, (const float*)ws, rows, C, total, stats);
+    UMI_LAUNCH_CHECK();
+    return UMI_OK;
+}
+
+extern "C" size_t umi_dice_ce_items_ws_bytes(int items, int n, int C, long HW) {
+    return (size_t)items * umi_dice_ce_ws_bytes(n, C, HW);
+}
+
+extern "C" int umi_dice_ce_fwd_items(const float* logits, const void* target, int target_dtype, int items, int n, int C, long HW,
+                                     float* stats, void* ws, size_t ws_bytes, umi_stream_t st) {
+    if (!logits || !target || !stats || !ws || items <= 0 || items > 65535 || n <= 0 || HW <= 0 || target_dtype < 0 ||
+        target_dtype > 3)
+        return UMI_ERR_BADARG;
+    if (C < 1 || C > 8) return UMI_ERR_UNSUPPORTED;
+    if (ws_bytes < umi_dice_ce_items_ws_bytes(items, n, C, HW)) return UMI_ERR_WORKSPACE;
+    const long total = (long)n * HW;
+    const int rows = blocks_for(total);
+    hipStream_t s = (hipStream_t)st;
+#define GO(NC) hipLaunchKernelGGL(dice_ce_stats_items_kernel<NC>, dim3(rows, items), dim3(256), 0, s, logits, target, target_dtype, HW, total, (float*)ws)
+    switch (C) { case 1: GO(1); break; case 2: GO(2); break; case 3: GO(3); break; case 4: GO(4); break;
+                 case 5: GO(5); break; case 6: GO(6); break; case 7: GO(7); break; default: GO(8); }
+#undef GO
+    UMI_LAUNCH_CHECK();
+    hipLaunchKernelGGL(dice_ce_finalize_items_kernel, dim3(items), dim3(1024), 0, s, (const float*)ws, rows, C, total, stats);
     UMI_LAUNCH_CHECK();
     return UMI_OK;
 }

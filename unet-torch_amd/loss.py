@@ -39,6 +39,12 @@ the pixel count before the quotients are formed, and the backward is world x the
 so that the averaged parameter gradients are those of the global loss.  Shards must be equal; 'Tversky', 'TopK' and 'BCE_HEM',
 which couple the batch in ways this does not cover, raise NotImplementedError while the switch is on.
 
+`calc_loss_items(pred, target, items, loss_type)` is the validation phase's form (Trainer(val_batch=k)): pred and target hold
+`items` consecutive groups of n images, and element i of the [items] result is `calc_loss` of the i-th group -- by default that
+very loop over contiguous slices, so every name behaves as in `calc_loss`; 'dice_bce_mc' on the fused kernels' inputs takes one
+`umi_dice_ce_fwd_items` pass whose stats rows are bit for bit those of `umi_dice_ce_fwd` on the slices (values only, no backward).
+It raises under an active global-batch switch.
+
 The remaining names raise NotImplementedError: 'dice', 'dice_score', 'dice_score_mc' and 'log_cosh_dice_loss' call
 DiceLoss() without n_classes, 'FL' names an undefined BinaryFocalLoss, HausdorffERLoss has no gradient and
 ActiveContourLoss hard-codes 512x512 tensors on cuda:0 in the reference itself.
@@ -593,6 +599,44 @@ def calc_loss(pred, target, bce_weight=0.5, loss_type='mse'):
     if loss_type in _OUT_OF_SCOPE:
         raise NotImplementedError(f"loss_type {loss_type!r} is outside the MI355X hot-path scope")
     raise ValueError(f"unknown loss_type {loss_type!r}")
+
+
+def _dice_ce_items(pred, target, items):
+    """'dice_bce_mc' of `items` consecutive groups in one pass: umi_dice_ce_fwd_items, whose stats row i holds the bits
+    umi_dice_ce_fwd leaves on the i-th slice.  Forward only."""
+    from umi import lib as L, ops
+    n, C = pred.shape[0] // items, pred.shape[1]
+    HW = pred[0, 0].numel()
+    stats = torch.empty((items, 3 * C + 2), dtype=torch.float32, device=pred.device)
+    ws = ops.workspace(L.fn("umi_dice_ce_items_ws_bytes")(items, n, C, HW), pred.device)
+    L.call("umi_dice_ce_fwd_items", pred.data_ptr(), target.data_ptr(), _TARGET_DTYPES[target.dtype], items, n, C, HW,
+           stats.data_ptr(), ws.data_ptr(), ws.numel(), ops._stream())
+    return stats[:, 3 * C + 1].clone()
+
+
+# False: calc_loss_items runs the per-slice loop for 'dice_bce_mc' too (the A/B switch of tools/bench_validation.py)
+ITEMS_KERNEL = True
+
+
+def calc_loss_items(pred, target, items, loss_type='mse'):
+    """The losses of `items` consecutive groups of n images each: pred [items*n, C, H, W] and target [items*n, ...] ->
+    a [items] tensor whose element i is calc_loss(pred[i*n:(i+1)*n], target[i*n:(i+1)*n], loss_type=loss_type).  By default
+    literally that loop over contiguous slices, so every loss name behaves as in calc_loss (the names that raise included);
+    'dice_bce_mc' on inputs of the fused kernels takes one pass for all items (same bits).  Values only: made for the
+    validation phase (Trainer(val_batch=k)), where nothing is differentiated.  Raises under an active global-batch switch
+    (umi.ddp), where a loss is that of the data-parallel group's whole batch and a per-item value has no meaning."""
+    items = int(items)
+    if items < 1 or pred.shape[0] % items or target.shape[0] != pred.shape[0]:
+        raise ValueError(f"calc_loss_items: {pred.shape[0]} predictions and {target.shape[0]} targets do not split into {items} "
+                         "equal groups")
+    if _batch_sync() is not None:
+        raise NotImplementedError("calc_loss_items under global_batch: losses are those of the group's whole batch there")
+    n = pred.shape[0] // items
+    if (loss_type == 'dice_bce_mc' and ITEMS_KERNEL and items <= 65535 and not (torch.is_grad_enabled() and pred.requires_grad)
+            and _fused_ok(pred, target)):
+        return _dice_ce_items(pred, target, items)
+    vals = [calc_loss(pred[i * n:(i + 1) * n], target[i * n:(i + 1) * n], loss_type=loss_type) for i in range(items)]
+    return torch.stack([v if torch.is_tensor(v) else torch.as_tensor(v) for v in vals])
 
 
 # ---------------------------------------------------------------------------------------------------------------------

@@ -24,6 +24,10 @@ Rules that make the capture valid (the class enforces what it can):
   * collectives are never captured: data parallel runs capture forward + backward only, with `GradReducer.deferred = True`
     (the tape fills the gradient buckets and launches nothing), and call `reducer.flush()` + `optimizer.step()` after each
     replay (bench.py, UMI_DDP_LAUNCH=graph); with a process group alive the capture uses the thread_local error mode.
+
+`GraphedEval` is the sibling for a no-grad function (an eval-mode forward and what follows it): the same static-input and
+error-mode rules, plus the one hazard an eval graph adds -- the kernel-layout weight copies it reads are refreshed outside the
+graph (see the class).
 """
 import torch
 
@@ -103,4 +107,62 @@ class GraphedStep:
         self.graph.replay()
         if self._params:
             torch.autograd.graph.increment_version(self._params)
+        return self.static_outputs
+
+
+class GraphedEval:
+    """HIP-graph capture of a no-grad function of static-shape device inputs (an eval-mode forward, with or without the loss
+    evaluation behind it): static input copies, one capture, `__call__` copies the inputs in, replays and returns the static
+    outputs (overwritten by the next replay: clone what must survive).
+
+    Protocol, as GraphedStep's with warmup=0:
+      * the caller has ALREADY run `fn` eagerly once on inputs of these shapes (allocations, the shared `ops.workspace`, the
+        weight-pack entries and tables and `PackCache._buffers()` exist before the capture; the constructor executes nothing);
+      * nothing in `fn` may synchronise with the host;
+      * the captured graph is one linear chain on one stream: no side streams, no parallel branches inside `fn`.
+
+    Stale weights.  An eval-mode forward reads the kernel-layout weight copies of the model's `ops.PackCache`, persistent
+    buffers re-packed in place when the parameter's version moved.  `pack_cache` (the model's cache, `umi.graph.pack_cache_of(
+    model)`; a sequence of them for several models; None when `fn` reads no such copies) is brought up to date EAGERLY, by one
+    `refresh()` (one launch per storage dtype, none when nothing is stale), before the capture and before every replay -- keyed
+    on the versions the cache tracks, so an optimizer step, a GraphedStep replay (which bumps the versions) or a
+    `load_state_dict` between two replays is picked up.  During the capture the cache is held: `refresh()` records no pack
+    node, and raises if an entry is stale.  The graph therefore holds no pack node and always reads current weights.  State
+    read in place as device tensors (BatchNorm running statistics, from which the eval transform is computed inside the
+    forward) needs nothing: the captured kernels re-read the current buffers."""
+
+    def __init__(self, fn, example_inputs, pack_cache=None, capture_error_mode=None):
+        if not all(t.is_cuda for t in example_inputs):
+            raise RuntimeError("GraphedEval needs device-resident example inputs")
+        caches = pack_cache if isinstance(pack_cache, (list, tuple)) else [pack_cache]
+        self._caches = [c for c in caches if c is not None]
+        self._fn = fn                           # keeps the model alive: the graph refers to its tensors by address
+        self.static_inputs = [t.clone() for t in example_inputs]
+        if capture_error_mode is None:          # the same rule as GraphedStep: a process group's watchdog thread polls events
+            import torch.distributed as dist
+            multi = dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1
+            capture_error_mode = "thread_local" if multi else "global"
+        self.refresh()
+        torch.cuda.synchronize()
+        self.graph = torch.cuda.CUDAGraph()
+        for c in self._caches:
+            c.held = True
+        try:
+            with torch.no_grad(), torch.cuda.graph(self.graph, capture_error_mode=capture_error_mode):
+                self.static_outputs = fn(*self.static_inputs)
+        finally:
+            for c in self._caches:
+                c.held = False
+
+    def refresh(self):
+        """Stale weight copies -> current, outside the graph (a host loop over the cache's entries; launches only if stale)."""
+        for c in self._caches:
+            c.refresh()
+
+    def __call__(self, *inputs):
+        for dst, src in zip(self.static_inputs, inputs):
+            if dst.data_ptr() != src.data_ptr():
+                dst.copy_(src, non_blocking=True)
+        self.refresh()
+        self.graph.replay()
         return self.static_outputs

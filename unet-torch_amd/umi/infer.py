@@ -5,6 +5,7 @@
     mask = infer.predict_mask(model, x)       # eval-mode forward (BatchNorm from running statistics) + argmax, uint8 [N,H,W]
 
     x = infer.preprocess(img, input_size=(512, 512))   # + the reference's cubic scipy.ndimage.zoom resize, on the device
+    predict = infer.GraphedPredictor(model, x)         # the same call replayed from a HIP graph for inputs of x's shape
 
 Binary (one-logit) models, the reference's test.py:391-455 and loss.py:422-440:
 
@@ -259,6 +260,49 @@ def predict_binary_mask(model, x, out_hw=None):
         return _binary_head(out, out_hw)
     finally:
         model.train(was_training)
+
+
+class GraphedPredictor:
+    """predict_mask (predict_binary_mask for a one-logit model) replayed from a HIP graph for inputs of one shape:
+
+        predict = infer.GraphedPredictor(model, example_x)
+        mask = predict(x)                         # uint8 [N,H,W], or a tuple of them for a two-headed model
+
+    The constructor runs the eval-mode forward once eagerly and captures it, with the mask kernels behind it, in a
+    umi.graphs.GraphedEval that holds the model's weight-pack cache: a call copies x into the static input, brings the weight
+    copies up to date if a parameter changed since (optimizer step, load_state_dict), replays and returns CLONES of the static
+    masks.  Inputs of another shape go through predict_mask / predict_binary_mask.  The model's training flag is left as it was."""
+
+    def __init__(self, model, example_x):
+        from . import graph as G
+        from .graphs import GraphedEval
+        self.model = model
+        x = example_x.to("cuda")
+        self.shape, self.dtype = tuple(x.shape), x.dtype
+
+        def fwd(xs):
+            out = model(xs)
+            self._tuple = isinstance(out, tuple)
+            outs = out if self._tuple else (out,)
+            self.binary = outs[0].shape[1] == 1
+            return tuple((binary_mask if o.shape[1] == 1 else argmax_mask)(o) for o in outs)
+
+        was_training = model.training
+        model.eval()
+        try:
+            with torch.no_grad():
+                fwd(x)                            # eager once: allocations, pack entries, the shared workspace
+            self._ge = GraphedEval(fwd, [x], pack_cache=G.pack_cache_of(model))
+        finally:
+            model.train(was_training)
+
+    @torch.no_grad()
+    def __call__(self, x):
+        x = x.to("cuda")
+        if tuple(x.shape) != self.shape or x.dtype != self.dtype:
+            return (predict_binary_mask if self.binary else predict_mask)(self.model, x)
+        masks = tuple(m.clone() for m in self._ge(x))
+        return masks if self._tuple else masks[0]
 
 
 @torch.no_grad()

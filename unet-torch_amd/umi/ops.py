@@ -364,6 +364,13 @@ class PackCache:
         # parameter versions were when it was captured (e.g. a captured forward + backward whose optimizer step runs outside
         # the graph: nothing is stale at capture time, everything is at the second replay)
         force = torch.cuda.is_available() and torch.cuda.is_current_stream_capturing()
+        if force and getattr(self, "held", False):
+            # umi.graphs.GraphedEval: the owner of the capture refreshes this cache EAGERLY before the capture and before every
+            # replay that follows a parameter change, so the graph holds no pack node; an entry that is stale here would be
+            # read stale by every replay
+            if any(e.w() is not None and e.ver != self._ver(e.w()) for e in (*self.wstds.values(), *self.ents.values())):
+                raise RuntimeError("PackCache: a stale entry inside a capture that holds the cache (run refresh() eagerly first)")
+            return
         wst = []
         for key, e in list(self.wstds.items()):
             w = e.w()
