@@ -859,6 +859,36 @@ size_t umi_augment_znorm_ws_bytes(int N);
 int umi_augment_znorm(const void* src, int dtype, float* out_nchw, const int* params, const double* geom, int N, int H, int W, int C,
                       int reverse_channels, void* ws, size_t ws_bytes, umi_stream_t stream);
 
+/* Hard-mask segmentation metrics (csrc/seg_metrics.hip; statement: umi/metrics.py): an exact integer confusion matrix per item
+ * and Dice / IoU / pixel error from it.  `items` consecutive groups of n images; target [items*n][HW] with target_dtype as
+ * umi_dice_ce_fwd (0 = int64, 1 = float32, 2 = uint8, 3 = int32).
+ *   umi_confusion_logits: fp32 logits [items*n][C][HW], 1 <= C <= 8.  C >= 2: K = C classes, prediction = umi_argmax_mask's rule
+ *     (the first strict maximum wins; a NaN never wins, so a NaN in channel 0 stays).  C == 1: K = 2, prediction =
+ *     umi_binary_mask's rule (1 where x >= -0x1.7ffffcp-23; NaN gives 0).
+ *   umi_confusion_masks: a uint8 prediction mask [items*n][HW] in place of the logits, 2 <= K <= 8 given; values >= K fall in
+ *     column K.
+ *   counts[items][K+1][K+1] (int64, 8-byte aligned): row = target class, column = predicted class.  Row K = "not a class": an
+ *     integer label outside 0..K-1, or a float32 label that is not exactly one of 0.0 .. K-1 (the reference's one-hot encoder
+ *     matches such a pixel to no class, loss.py:220-226, while its prediction still counts).  Column K is 0 from logits.
+ *     EVERY entry is written; neither counts nor ws needs presetting.  ws: umi_confusion_ws_bytes(items, n, K, HW) bytes of
+ *     uint32 partial rows, 4-byte aligned (0 for sizes out of range).  16-byte loads when HW % 4 == 0 and logits / target are
+ *     16-byte aligned (uint8: 4-byte), scalar loads otherwise.  No global atomics: integer sums, exact in any order.
+ *   umi_confusion_scores: out[item] (fp32) from counts, with I_c = counts[c][c], Z_c = column sum and Y_c = row sum over all
+ *     K+1 entries; float64 in this order without contraction, one rounding to fp32:
+ *       kind 0 (Dice error)   1 - (sum_{c = c0..K-1} (2 I_c + 1e-5) / (Z_c + Y_c + 1e-5)) / (K - c0), classes in class order; with
+ *                             c0 = 0 the reference's DiceLoss(K)(one_hot(argmax), target, softmax=False) (loss.py:228-251)
+ *       kind 1 (IoU error)    the same with (I_c + 1e-5) / (Z_c + Y_c - I_c + 1e-5)
+ *       kind 2 (pixel error)  1 - (sum_c I_c + 1e-5) / (sum_{rows < K} Y_c + 1e-5)
+ * UMI_ERR_BADARG: null pointers, items / n / HW <= 0, items > 65535, unknown target_dtype / kind, c0 outside 0..K-1, misaligned
+ * pointers.  UMI_ERR_UNSUPPORTED: C or K out of range, n * HW >= 2^31.  UMI_ERR_WORKSPACE: ws_bytes too small.  Nothing is
+ * launched then.  No allocation, no host synchronisation, one stream: all three calls can be captured. */
+size_t umi_confusion_ws_bytes(int items, int n, int K, long HW);
+int umi_confusion_logits(const float* logits, const void* target, int target_dtype, int items, int n, int C, long HW,
+                         long long* counts, void* ws, size_t ws_bytes, umi_stream_t stream);
+int umi_confusion_masks(const unsigned char* mask, const void* target, int target_dtype, int items, int n, int K, long HW,
+                        long long* counts, void* ws, size_t ws_bytes, umi_stream_t stream);
+int umi_confusion_scores(const long long* counts, int items, int K, int kind, int c0, float* out, umi_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -72,6 +72,17 @@ every replay, keyed on the parameter versions the cache tracks, so a replay afte
 current weights; BatchNorm running statistics are device tensors the captured kernels re-read.  `multi_task_trainRatio` with
 `val_batch` raises NotImplementedError at train() (its validation bookkeeping is its own); a `val_batch` that is not None or a
 positive int raises ValueError.
+The hard-mask metrics of `loss.SEG_METRICS` ('dice_err_mc', 'iou_err_mc', 'pixel_err_mc', 'dice_err', 'iou_err', 'pixel_err':
+1 - Dice / IoU / pixel accuracy of the argmax or threshold mask, lower is better) work as `accuracy_metric` in every validation
+path above -- item by item, `val_batch` groups (one counting pass over the group), replayed groups, data parallel; as
+`loss_function` they raise ValueError (not differentiable).  `Trainer(..., val_confusion=True)` (keyword-only; the single-output
+model types): the validation phase also adds every item's confusion matrix (umi/metrics.py: [K+1, K+1] int64, row = label,
+column = prediction, index K = "not a class"; K = the logits' channel count, 2 for one logit) into a static device accumulator
+-- inside the captured group function too --, reads it back once after the phase (under data parallel after an int64
+all-reduce, exact), appends it to `self.val_confusion_list` and keeps the per-class Dice / IoU of that dataset-level matrix in
+`self.val_class_scores`.  When the accuracy metric is a hard-mask one the score comes from the same matrices (one pass).
+`logs.txt`, the checkpoints and the other lists do not change; with `val_confusion=False` and another metric name none of
+this runs.
 `lr_scheduler=True` (what the reference's train.py passes) crashes the reference in its first validation after epoch 5
 (`True.step`); here train() raises NotImplementedError before the first step whenever the run would reach that point.
 The remaining epoch loops of the reference (uncertainty-weighted multi-task, CLTR, Topo losses) are out of scope and raise.
@@ -85,7 +96,7 @@ import torch
 import torch.nn.functional as F
 from tqdm import tqdm
 
-from loss import calc_loss, calc_loss_items, multi_task_ratio_loss
+from loss import SEG_METRICS, calc_loss, calc_loss_items, multi_task_ratio_loss, seg_confusion_items, seg_scores
 
 _SINGLE = ('single', 'TransUnet', 'regression', 'regression_t', 'attention')
 _TOPO = ('TopoCount', 'TopoCount2', 'TopoLoss', 'TopoLoss2', 'MyTopoLoss1', 'MyTopoLoss2', 'MyTopoLossGraph',
@@ -97,7 +108,7 @@ _OTHER = ('CLTR',)
 class Trainer():
     def __init__(self, model, model_type, dtype, device, output_save_dir, dataloaders, batch_size, optimizer,
                  patience, num_epochs, loss_function, accuracy_metric, lr_scheduler=None, start_epoch=1, *, graph=None,
-                 batch_transform=None, grad_guard=None, data_parallel=None, val_batch=None):
+                 batch_transform=None, grad_guard=None, data_parallel=None, val_batch=None, val_confusion=False):
         self.model = model
         self.model_type = model_type
         self.dtype = dtype
@@ -143,6 +154,14 @@ class Trainer():
             raise ValueError(f"val_batch takes None or a positive int, not {val_batch!r}")
         self.val_batch = val_batch
         self._eval_graphs, self._eval_seen, self._val_sums = {}, set(), None
+        # hard-mask metrics (see the module docstring): the dataset-level matrix of each validation phase, its per-class scores,
+        # and the static device accumulator the validation steps add into
+        if loss_function in SEG_METRICS:
+            raise ValueError(f"loss_function {loss_function!r} is a hard-mask metric: not differentiable, use it as accuracy_metric")
+        if val_confusion and model_type not in _SINGLE:
+            raise ValueError(f"val_confusion covers the single-output model types {_SINGLE}, not {model_type!r}")
+        self.val_confusion = bool(val_confusion)
+        self.val_confusion_list, self.val_class_scores, self._val_conf = [], None, None
 
         self.save_dir_model = os.path.join(self.output_save_dir, 'models/')
         os.makedirs(self.save_dir_model, exist_ok=True)
@@ -438,8 +457,53 @@ class Trainer():
             out, loss = self._forward_loss(inputs, labels)
             if self.model_type in _MULTI:                        # the reference reports no validation score there (:853)
                 return loss.detach(), torch.zeros((), device=loss.device)
-            score = calc_loss(out, labels, loss_type=self.accuracy_metric)
+            if self.val_confusion or self.accuracy_metric in SEG_METRICS:
+                score = self._seg_scores(out, labels, 1, loss.reshape(1))[0]
+            else:
+                score = calc_loss(out, labels, loss_type=self.accuracy_metric)
         return loss.detach(), score.detach()
+
+    # ---- hard-mask metrics ---------------------------------------------------------------
+    def _seg_scores(self, out, labels, items, loss):
+        """The [items] scores of a validation step with a hard-mask accuracy metric and / or val_confusion: ONE counting pass
+        gives the per-item matrices; they are added into the static accumulator `_val_conf` (val_confusion) and scored.  No host
+        synchronisation: part of what a GraphedEval captures.  `loss`: the [items] losses, the score when the names agree."""
+        name = self.accuracy_metric
+        seg = name in SEG_METRICS
+        counts = seg_confusion_items(out, labels, items, SEG_METRICS[name][2] if seg else None)
+        if self.val_confusion:
+            if self._val_conf is None or (self._val_conf.shape, self._val_conf.device) != (counts.shape[1:], counts.device):
+                if self._val_conf is not None and bool(self._val_conf.any()):
+                    raise ValueError(f"val_confusion: the class count changed inside a validation phase ({self._val_conf.shape[0] - 1} "
+                                     f"-> {counts.shape[1] - 1})")
+                self._val_conf = torch.zeros_like(counts[0])             # only ever in an eager step (the first of a shape)
+                self._eval_graphs, self._eval_seen = {}, set()           # (graphs hold the old accumulator's address)
+            self._val_conf.add_(counts.sum(dim=0))
+        if seg:
+            return seg_scores(counts, name)
+        return loss if name == self.loss_function else calc_loss_items(out, labels, items, loss_type=name)
+
+    def _read_confusion(self):
+        """After a validation phase: the dataset-level matrix (summed over the ranks under data parallel: int64, exact) to the
+        host, once; per-class Dice / IoU of it."""
+        from umi import metrics
+        dp = self._dp is not None and self._dp.world > 1
+        if dp:                                # a rank with an empty shard has no accumulator yet: agree on the size first
+            import torch.distributed as dist
+            size = torch.tensor([0 if self._val_conf is None else self._val_conf.shape[0]], dtype=torch.int64,
+                                device=self._dp_device())
+            dist.all_reduce(size, op=dist.ReduceOp.MAX, group=self._dp.group)
+            if self._val_conf is None and int(size):
+                self._val_conf = torch.zeros((int(size), int(size)), dtype=torch.int64, device=self._dp_device())
+        if self._val_conf is None:
+            return
+        total = self._val_conf.clone()
+        if dp:
+            dist.all_reduce(total, op=dist.ReduceOp.SUM, group=self._dp.group)
+        matrix = total.cpu().numpy()
+        self.val_confusion_list.append(matrix)
+        per_class = metrics.class_scores_numpy(matrix)
+        self.val_class_scores = {"dice": per_class["dice"], "iou": per_class["iou"]}
 
     # ---- batched validation (val_batch=k) ------------------------------------------------
     def _val_group_fn(self, items):
@@ -461,8 +525,11 @@ class Trainer():
                     if relu:
                         out = F.relu(out)
                     loss = calc_loss_items(out, ys[0], items, loss_type=self.loss_function)
-                    score = loss if self.accuracy_metric == self.loss_function else \
-                        calc_loss_items(out, ys[0], items, loss_type=self.accuracy_metric)
+                    if self.val_confusion or self.accuracy_metric in SEG_METRICS:
+                        score = self._seg_scores(out, ys[0], items, loss)
+                    else:
+                        score = loss if self.accuracy_metric == self.loss_function else \
+                            calc_loss_items(out, ys[0], items, loss_type=self.accuracy_metric)
                     t1 = t2 = torch.zeros_like(loss)
                 rows = torch.stack([v.detach() for v in (loss, score, t1, t2)], dim=1)
                 if self._val_sums is None or (self._val_sums.dtype, self._val_sums.device) != (rows.dtype, rows.device):
@@ -678,6 +745,8 @@ class Trainer():
                     since = time.time()
                 self.model.train(train)
                 self._dp_phase(train)
+                if not train and self._val_conf is not None:
+                    self._val_conf.zero_()
 
                 loss_sum, score_sum, steps = None, None, 0
                 task_sums = [0.0, 0.0]
@@ -725,6 +794,8 @@ class Trainer():
                     continue
 
                 val_score = float(score_sum) / steps
+                if self.val_confusion:
+                    self._read_confusion()
                 if multi:
                     self.val_loss_list_1.append(float(task_sums[0]) / steps)
                     self.val_loss_list_2.append(float(task_sums[1]) / steps)

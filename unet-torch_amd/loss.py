@@ -45,6 +45,15 @@ very loop over contiguous slices, so every name behaves as in `calc_loss`; 'dice
 `umi_dice_ce_fwd_items` pass whose stats rows are bit for bit those of `umi_dice_ce_fwd` on the slices (values only, no backward).
 It raises under an active global-batch switch.
 
+The hard-mask metrics 'dice_err_mc', 'iou_err_mc', 'pixel_err_mc' (logits with C >= 2 channels, the argmax mask, all classes),
+'dice_err', 'iou_err' (one logit, the fp32 sigmoid >= 0.5 mask, the foreground class alone) and 'pixel_err' (one logit, both
+classes) are values for `accuracy_metric`, not losses: 1 - Dice / 1 - IoU / 1 - pixel accuracy of the hard mask from an exact
+integer confusion matrix (umi/metrics.py states the rule), lower is better, returned without a graph.  Contiguous fp32 device
+logits with contiguous device labels run two HIP kernels and a scoring kernel (csrc/seg_metrics.hip; `calc_loss_items` counts all
+items in one pass), everything else a torch.bincount composite with the same integers and the same float64 formula.
+`METRICS_KERNEL = False` sends every input to the composite (the A/B switch of tools/bench_seg_metrics.py).  Under a
+global-batch switch they stay per replica, like the pointwise losses.
+
 The remaining names raise NotImplementedError: 'dice', 'dice_score', 'dice_score_mc' and 'log_cosh_dice_loss' call
 DiceLoss() without n_classes, 'FL' names an undefined BinaryFocalLoss, HausdorffERLoss has no gradient and
 ActiveContourLoss hard-codes 512x512 tensors on cuda:0 in the reference itself.
@@ -559,6 +568,47 @@ def MRAccuracy(pred, target):
     return mre
 
 
+# ---------------------------------------------------------------------------------------------------------------------
+# hard-mask metrics (umi/metrics.py, csrc/seg_metrics.hip)
+
+# name -> (kind of umi.metrics.scores, first class c0, multi-class)
+SEG_METRICS = {'dice_err_mc': (0, 0, True), 'iou_err_mc': (1, 0, True), 'pixel_err_mc': (2, 0, True),
+               'dice_err': (0, 1, False), 'iou_err': (1, 1, False), 'pixel_err': (2, 0, False)}
+
+# False: the hard-mask metrics run the torch composite on every input (the A/B switch of tools/bench_seg_metrics.py)
+METRICS_KERNEL = True
+
+
+def seg_confusion_items(pred, target, items=1, multiclass=None):
+    """The confusion matrices [items, K+1, K+1] (int64, where pred lives) of `items` consecutive groups of logits: the argmax
+    mask of C >= 2 channels (`multiclass`; K = C) or the threshold mask of one logit (K = 2; labels (B, H, W) or (B, 1, H, W)).
+    `multiclass` None: by the channel count.  One pass of the items-native kernel on its inputs, else the composite."""
+    from umi import metrics
+    if pred.dim() < 3:
+        raise ValueError(f"hard-mask metrics take logits (B, C, ...), got {tuple(pred.shape)}")
+    if multiclass is None:
+        multiclass = pred.shape[1] != 1
+    if multiclass and pred.shape[1] < 2:
+        raise ValueError(f"the multi-class metrics ('*_mc') take logits with C >= 2 channels, got {tuple(pred.shape)}")
+    if not multiclass and pred.shape[1] != 1:
+        raise ValueError(f"the binary metrics take one-logit maps (B, 1, ...), got {tuple(pred.shape)}; use the '*_mc' names")
+    pred = pred.detach()
+    if METRICS_KERNEL and metrics.kernel_ok(pred, target, items):
+        return metrics.confusion(pred, target, items)
+    return metrics.confusion_composite(pred, target, items)
+
+
+def seg_scores(counts, loss_type):
+    """[items] fp32 values of a hard-mask metric name from its confusion matrices."""
+    from umi import metrics
+    kind, c0, _ = SEG_METRICS[loss_type]
+    return (metrics.scores if METRICS_KERNEL else metrics.scores_composite)(counts, kind, c0)
+
+
+def _seg_metric_items(pred, target, items, loss_type):
+    return seg_scores(seg_confusion_items(pred, target, items, SEG_METRICS[loss_type][2]), loss_type)
+
+
 def calc_loss(pred, target, bce_weight=0.5, loss_type='mse'):
     sync = _batch_sync()              # umi.ddp.GradReducer(global_batch=True): losses are those of the group's whole batch
     if sync is not None and loss_type in _BATCH_COUPLED:
@@ -596,6 +646,8 @@ def calc_loss(pred, target, bce_weight=0.5, loss_type='mse'):
         return topk_loss(pred, target)
     if loss_type == 'BCE_HEM':
         return bce_hem_loss(pred, target)
+    if loss_type in SEG_METRICS:
+        return _seg_metric_items(pred, target, 1, loss_type)[0]
     if loss_type in _OUT_OF_SCOPE:
         raise NotImplementedError(f"loss_type {loss_type!r} is outside the MI355X hot-path scope")
     raise ValueError(f"unknown loss_type {loss_type!r}")
@@ -622,7 +674,7 @@ def calc_loss_items(pred, target, items, loss_type='mse'):
     """The losses of `items` consecutive groups of n images each: pred [items*n, C, H, W] and target [items*n, ...] ->
     a [items] tensor whose element i is calc_loss(pred[i*n:(i+1)*n], target[i*n:(i+1)*n], loss_type=loss_type).  By default
     literally that loop over contiguous slices, so every loss name behaves as in calc_loss (the names that raise included);
-    'dice_bce_mc' on inputs of the fused kernels takes one pass for all items (same bits).  Values only: made for the
+    'dice_bce_mc' on inputs of the fused kernels and the hard-mask metrics take one pass for all items (same bits).  Values only: made for the
     validation phase (Trainer(val_batch=k)), where nothing is differentiated.  Raises under an active global-batch switch
     (umi.ddp), where a loss is that of the data-parallel group's whole batch and a per-item value has no meaning."""
     items = int(items)
@@ -635,6 +687,8 @@ def calc_loss_items(pred, target, items, loss_type='mse'):
     if (loss_type == 'dice_bce_mc' and ITEMS_KERNEL and items <= 65535 and not (torch.is_grad_enabled() and pred.requires_grad)
             and _fused_ok(pred, target)):
         return _dice_ce_items(pred, target, items)
+    if loss_type in SEG_METRICS and METRICS_KERNEL:      # one counting pass over all items (the composite when not eligible)
+        return _seg_metric_items(pred, target, items, loss_type)
     vals = [calc_loss(pred[i * n:(i + 1) * n], target[i * n:(i + 1) * n], loss_type=loss_type) for i in range(items)]
     return torch.stack([v if torch.is_tensor(v) else torch.as_tensor(v) for v in vals])
 
