@@ -889,6 +889,31 @@ int umi_confusion_masks(const unsigned char* mask, const void* target, int targe
                         long long* counts, void* ws, size_t ws_bytes, umi_stream_t stream);
 int umi_confusion_scores(const long long* counts, int items, int K, int kind, int c0, float* out, umi_stream_t stream);
 
+/* Surface-distance metrics of hard masks (csrc/surface_metrics.hip; statement: umi/surface.py), unit pixel spacing, 2-D.
+ * Per image b and class c in c0..K-1: A = (pred_mask == c), G = (target is class c; target_dtype and the label rule as
+ * umi_confusion_masks).  Surface of a mask = its pixels on the image edge or with a 4-neighbour outside the mask.  Every surface
+ * pixel of one side gets the exact integer squared distance to the nearest surface pixel of the other side; S = the roots
+ * (float64) of both directions, n of them.
+ *   umi_surface_distances: pred_mask uint8 [B][H][W], target [B][H][W].  stats[B][K][4] (float64) = hd = max(S); hd95 =
+ *     np.percentile(S, 95) (v = (n-1) * 0.95, lo = floor(v), t = v - lo, a = S[lo], b = S[min(lo+1, n-1)], a + (b-a) t if t < 0.5 else
+ *     b - (b-a)(1-t), no contraction); assd = (mean of A->G + mean of G->A) / 2, each sum in a fixed order; state = 0 both sides
+ *     non-empty, 1 both empty, 2 prediction empty only, 3 label empty only (hd, hd95, assd are 0 unless state is 0).
+ *     counts[B][K][2] (int64) = surface pixels of A, of G.  Classes below c0 get zeros.  EVERY entry is written; neither the
+ *     outputs nor ws needs presetting, and two runs agree bit for bit.  ws: umi_surface_ws_bytes(B, K, c0, H, W) bytes, 8-byte aligned
+ *     (0 for sizes out of range): 12 bytes per pixel and 64 KiB per (image, class) for the B * (K - c0) scored pairs.
+ *   umi_surface_scores: out[item] (fp32) = the float64 mean over the item's n images and the classes c0..K-1, in (image, class)
+ *     order, of stats[..][kind] (kind 0 hd, 1 hd95, 2 assd) in state 0, of 0.0 in state 1, and in states 2 and 3 of
+ *     sqrt((H-1)^2 + (W-1)^2) (empty_rule 0), 0.0 (1) or NaN (2); one rounding to fp32.  stats [items*n][K][4].
+ * UMI_ERR_BADARG: null or misaligned pointers, B / items / n / H / W <= 0, unknown target_dtype / kind / empty_rule, c0 outside
+ * 0..K-1.  UMI_ERR_UNSUPPORTED: H or W > 4096, K outside 2..8, B * K * H * W >= 2^31, B * K > 65535.  UMI_ERR_WORKSPACE: ws_bytes
+ * too small.  Nothing is launched then.  Four launches and one, no allocation, no host synchronisation, one stream, integer
+ * atomics only: both calls can be captured. */
+size_t umi_surface_ws_bytes(int B, int K, int c0, int H, int W);
+int umi_surface_distances(const unsigned char* pred_mask, const void* target, int target_dtype, int B, int K, int c0, int H, int W,
+                          double* stats, long long* counts, void* ws, size_t ws_bytes, umi_stream_t stream);
+int umi_surface_scores(const double* stats, int items, int n, int K, int c0, int kind, int empty_rule, int H, int W, float* out,
+                       umi_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -83,6 +83,16 @@ all-reduce, exact), appends it to `self.val_confusion_list` and keeps the per-cl
 `self.val_class_scores`.  When the accuracy metric is a hard-mask one the score comes from the same matrices (one pass).
 `logs.txt`, the checkpoints and the other lists do not change; with `val_confusion=False` and another metric name none of
 this runs.
+The surface-distance metrics of `loss.SURFACE_METRICS` ('hd_mc', 'hd95_mc', 'assd_mc', 'hd', 'hd95', 'assd': Hausdorff distance,
+its 95th percentile and the average symmetric surface distance of the argmax or threshold mask's foreground classes, in pixels,
+lower is better; umi/surface.py) work as `accuracy_metric` in the same validation paths through `calc_loss` / `calc_loss_items`
+(one kernel call per group).  The kernels take contiguous fp32 device logits with at most 8 channels and H, W <= 4096; on those
+nothing allocates outside the caching allocator or synchronises, so a full group replays from its GraphedEval like any other.
+Every other input (a 9-class model, `loss.METRICS_KERNEL = False`, ...) runs the NumPy statement on host copies, which
+synchronises: a group whose first, eager run took that route is never captured and stays eager under `graph=True`
+(`_eval_host`, decided by `loss.surface_host_calls()`), with the same scores, at the host's speed.  As `loss_function` they raise
+ValueError.  With `val_confusion=True` the
+confusion matrices take their own pass next to it.
 `lr_scheduler=True` (what the reference's train.py passes) crashes the reference in its first validation after epoch 5
 (`True.step`); here train() raises NotImplementedError before the first step whenever the run would reach that point.
 The remaining epoch loops of the reference (uncertainty-weighted multi-task, CLTR, Topo losses) are out of scope and raise.
@@ -96,7 +106,8 @@ import torch
 import torch.nn.functional as F
 from tqdm import tqdm
 
-from loss import SEG_METRICS, calc_loss, calc_loss_items, multi_task_ratio_loss, seg_confusion_items, seg_scores
+import loss as _loss
+from loss import SEG_METRICS, SURFACE_METRICS, calc_loss, calc_loss_items, multi_task_ratio_loss, seg_confusion_items, seg_scores
 
 _SINGLE = ('single', 'TransUnet', 'regression', 'regression_t', 'attention')
 _TOPO = ('TopoCount', 'TopoCount2', 'TopoLoss', 'TopoLoss2', 'MyTopoLoss1', 'MyTopoLoss2', 'MyTopoLossGraph',
@@ -154,10 +165,14 @@ class Trainer():
             raise ValueError(f"val_batch takes None or a positive int, not {val_batch!r}")
         self.val_batch = val_batch
         self._eval_graphs, self._eval_seen, self._val_sums = {}, set(), None
+        self._eval_host = set()       # group shapes whose eager run copied to the host (surface metrics' composite): never captured
         # hard-mask metrics (see the module docstring): the dataset-level matrix of each validation phase, its per-class scores,
         # and the static device accumulator the validation steps add into
         if loss_function in SEG_METRICS:
             raise ValueError(f"loss_function {loss_function!r} is a hard-mask metric: not differentiable, use it as accuracy_metric")
+        if loss_function in SURFACE_METRICS:
+            raise ValueError(f"loss_function {loss_function!r} is a surface-distance metric: not differentiable, use it as "
+                             "accuracy_metric")
         if val_confusion and model_type not in _SINGLE:
             raise ValueError(f"val_confusion covers the single-output model types {_SINGLE}, not {model_type!r}")
         self.val_confusion = bool(val_confusion)
@@ -554,16 +569,32 @@ class Trainer():
         if self.graph and x.is_cuda and items == self.val_batch:
             key = tuple(tuple(t.shape) for t in flat)
             ge = self._eval_graphs.get(key)
-            if ge is None and key in self._eval_seen:            # 2nd full group of a shape: capture (nothing executes), replay
+            if ge is None and self._eval_capture_ok(key):        # 2nd full group of a shape: capture (nothing executes), replay
                 from umi.graph import pack_cache_of
                 from umi.graphs import GraphedEval
                 ge = self._eval_graphs[key] = GraphedEval(self._val_group_fn(items), flat, pack_cache=pack_cache_of(self.model))
             if ge is not None:
                 ge(*flat)
                 return
+        host = _loss.surface_host_calls()
         self._val_group_fn(items)(*flat)                         # 1st full group of a shape (allocations, pack entries), short
         if key is not None:                                      # groups, graph=False, CPU models: eager
+            self._eval_note_eager(key, host)
+
+    def _eval_note_eager(self, key, host_calls_before):
+        """After the eager run of a full group of shapes `key`: seen once, or -- when a surface metric copied to the host in it
+        (loss.surface_host_calls() moved) -- never to be captured."""
+        if _loss.surface_host_calls() != host_calls_before:
+            self._eval_host.add(key)
+        else:
             self._eval_seen.add(key)
+
+    def _eval_capture_ok(self, key):
+        """Whether the next full group of shapes `key` may be captured: it ran eagerly once, without a host copy, and a surface
+        metric would still take the kernels."""
+        if key in self._eval_host or key not in self._eval_seen:
+            return False
+        return not (self.accuracy_metric in SURFACE_METRICS and not _loss.METRICS_KERNEL)
 
     def _validate_batched(self, bar, epoch, use_cuda, total_mem):
         """The validation phase under val_batch=k: loader items gathered into groups of up to k consecutive items of equal

@@ -54,10 +54,27 @@ items in one pass), everything else a torch.bincount composite with the same int
 `METRICS_KERNEL = False` sends every input to the composite (the A/B switch of tools/bench_seg_metrics.py).  Under a
 global-batch switch they stay per replica, like the pointwise losses.
 
+The surface-distance metrics 'hd_mc', 'hd95_mc', 'assd_mc' (logits with C >= 2 channels, the argmax mask, K = C) and 'hd',
+'hd95', 'assd' (one logit, the fp32 sigmoid >= 0.5 mask, K = 2) are values for `accuracy_metric` too: the Hausdorff distance, its
+95th percentile and the average symmetric surface distance between the boundaries of the predicted and the true mask, in pixels,
+per image and FOREGROUND class (c0 = 1, as TransUNet's evaluation averages them), averaged over the item's images and classes
+(umi/surface.py states the rule; it is medpy's / scipy's for unit spacing).  Lower is better; returned without a graph, fp32.
+Logits must be 4-D; binary labels may be (B, H, W) or (B, 1, H, W).  An (image, class) with one empty mask scores by the
+module-level `SURFACE_EMPTY`: 'diagonal' (default: the image diagonal, so an empty prediction is never the best model), 'zero'
+(TransUNet's script) or 'nan'.  Contiguous fp32 device logits with contiguous device labels run `umi_argmax_mask` /
+`umi_binary_mask` and the HIP kernels of csrc/surface_metrics.hip (one call for all items of `calc_loss_items`, capturable);
+everything else -- logits with MORE THAN 8 CHANNELS (the 9-class Synapse TransUNet among them), other dtypes, non-contiguous tensors,
+H or W > 4096, and every input under `METRICS_KERNEL = False` -- runs the NumPy statement on host copies: about 65 ms per 512 x 512
+image and class instead of microseconds, synchronising and therefore not capturable; on device logits it warns once
+(RuntimeWarning), `surface_host_calls()` counts it, and the Trainer keeps such validation groups eager.
+Under a global-batch switch they stay per replica.
+
 The remaining names raise NotImplementedError: 'dice', 'dice_score', 'dice_score_mc' and 'log_cosh_dice_loss' call
 DiceLoss() without n_classes, 'FL' names an undefined BinaryFocalLoss, HausdorffERLoss has no gradient and
 ActiveContourLoss hard-codes 512x512 tensors on cuda:0 in the reference itself.
 """
+import warnings
+
 import numpy as np
 import torch
 import torch.nn as nn
@@ -609,6 +626,71 @@ def _seg_metric_items(pred, target, items, loss_type):
     return seg_scores(seg_confusion_items(pred, target, items, SEG_METRICS[loss_type][2]), loss_type)
 
 
+# ---------------------------------------------------------------------------------------------------------------------
+# surface-distance metrics (umi/surface.py, csrc/surface_metrics.hip)
+
+# name -> (kind of umi.surface.surface_scores, multi-class); all of them score the foreground classes c0 = 1 .. K-1
+SURFACE_METRICS = {'hd_mc': (0, True), 'hd95_mc': (1, True), 'assd_mc': (2, True),
+                   'hd': (0, False), 'hd95': (1, False), 'assd': (2, False)}
+
+# what an (image, class) with exactly one empty mask scores: 'diagonal' (sqrt((H-1)^2 + (W-1)^2)), 'zero' or 'nan'
+SURFACE_EMPTY = 'diagonal'
+
+
+def surface_stats_items(pred, target, multiclass=None):
+    """(stats [B, K, 4] float64, counts [B, K, 2] int64, where pred lives) of 4-D logits against labels: the surface distances of the
+    argmax mask of C >= 2 channels (`multiclass`; K = C) or of the threshold mask of one logit (K = 2; labels (B, H, W) or
+    (B, 1, H, W)), foreground classes.  `multiclass` None: by the channel count.  The mask and distance kernels on their inputs,
+    else the host composite."""
+    from umi import metrics, surface
+    if pred.dim() != 4:
+        raise ValueError(f"surface-distance metrics take logits (B, C, H, W), got {tuple(pred.shape)}")
+    if multiclass is None:
+        multiclass = pred.shape[1] != 1
+    if multiclass and pred.shape[1] < 2:
+        raise ValueError(f"the multi-class metrics ('*_mc') take logits with C >= 2 channels, got {tuple(pred.shape)}")
+    if not multiclass and pred.shape[1] != 1:
+        raise ValueError(f"the binary metrics take one-logit maps (B, 1, ...), got {tuple(pred.shape)}; use the '*_mc' names")
+    pred = pred.detach()
+    K = pred.shape[1] if multiclass else 2
+    if target.dim() == 4 and target.shape[1] == 1:
+        target = target[:, 0]
+    if tuple(target.shape) != (pred.shape[0],) + tuple(pred.shape[2:]):
+        raise ValueError(f"logits {tuple(pred.shape)} and labels {tuple(target.shape)} do not match")
+    if (METRICS_KERNEL and pred.is_cuda and pred.dtype == torch.float32 and pred.is_contiguous() and K <= 8 and pred.numel()
+            and target.is_cuda and target.device == pred.device and target.is_contiguous() and target.dtype in _TARGET_DTYPES):
+        from umi import infer
+        mask = infer.argmax_mask(pred) if multiclass else infer.binary_mask(pred)
+        if surface.surface_kernel_ok(mask, target, K):
+            return surface.surface(mask, target, K, 1)
+    else:
+        mask = metrics.predict_composite(pred)[0].to(torch.uint8)
+    _SURFACE_HOST_CALLS[0] += 1
+    if pred.is_cuda and METRICS_KERNEL:
+        warnings.warn(f"surface-distance metric on device logits {tuple(pred.shape)} {pred.dtype} with labels {target.dtype} runs the "
+                      "NumPy statement on host copies (the kernels take contiguous fp32 logits with at most 8 channels, contiguous "
+                      "int64 / float32 / uint8 / int32 labels and H, W <= 4096): thousands of times slower, and not capturable",
+                      RuntimeWarning, stacklevel=3)
+    return surface.surface_composite(mask, target, K, 1)
+
+
+_SURFACE_HOST_CALLS = [0]
+
+
+def surface_host_calls():
+    """How often a surface-distance metric has taken the host composite so far.  A caller that wants to capture a step compares
+    the figure before and after an eager run of it: the composite copies to the host, which a graph capture forbids."""
+    return _SURFACE_HOST_CALLS[0]
+
+
+def _surface_metric_items(pred, target, items, loss_type):
+    from umi import surface
+    kind, multiclass = SURFACE_METRICS[loss_type]
+    stats, _ = surface_stats_items(pred, target, multiclass)
+    score = surface.surface_scores if METRICS_KERNEL else surface.surface_scores_composite
+    return score(stats, items, kind, 1, SURFACE_EMPTY, tuple(pred.shape[2:]))
+
+
 def calc_loss(pred, target, bce_weight=0.5, loss_type='mse'):
     sync = _batch_sync()              # umi.ddp.GradReducer(global_batch=True): losses are those of the group's whole batch
     if sync is not None and loss_type in _BATCH_COUPLED:
@@ -648,6 +730,8 @@ def calc_loss(pred, target, bce_weight=0.5, loss_type='mse'):
         return bce_hem_loss(pred, target)
     if loss_type in SEG_METRICS:
         return _seg_metric_items(pred, target, 1, loss_type)[0]
+    if loss_type in SURFACE_METRICS:
+        return _surface_metric_items(pred, target, 1, loss_type)[0]
     if loss_type in _OUT_OF_SCOPE:
         raise NotImplementedError(f"loss_type {loss_type!r} is outside the MI355X hot-path scope")
     raise ValueError(f"unknown loss_type {loss_type!r}")
@@ -674,7 +758,8 @@ def calc_loss_items(pred, target, items, loss_type='mse'):
     """The losses of `items` consecutive groups of n images each: pred [items*n, C, H, W] and target [items*n, ...] ->
     a [items] tensor whose element i is calc_loss(pred[i*n:(i+1)*n], target[i*n:(i+1)*n], loss_type=loss_type).  By default
     literally that loop over contiguous slices, so every loss name behaves as in calc_loss (the names that raise included);
-    'dice_bce_mc' on inputs of the fused kernels and the hard-mask metrics take one pass for all items (same bits).  Values only: made for the
+    'dice_bce_mc' on inputs of the fused kernels, the hard-mask metrics and the surface-distance metrics take one pass for all items
+    (same bits).  Values only: made for the
     validation phase (Trainer(val_batch=k)), where nothing is differentiated.  Raises under an active global-batch switch
     (umi.ddp), where a loss is that of the data-parallel group's whole batch and a per-item value has no meaning."""
     items = int(items)
@@ -689,6 +774,8 @@ def calc_loss_items(pred, target, items, loss_type='mse'):
         return _dice_ce_items(pred, target, items)
     if loss_type in SEG_METRICS and METRICS_KERNEL:      # one counting pass over all items (the composite when not eligible)
         return _seg_metric_items(pred, target, items, loss_type)
+    if loss_type in SURFACE_METRICS:                     # one call for all items (the host composite when not eligible)
+        return _surface_metric_items(pred, target, items, loss_type)
     vals = [calc_loss(pred[i * n:(i + 1) * n], target[i * n:(i + 1) * n], loss_type=loss_type) for i in range(items)]
     return torch.stack([v if torch.is_tensor(v) else torch.as_tensor(v) for v in vals])
 
