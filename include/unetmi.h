@@ -914,6 +914,33 @@ int umi_surface_distances(const unsigned char* pred_mask, const void* target, in
 int umi_surface_scores(const double* stats, int items, int n, int K, int c0, int kind, int empty_rule, int H, int W, float* out,
                        umi_stream_t stream);
 
+/* Overlap-tile / sliding-window inference over an image larger than the network input (csrc/tiles.hip; statement and the host
+ * plan: umi/tiles.py).  A plan is a grid of ny x nx equal th x tw tiles, tile id = iy * nx + ix, with origins oy[ny], ox[nx] in
+ * image coordinates (negative, or past H - th: the tile hangs over the edge), fp32 windows wy[th], wx[tw] (finite, >= 0) and their
+ * sums over the tiles sy[H], sx[W] (> 0).  A chunk is n slots of tile ids; a slot with id < 0 (or >= ny * nx) is empty.  oy, ox, wy,
+ * wx, sy, sx and ids are DEVICE arrays, read by the kernels: a captured call replays with other ids copied into the same buffer.
+ *   umi_tile_gather: x fp32 [C][H][W] -> tiles fp32 [n][C][th][tw], tile pixel (i, j) = x[c][r(oy + i)][r(ox + j)].  pad_mode 0
+ *     (reflect): r(i) over an axis of m: 0 for m == 1, else p = 2 (m - 1), q = i mod p (non-negative), q if q < m else p - q
+ *     (numpy.pad mode='reflect' for every pad width).  pad_mode 1: pad_value where the sample lies outside the image.  An empty slot
+ *     is written as zeros: every element of `tiles` is written.
+ *   umi_tile_blend: logits fp32 [n][K][th][tw]; for every canvas pixel p and the chunk's slots in order, for a tile that contains p
+ *     at (i, j) with w = fp32(wy[i] * wx[j]) > 0: acc[k][p] = fp32(acc[k][p] + fp32(w * logit)), two roundings, no fused
+ *     multiply-add.  A tile with w == 0 at p is skipped, so a non-finite logit there does not reach the canvas.  No atomics: one
+ *     thread owns a pixel per launch; calls on one stream with the ids ascending give every pixel its tiles in ascending order
+ *     whatever the chunk size.  acc fp32 [K][H][W], zeroed by the caller before the first chunk.
+ *   umi_tile_finish: acc[k][y][x] = fp32(acc[k][y][x] / fp32(sy[y] * sx[x])) in place; mask (uint8 [H][W], or NULL) = for K == 1
+ *     umi_binary_mask's rule on the quotient (1 where >= -0x1.7ffffcp-23, NaN gives 0), for K >= 2 umi_argmax_mask's (first
+ *     maximum wins).
+ * UMI_ERR_BADARG: null pointers (but `mask`), non-positive sizes, unknown pad_mode, pointers not 4-byte aligned.
+ * UMI_ERR_UNSUPPORTED: th or tw > 4096, ny or nx > 1024, n > 64, K * H * W or n * max(C, K) * th * tw >= 2^31 (each call checks
+ * its own tensors), n * C or n * K > 65535, K > 256 in umi_tile_finish.  Nothing is launched then.  One launch each, no allocation,
+ * no host synchronisation: all three can be captured. */
+int umi_tile_gather(const float* x, int C, int H, int W, float* tiles, int th, int tw, const int* oy, const int* ox, int ny, int nx,
+                    const int* ids, int n, int pad_mode, float pad_value, umi_stream_t stream);
+int umi_tile_blend(const float* logits, int K, int th, int tw, float* acc, int H, int W, const int* oy, const int* ox, int ny, int nx,
+                   const float* wy, const float* wx, const int* ids, int n, umi_stream_t stream);
+int umi_tile_finish(float* acc, int K, int H, int W, const float* sy, const float* sx, unsigned char* mask, umi_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -16,6 +16,12 @@ Binary (one-logit) models, the reference's test.py:391-455 and loss.py:422-440:
 
     scores = infer.score_binary_masks(mask, gt_dots, [5, 20], np.arange(0.5, 1, 0.05))   # localisation metrics per image
 
+Images larger than the network input, any model (umi/tiles.py: overlap-tile or windowed sliding average, stitched on the device):
+
+    plan = tiles.TilePlan.overlap_tile(H, W, 512, halo=64)
+    logits = infer.predict_logits_tiled(model, x, plan, batch=8)   # fp32 (K,H,W); predict_mask_tiled: the uint8 (H,W) mask
+    predict = infer.TiledPredictor(model, plan, channels)          # the chunk replayed from a HIP graph
+
 Multi-class models, the rest of test_mc3serousv5.py (Results2Class / Results3Class) after predict_mask:
 
     labels, counts, class_counts, label_class, area, sum_y, sum_x = infer.label_class_components(mask, n_classes)
@@ -333,6 +339,174 @@ def predict_binary_mask_tiled(model, x, crop_size):
         return tuple(pred) if isinstance(out, tuple) else pred[0]
     finally:
         model.train(was_training)
+
+
+# ---- overlap-tile / sliding-window inference over an image larger than the network input (umi/tiles.py, csrc/tiles.hip) -------------
+def tile_gather(x, plan, ids, out=None):
+    """x fp32 (C,H,W) on the device, ids int32 (n,) DEVICE tile ids (< 0: empty slot) -> fp32 (n,C,th,tw): tiles.gather_numpy."""
+    from .tiles import PAD_MODES
+    ops._need_cuda(x, ids)
+    if x.dim() != 3 or x.dtype != torch.float32 or tuple(x.shape[1:]) != (plan.H, plan.W) or not x.is_contiguous():
+        raise ValueError(f"tile_gather expects a contiguous fp32 (C,{plan.H},{plan.W}) image, got {tuple(x.shape)} {x.dtype}")
+    if ids.dim() != 1 or ids.dtype != torch.int32 or not ids.is_contiguous() or ids.numel() < 1:
+        raise ValueError(f"tile_gather expects contiguous int32 (n,) ids, got {tuple(ids.shape)} {ids.dtype}")
+    C, n = x.shape[0], ids.numel()
+    if out is None:
+        out = torch.empty((n, C, plan.th, plan.tw), dtype=torch.float32, device=x.device)
+    elif tuple(out.shape) != (n, C, plan.th, plan.tw) or out.dtype != torch.float32 or not out.is_cuda or not out.is_contiguous():
+        raise ValueError(f"tile_gather: `out` must be a contiguous fp32 device tensor ({n},{C},{plan.th},{plan.tw}), got "
+                         f"{tuple(out.shape)} {out.dtype}")
+    oy, ox = plan.device_tables(x.device)[:2]
+    L.call("umi_tile_gather", x.data_ptr(), C, plan.H, plan.W, out.data_ptr(), plan.th, plan.tw, oy.data_ptr(), ox.data_ptr(),
+           plan.ny, plan.nx, ids.data_ptr(), n, PAD_MODES[plan.pad], plan.pad_value, ops._stream())
+    return out
+
+
+def tile_blend(acc, logits, plan, ids):
+    """acc fp32 (K,H,W) += the chunk's windowed logits fp32 (n,K,th,tw), in place: tiles.blend_numpy, bit for bit."""
+    ops._need_cuda(acc, logits, ids)
+    n = ids.numel()
+    if logits.dtype != torch.float32 or logits.dim() != 4 or tuple(logits.shape[2:]) != (plan.th, plan.tw) or logits.shape[0] != n:
+        raise ValueError(f"tile_blend expects fp32 logits ({n},K,{plan.th},{plan.tw}), got {tuple(logits.shape)} {logits.dtype}")
+    K = logits.shape[1]
+    if acc.dtype != torch.float32 or tuple(acc.shape) != (K, plan.H, plan.W) or not acc.is_contiguous():
+        raise ValueError(f"tile_blend expects a contiguous fp32 canvas ({K},{plan.H},{plan.W}), got {tuple(acc.shape)} {acc.dtype}")
+    if ids.dtype != torch.int32 or ids.dim() != 1 or not ids.is_contiguous():
+        raise ValueError(f"tile_blend expects contiguous int32 (n,) ids, got {tuple(ids.shape)} {ids.dtype}")
+    logits = logits.contiguous()
+    oy, ox, wy, wx = plan.device_tables(acc.device)[:4]
+    L.call("umi_tile_blend", logits.data_ptr(), K, plan.th, plan.tw, acc.data_ptr(), plan.H, plan.W, oy.data_ptr(), ox.data_ptr(),
+           plan.ny, plan.nx, wy.data_ptr(), wx.data_ptr(), ids.data_ptr(), n, ops._stream())
+    return acc
+
+
+def tile_finish(acc, plan, mask=False):
+    """The canvas of window-weighted sums -> stitched logits, in place (tiles.finish_numpy); mask=True also returns the uint8 (H,W)
+    mask of the stitched logits: binary_mask's rule for one logit, argmax_mask's otherwise."""
+    ops._need_cuda(acc)
+    if acc.dtype != torch.float32 or acc.dim() != 3 or tuple(acc.shape[1:]) != (plan.H, plan.W) or not acc.is_contiguous():
+        raise ValueError(f"tile_finish expects a contiguous fp32 canvas (K,{plan.H},{plan.W}), got {tuple(acc.shape)} {acc.dtype}")
+    sy, sx = plan.device_tables(acc.device)[4:]
+    m = torch.empty((plan.H, plan.W), dtype=torch.uint8, device=acc.device) if mask else None
+    L.call("umi_tile_finish", acc.data_ptr(), acc.shape[0], plan.H, plan.W, sy.data_ptr(), sx.data_ptr(),
+           m.data_ptr() if mask else None, ops._stream())
+    return (acc, m) if mask else acc
+
+
+def _tiled_image(x, plan):
+    if x.dim() != 4 or x.shape[0] != 1 or tuple(x.shape[2:]) != (plan.H, plan.W):
+        raise ValueError(f"expected x (1,C,{plan.H},{plan.W}) for this plan, got {tuple(x.shape)}")
+    if x.dtype != torch.float32:
+        raise ValueError(f"expected an fp32 image, got {x.dtype}")
+    return x.to("cuda")[0].contiguous()
+
+
+def _chunk_ids(plan, batch, device):
+    return torch.from_numpy(plan.chunks(batch)).to(device)
+
+
+def _tiled_chunk(model, x3, plan, ids, canvases, tiles=None):
+    """One chunk: gather -> eval forward -> blend into `canvases` (a list filled with zeroed canvases on the first chunk).
+    Returns whether the model is two-headed."""
+    out = model(tile_gather(x3, plan, ids, tiles))
+    outs = out if isinstance(out, tuple) else (out,)
+    if not canvases:
+        canvases.extend(torch.zeros((o.shape[1], plan.H, plan.W), dtype=torch.float32, device=x3.device) for o in outs)
+    for acc, o in zip(canvases, outs):
+        tile_blend(acc, o, plan, ids)
+    return isinstance(out, tuple)
+
+
+@torch.no_grad()
+def _predict_tiled(model, x, plan, batch, mask):
+    x3 = _tiled_image(x, plan)
+    ids = _chunk_ids(plan, batch, x3.device)
+    was_training = model.training
+    model.eval()
+    try:
+        canvases, two = [], False
+        for c in range(ids.shape[0]):
+            two = _tiled_chunk(model, x3, plan, ids[c], canvases)
+        res = tuple(tile_finish(acc, plan, mask) for acc in canvases)
+        if mask:
+            res = tuple(m for _, m in res)
+        return res if two else res[0]
+    finally:
+        model.train(was_training)
+
+
+def predict_logits_tiled(model, x, plan, batch=8):
+    """Whole-image logits of a model whose input is one tile of `plan` (umi.tiles.TilePlan over x's H x W): x (1,C,H,W) fp32 ->
+    fp32 (K,H,W) stitched logits on the device, a tuple of them for a two-headed model.  Eval-mode forwards over chunks of `batch`
+    tiles in ascending id order (the last chunk padded with empty slots, which go through the network as zero tiles and are not
+    blended): umi_tile_gather -> model -> umi_tile_blend per chunk, then umi_tile_finish; nothing returns to the host.  The
+    stitching is umi.tiles' NumPy statement bit for bit and does not depend on `batch`; the model's training flag is restored."""
+    return _predict_tiled(model, x, plan, batch, False)
+
+
+def predict_mask_tiled(model, x, plan, batch=8):
+    """predict_logits_tiled, returning the uint8 (H,W) mask of the stitched logits instead (a tuple for a two-headed model): the
+    threshold of binary_mask for a one-logit model, argmax_mask's first maximum otherwise, written by the finish kernel.  With
+    TilePlan.overlap_tile(H, W, crop_size, 0) on a padded image this is predict_binary_mask_tiled with `batch` tiles per forward."""
+    return _predict_tiled(model, x, plan, batch, True)
+
+
+class TiledPredictor:
+    """predict_logits_tiled / predict_mask_tiled with the chunk replayed from a HIP graph:
+
+        predict = infer.TiledPredictor(model, plan, channels, batch=8)
+        logits = predict(x)                       # fp32 (K,H,W), or a tuple for a two-headed model
+        mask = predict.predict_mask(x)            # uint8 (H,W)
+
+    The constructor runs one chunk eagerly and captures it (gather -> eval forward -> blend into static canvases) in a
+    umi.graphs.GraphedEval holding the model's weight-pack cache.  A call copies the image into the static input once, zeroes the
+    canvases, replays the graph once per chunk with that chunk's ids copied into the static id buffer, runs the finish kernel behind
+    the last replay and returns CLONES.  A replay after an optimizer step or load_state_dict reads the current weights, as
+    GraphedPredictor does.  The model's training flag is left as it was."""
+
+    def __init__(self, model, plan, channels, batch=8):
+        from . import graph as G
+        from .graphs import GraphedEval
+        self.model, self.plan = model, plan
+        dev = torch.device("cuda", torch.cuda.current_device())
+        self._ids = _chunk_ids(plan, batch, dev)
+        x3 = torch.zeros((int(channels), plan.H, plan.W), dtype=torch.float32, device=dev)
+        self._tiles = torch.empty((self._ids.shape[1], int(channels), plan.th, plan.tw), dtype=torch.float32, device=dev)
+        self._canvases = []
+
+        def chunk(xs, ids):
+            self._tuple = _tiled_chunk(model, xs, plan, ids, self._canvases, self._tiles)
+            return ()
+
+        was_training = model.training
+        model.eval()
+        try:
+            with torch.no_grad():
+                chunk(x3, self._ids[0])           # eager once: allocations, pack entries, the canvases
+            self._ge = GraphedEval(chunk, [x3, self._ids[0]], pack_cache=G.pack_cache_of(model))
+        finally:
+            model.train(was_training)
+
+    @torch.no_grad()
+    def _run(self, x, mask):
+        x3 = _tiled_image(x, self.plan)
+        xs = self._ge.static_inputs[0]
+        if tuple(x3.shape) != tuple(xs.shape):
+            raise ValueError(f"this TiledPredictor was built for {xs.shape[0]} channels, got {x3.shape[0]}")
+        xs.copy_(x3, non_blocking=True)
+        for acc in self._canvases:
+            acc.zero_()
+        for c in range(self._ids.shape[0]):
+            self._ge(xs, self._ids[c])            # xs is the static input itself: only the ids are copied
+        res = tuple(tile_finish(acc, self.plan, mask) for acc in self._canvases)
+        res = tuple(m for _, m in res) if mask else tuple(acc.clone() for acc in res)
+        return res if self._tuple else res[0]
+
+    def __call__(self, x):
+        return self._run(x, False)
+
+    def predict_mask(self, x):
+        return self._run(x, True)
 
 
 def score_binary_masks(mask, gt_dots, sigma_list, sigma_thresh_list, dist_thresh=10, size=512):
