@@ -1,5 +1,7 @@
-"""Kernel-level GPU parity: every libunetmi op against plain PyTorch fp32 (CPU) on odd shapes, and the
-MFMA fast paths against the generic kernels (UMI_CONV_FORCE_GENERIC) on the same inputs."""
+"""Kernel-level GPU parity in fp16 STORAGE: every libunetmi op, fed fp16 tensors, against plain PyTorch fp32 (CPU) on odd
+shapes, and the MFMA fast paths against the generic kernels (UMI_CONV_FORCE_GENERIC; their <half_t, half_t> instantiations) on
+the same inputs.  The fp32 instantiations of the generic kernels -- what compute_dtype="fp32" runs on -- are held to float64 in
+tests/test_gpu_valu_f32.py."""
 import pytest
 import torch
 import torch.nn.functional as F
