@@ -941,6 +941,31 @@ int umi_tile_blend(const float* logits, int K, int th, int tw, float* acc, int H
                    const float* wy, const float* wx, const int* ids, int n, umi_stream_t stream);
 int umi_tile_finish(float* acc, int K, int H, int W, const float* sy, const float* sx, unsigned char* mask, umi_stream_t stream);
 
+/* Test-time augmentation over the rot90 / flip symmetries of the square, and model ensembles (csrc/tta.hip; statement:
+ * umi/tta.py).  Element e in 0..7: k = e & 3 quarter turns as np.rot90(x, k, axes=(-2, -1)), then np.flip(axis=-1) if e >> 2; odd k
+ * turns [H][W] into [W][H].  `elems` holds the V <= 16 elements of a call BY VALUE, 4 bits each, the first in the lowest bits; they
+ * must share one output shape [H'][W'] (any mix for H == W, otherwise all even or all odd k).  mode: 0 = logit, 1 = relu, 2 = prob.
+ *   umi_tta_views: x fp32 [N][C][H][W] -> out fp32 [V*N][C][H'][W'], view-major: out[s*N + n] = view_e(s)(x[n]).  Every element of
+ *     `out` is written.
+ *   umi_tta_accumulate: y fp32 [V*N][K][H'][W'], the network's outputs for those views; for every image pixel p and the views in
+ *     order, acc[n][k][p] = fp32(acc[n][k][p] + t(y[s*N + n][.][q])[k]) with q the view pixel that shows p and t by mode: the value;
+ *     0 where the value < 0 (a NaN and -0.0 pass through); the fp32 softmax over the K channels, exp(v - max) / sum, for K == 1
+ *     1 / (1 + exp(-v)).  One thread owns a pixel and holds its K sums in registers: one read and one write of acc per call, no
+ *     atomics.  acc fp32 [N][K][H][W], zeroed by the caller before the first call.
+ *   umi_tta_finish: acc = fp32(acc / float(count)) in place.  mask (uint8 [N][H][W], or NULL): K >= 2 umi_argmax_mask's rule on the
+ *     quotient (the first strict maximum wins, a NaN never wins); K == 1 umi_binary_mask's (>= -0x1.7ffffcp-23) in modes 0 and 1,
+ *     >= 0.5 in mode 2; NaN gives 0.  entropy (fp32 [N][H][W], or NULL; mode 2 only): -sum_k p log p over the quotients with p > 0,
+ *     for K == 1 over p and fp32(1 - p).
+ * UMI_ERR_BADARG: null pointers (but `mask`, `entropy`), pointers not 4-byte aligned, non-positive sizes or count, V outside 1..16,
+ * an element above 7 or bits above the V-th element, two output shapes in one call, an unknown mode, `entropy` outside mode 2.
+ * UMI_ERR_UNSUPPORTED: K > 32, V * N * C * H * W (views), V * N * K * H * W (accumulate) or N * K * H * W (finish) >= 2^31, N * C
+ * (views) or N (accumulate, finish) > 65535.  Nothing is launched then.  One launch each, no allocation, no host
+ * synchronisation, no host memory read at launch time: all three can be captured. */
+int umi_tta_views(const float* x, int N, int C, int H, int W, float* out, long long elems, int V, umi_stream_t stream);
+int umi_tta_accumulate(float* acc, int N, int K, int H, int W, const float* y, long long elems, int V, int mode, umi_stream_t stream);
+int umi_tta_finish(float* acc, int N, int K, int H, int W, int count, int mode, unsigned char* mask, float* entropy,
+                   umi_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -22,6 +22,12 @@ Images larger than the network input, any model (umi/tiles.py: overlap-tile or w
     logits = infer.predict_logits_tiled(model, x, plan, batch=8)   # fp32 (K,H,W); predict_mask_tiled: the uint8 (H,W) mask
     predict = infer.TiledPredictor(model, plan, channels)          # the chunk replayed from a HIP graph
 
+Test-time augmentation over the rot90 / flip views the models are trained under, and model ensembles (umi/tta.py):
+
+    probs = infer.predict_logits_tta(model, x, views='d4', mode='prob')      # fp32 (N,K,H,W): mean softmax over the eight views
+    mask = infer.predict_mask_tta([model_a, model_b], x, 'flips', 'logit')   # uint8 (N,H,W); a list of models is an ensemble
+    predict = infer.TTAPredictor(model, x, 'd4', 'prob')                     # views -> forwards -> accumulate from a HIP graph
+
 Multi-class models, the rest of test_mc3serousv5.py (Results2Class / Results3Class) after predict_mask:
 
     labels, counts, class_counts, label_class, area, sum_y, sum_x = infer.label_class_components(mask, n_classes)
@@ -507,6 +513,188 @@ class TiledPredictor:
 
     def predict_mask(self, x):
         return self._run(x, True)
+
+
+# ---- test-time augmentation over the rot90 / flip views, and model ensembles (umi/tta.py, csrc/tta.hip) ------------------------------
+def _tta_models(model):
+    models = list(model) if isinstance(model, (list, tuple)) else [model]
+    if not models:
+        raise ValueError("an empty list of models")
+    return models
+
+
+def _tta_input(x):
+    if x.dim() != 4 or x.dtype != torch.float32 or x.numel() == 0:
+        raise ValueError(f"expected a non-empty fp32 batch (N,C,H,W), got {tuple(x.shape)} {x.dtype}")
+    return x.to("cuda").contiguous()
+
+
+def _tta_forward(model, v, batch):
+    """model over the rows of v in chunks of at most `batch` -> a list (one entry per head) of fp32 (rows,K,h,w) and whether the
+    model is two-headed."""
+    rows = v.shape[0]
+    step = rows if batch is None else int(batch)
+    heads, two = None, False
+    for a in range(0, rows, step):
+        out = model(v[a:a + step])
+        two = isinstance(out, tuple)
+        outs = out if two else (out,)
+        for o in outs:
+            if o.dim() != 4 or o.dtype != torch.float32 or not o.is_cuda or o.shape[0] != min(step, rows - a):
+                raise ValueError(f"a model under TTA must return fp32 device logits (n,K,h,w) for n view-images, got "
+                                 f"{tuple(o.shape)} {o.dtype}")
+        if heads is None:
+            if step >= rows:
+                return [o.contiguous() for o in outs], two
+            heads = [torch.empty((rows,) + tuple(o.shape[1:]), dtype=torch.float32, device=v.device) for o in outs]
+        for h, o in zip(heads, outs):
+            h[a:a + step] = o
+    return heads, two
+
+
+def _tta_accumulate(models, x, elements, mode, batch, accs):
+    """Every model's outputs over every view of x, accumulated into `accs` (a list filled with zeroed (N,K,H,W) sums on first use)
+    model after model and, per pixel, in the order of `elements`.  The views of one shape go through a model together (in chunks of
+    `batch` view-images) and their outputs are kept; the accumulate calls then walk the tuple in runs of one shape, so the order
+    of the sum is the tuple's whatever the shapes and the chunks.  Returns whether the models are two-headed."""
+    from . import tta as T
+    N, _, H, W = x.shape
+    classes = T.shape_classes(elements, H, W)
+    vx = {shape: T.views(x, [elements[p] for p in pos]) for shape, pos in classes.items()}
+    slot = {p: (shape, s) for shape, pos in classes.items() for s, p in enumerate(pos)}
+    two = False
+    for model in models:
+        outs = {}
+        for shape in classes:
+            outs[shape], two = _tta_forward(model, vx[shape], batch)
+        if not accs:
+            accs.extend(torch.zeros((N, o.shape[1], H, W), dtype=torch.float32, device=x.device) for o in next(iter(outs.values())))
+        a = 0
+        while a < len(elements):
+            shape, s0 = slot[a]
+            b = a + 1
+            while b < len(elements) and b - a < T.MAX_CALL_VIEWS and slot[b] == (shape, s0 + b - a):
+                b += 1
+            for acc, o in zip(accs, outs[shape]):
+                T.accumulate(acc, o[s0 * N:(s0 + b - a) * N], elements[a:b], mode)
+            a = b
+    return two
+
+
+def _tta_finish(accs, count, mode, mask, entropy, two, clone=False):
+    from . import tta as T
+    res = []
+    for acc in accs:
+        r = T.finish(acc, count, mode, mask=mask, entropy=entropy)
+        r = list(r) if isinstance(r, tuple) else [r]
+        mean = r.pop(0)
+        head = r.pop(0) if mask else (mean.clone() if clone else mean)
+        res.append((head, r[0]) if entropy else head)
+    return tuple(res) if two else res[0]
+
+
+@torch.no_grad()
+def _predict_tta(model, x, views, mode, batch, entropy, mask):
+    from . import tta as T
+    elements = T.view_set(views)
+    T.check_mode(mode)
+    if entropy and mode != "prob":
+        raise ValueError("the entropy map exists in 'prob' mode only")
+    if batch is not None and int(batch) < 1:
+        raise ValueError(f"batch must be >= 1 or None, got {batch}")
+    x = _tta_input(x)
+    models = _tta_models(model)
+    flags = [(m, m.training) for m in models if isinstance(m, torch.nn.Module)]
+    for m, _ in flags:
+        m.eval()
+    try:
+        accs = []
+        two = _tta_accumulate(models, x, elements, mode, batch, accs)
+        return _tta_finish(accs, len(elements) * len(models), mode, mask, entropy, two)
+    finally:
+        for m, was_training in flags:
+            m.train(was_training)
+
+
+def predict_logits_tta(model, x, views="d4", mode="prob", batch=None, entropy=False):
+    """Test-time augmentation (umi/tta.py): the model's outputs over the rot90 / flip views of x (N,C,H,W) fp32, mapped back and
+    averaged on the device -> fp32 (N,K,H,W): the mean logits ('logit'), the mean of the rectified outputs ('relu') or the mean
+    softmax / sigmoid probabilities ('prob').  views: 'none', 'flips', 'd4' or a tuple of elements 0..7.  entropy=True ('prob')
+    returns (mean, entropy) with the fp32 (N,H,W) predictive entropy of the mean probabilities.  A two-headed model gives a tuple.
+
+    Eval-mode forwards over chunks of at most `batch` view-images (None: all views of one shape at once); with H != W the odd
+    turns form a second batch of shape (W,H).  The sum runs per pixel in the order of `views` whatever the chunks: 'logit' and
+    'relu' are tta.merge_numpy bit for bit, 'prob' within tta.prob_bound.  Nothing returns to the host; the training flags are
+    restored.  `model` may also be a callable returning fp32 device logits (n,K,h,w) for n view-images, e.g.
+    `lambda v: predict_logits_tiled(m, v, plan)[None]` with batch=1, or a list of models or callables: the per-seed ensemble of
+    train.py, accumulated model after model and divided by len(views) * len(models)."""
+    return _predict_tta(model, x, views, mode, batch, entropy, False)
+
+
+def predict_mask_tta(model, x, views="d4", mode="prob", batch=None, entropy=False):
+    """predict_logits_tta, returning the uint8 (N,H,W) mask of the mean instead, written by the finish kernel: argmax_mask's rule
+    (K >= 2); for one logit binary_mask's rule on the mean logit, or mean probability >= 0.5 in 'prob' mode.  entropy=True:
+    (mask, entropy)."""
+    return _predict_tta(model, x, views, mode, batch, entropy, True)
+
+
+class TTAPredictor:
+    """predict_logits_tta / predict_mask_tta replayed from a HIP graph for inputs of one shape:
+
+        predict = infer.TTAPredictor(model, example_x, views='d4', mode='prob')
+        mean = predict(x)                         # fp32 (N,K,H,W); predict(x, entropy=True): (mean, entropy)
+        mask = predict.predict_mask(x)            # uint8 (N,H,W)
+
+    The constructor runs views -> forward(s) -> accumulate once eagerly and captures it in a umi.graphs.GraphedEval holding the
+    models' weight-pack caches; a call copies x into the static input, replays (the sums are zeroed inside the graph), runs the
+    finish kernel behind the replay and returns CLONES.  As GraphedPredictor: a replay after an optimizer step or load_state_dict
+    reads the current weights, inputs of another shape go through the eager functions, the training flags are left as they were.
+    `model` may be a list of models (an ensemble)."""
+
+    def __init__(self, model, example_x, views="d4", mode="prob", batch=None):
+        from . import graph as G
+        from . import tta as T
+        from .graphs import GraphedEval
+        self.model, self.views, self.mode, self.batch = model, T.view_set(views), mode, batch
+        T.check_mode(mode)
+        models = _tta_models(model)
+        x = _tta_input(example_x)
+        self.shape = tuple(x.shape)
+        self._accs = []
+
+        def fwd(xs):
+            for acc in self._accs:
+                acc.zero_()
+            self._tuple = _tta_accumulate(models, xs, self.views, mode, batch, self._accs)
+            return ()
+
+        self._count = len(self.views) * len(models)
+        flags = [(m, m.training) for m in models if isinstance(m, torch.nn.Module)]
+        for m, _ in flags:
+            m.eval()
+        try:
+            with torch.no_grad():
+                fwd(x)                            # eager once: allocations, pack entries, the sums
+            caches = [G.pack_cache_of(m) for m, _ in flags]
+            self._ge = GraphedEval(fwd, [x], pack_cache=caches)
+        finally:
+            for m, was_training in flags:
+                m.train(was_training)
+
+    @torch.no_grad()
+    def _run(self, x, entropy, mask):
+        if tuple(x.shape) != self.shape or x.dtype != torch.float32:
+            return _predict_tta(self.model, x, self.views, self.mode, self.batch, entropy, mask)
+        if entropy and self.mode != "prob":
+            raise ValueError("the entropy map exists in 'prob' mode only")
+        self._ge(x.to("cuda"))
+        return _tta_finish(self._accs, self._count, self.mode, mask, entropy, self._tuple, clone=True)
+
+    def __call__(self, x, entropy=False):
+        return self._run(x, entropy, False)
+
+    def predict_mask(self, x, entropy=False):
+        return self._run(x, entropy, True)
 
 
 def score_binary_masks(mask, gt_dots, sigma_list, sigma_thresh_list, dist_thresh=10, size=512):
