@@ -838,6 +838,39 @@ int umi_split_classes(const unsigned char* map, unsigned char* planes, int N, in
 int umi_class_center_lists(const int* counts, const unsigned char* label_class, const int* area, const long long* sum_y,
                            const long long* sum_x, int* centers, int* c_count, int N, int cap, int n_classes, umi_stream_t stream);
 
+/* Density-map (regression) evaluation (csrc/peaks.hip; statement and rule: umi/peaks.py): what the reference's test_single_reg /
+ * test_multiple_reg do with a head's output before CrowdMatchingTest(..., inputType='Regression').
+ *   umi_density_maps: x[N][H][W] fp32 -> pred = max(x, 0) / scale with an IEEE-rounded division (NaN stays NaN); counts[N]
+ *     (float64) = the sum of pred per image in a fixed order (per 4096-pixel block: 256 strided partial sums and a fixed tree;
+ *     then the blocks the same way), vmin[N] (fp32, nullable) = the minimum of pred per image with a NaN counted as 0 (what
+ *     umi_peak_lists needs of the image minimum).  scale > 0.  With pred null nothing is rectified, divided or stored: counts and
+ *     vmin are those of x itself (the sums of a map that exists already).  ws: umi_density_maps_ws_bytes(N, H, W) bytes, 8-byte
+ *     aligned.  No atomics.
+ *   umi_peak_lists: the local maxima of N fp32 maps [H][W] by the project's restatement of
+ *     skimage.feature.peak_local_max(map, min_distance=d) after map[map < floor] = 0, d = min_distance in 1..8, floor >= 0:
+ *       a = x >= floor ? x : 0 (NaN -> 0);  m = max of a over the (2d+1)^2 window clipped to the image;
+ *       candidate: a == m, a > min(a) over the image, d <= y < H - d, d <= x < W - d;
+ *       spacing: the candidates in raster order, each kept unless an already kept one lies at Chebyshev distance <= d - 1;
+ *       order: value descending, raster ascending among equal values.
+ *     peaks[N][max_peaks][2] (x, y) and p_count[N]; every entry beyond p_count[n] is written (0, 0).  max_peaks <=
+ *     umi_peaks_max() (8192).  vmin: umi_density_maps' vmin of the same maps, or null (the minimum is then taken here).
+ *     The fault word (the first int32 of ws, cleared by every call) is an OR of UMI_PEAKS_FAULT_OVERFLOW (1): an image has more
+ *     than max_peaks peaks, its first max_peaks in output order are listed and p_count = max_peaks, and
+ *     UMI_PEAKS_FAULT_CONTESTED (2): an image has more candidates with another candidate within d - 1 than the contested list
+ *     holds (min(H * W, 131072)); those beyond it are dropped and the image's list is invalid.  The spacing loop runs at most as
+ *     many rounds as the list holds entries, so the call always terminates.
+ *     H, W <= 4096, N <= 65535, N * H * W < 2^31, else UMI_ERR_UNSUPPORTED; ws: umi_peak_lists_ws_bytes(N, H, W) bytes (0:
+ *     unsupported size).  Nothing synchronises with the host; integer atomics only, and the lists do not depend on the order in
+ *     which they complete; no value of a map forms an address. */
+enum { UMI_PEAKS_FAULT_OVERFLOW = 1, UMI_PEAKS_FAULT_CONTESTED = 2 };
+int umi_peaks_max(void);
+size_t umi_density_maps_ws_bytes(int N, int H, int W);
+int umi_density_maps(const float* x, float* pred, double* counts, float* vmin, int N, int H, int W, float scale, void* ws,
+                     size_t ws_bytes, umi_stream_t stream);
+size_t umi_peak_lists_ws_bytes(int N, int H, int W);
+int umi_peak_lists(const float* maps, const float* vmin, int* peaks, int* p_count, int N, int H, int W, int min_distance,
+                   float floor, int max_peaks, void* ws, size_t ws_bytes, umi_stream_t stream);
+
 /* Training-batch transform (csrc/augment.hip; statement and rule: umi/augment.py): the reference's Dataset.transform for a batch.
  * Per sample params[n] = {mode, k, axis, angle} (int32) and geom[n] = {M00, M01, M10, M11, off0, off1} (float64, formed on the
  * host as scipy.ndimage.rotate forms them), both on the device and read there: mode 1 = np.flip(np.rot90(x, k), axis) (an odd k

@@ -12,7 +12,10 @@ CrowdMatchingTest2 gives (0, 0, 0) without centres and raises ZeroDivisionError 
 
 Not restated: inputType='Segmentation' (centres from cv2.findContours / cv2.moments) and 'Regression'
 (skimage.feature.peak_local_max) -- neither library is a dependency of this project; pass coordinates, e.g. from
-umi.infer.label_components + umi.matching.component_centers (pixel centroids, see umi/matching.py).  Dot maps must hold only 0
+umi.infer.label_components + umi.matching.component_centers (pixel centroids, see umi/matching.py).  For density maps,
+CrowdMatchingTestPeaks(g_dot, estimation, sigma_list, sigma_thresh_list) below takes the centres from the project's own
+restatement of the local-maximum rule (umi/peaks.py, pinned to SciPy; its agreement with scikit-image itself is unmeasured),
+which is why it has a name of its own and inputType='Regression' keeps raising.  Dot maps must hold only 0
 and 1, thresholds must be positive, and on the NumPy path centres must lie inside the image (ValueError otherwise: the
 reference's slicing does something of its own there).
 """
@@ -113,6 +116,32 @@ def CrowdMatchingTest(g_dot, estimation, sigma_list, sigma_thresh_list, inputTyp
     dots, g_count, centers, c_count = _host_lists(g_dot, e_coord_x, e_coord_y, inside=True)
     res = M.crowd_match_numpy(dots, g_count, centers, c_count, sigma_list, sigma_thresh_list)
     return precision_recall_f1(res[0], int(g_count[0]), int(c_count[0]))
+
+
+def CrowdMatchingTestPeaks(g_dot, estimation, sigma_list, sigma_thresh_list, min_distance=3, floor=0.001):
+    """CrowdMatchingTest on the local maxima of the float32 density map `estimation` (H, W): the reference's
+    inputType='Regression' with the peaks taken by umi.peaks' rule (the restatement of peak_local_max(estimation, min_distance)
+    after estimation[estimation < floor] = 0; `estimation` itself is left unmodified).  NumPy inputs run the statements; device
+    tensors run the kernels (peak lists, dot lists, matching) and read the integers back once."""
+    from umi import peaks as P
+    if _on_device(g_dot, estimation):
+        import torch
+        if g_dot.dim() != 2 or estimation.shape != g_dot.shape:
+            raise ValueError(f"expected an (H, W) dot map and density map, got {tuple(g_dot.shape)} {tuple(estimation.shape)}")
+        peaks, p_count, peak_fault = P.peak_lists(estimation, min_distance, floor, _fault=True)
+        dots, g_count, dot_fault = M.dot_lists(g_dot, _fault=True)
+        res = M.crowd_match(dots, g_count, peaks, p_count, sigma_list, sigma_thresh_list)
+        back = torch.cat([peak_fault, dot_fault, g_count, p_count, res.reshape(-1)]).cpu().numpy()
+        P.raise_on_peak_fault(back[0])
+        M.raise_on_dot_overflow(back[1])
+        return precision_recall_f1(back[4:].reshape(res.shape[1:]), int(back[2]), int(back[3]))
+    est = np.asarray(estimation.numpy() if hasattr(estimation, "numpy") else estimation)
+    if est.ndim != 2:
+        raise ValueError(f"expected an (H, W) density map, got {est.shape}")
+    peaks, p_count, fault = P.peak_lists_numpy(est, min_distance, floor)
+    P.raise_on_peak_fault(fault)
+    n = int(p_count[0])
+    return CrowdMatchingTest(g_dot, (peaks[0, :n, 0], peaks[0, :n, 1]), sigma_list, sigma_thresh_list, inputType='Coordinates')
 
 
 def _prf_distance(tp, n_centers, n_dots):

@@ -34,6 +34,13 @@ Multi-class models, the rest of test_mc3serousv5.py (Results2Class / Results3Cla
     class_counts = infer.count_class_objects(mask, n_classes)
     scores = infer.score_multiclass_masks(mask, gt_dots, n_classes, [10, 20], np.arange(0.5, 1, 0.05))
 
+Regression (density-map) models, the reference's test_single_reg / test_multiple_reg (umi/peaks.py: the peak rule is the
+project's restatement of skimage.feature.peak_local_max, pinned to SciPy; agreement with scikit-image itself is unmeasured):
+
+    pred = infer.predict_density(model, x, out_hw=(h, w))           # relu -> order-0 zoom -> / 200, fp32 (N,H,W) per head
+    peaks, p_count = peaks.peak_lists(pred, min_distance=3)          # local maxima as (x, y), value descending
+    scores = infer.score_density_maps(pred, gt_dots, [5, 20], np.arange(0.5, 1, 0.05))   # counts, GAME, matching per image
+
 No CPU path: the arithmetic is libunetmi kernels (the resize restates SciPy's spline algorithm, oracle/ref_resize.py).
 """
 import struct
@@ -274,21 +281,58 @@ def predict_binary_mask(model, x, out_hw=None):
         model.train(was_training)
 
 
+def _density_head(out, out_hw, scale):
+    from . import peaks as P
+    if out.dim() != 4 or out.dtype != torch.float32 or not out.is_cuda:
+        raise ValueError(f"predict_density expects fp32 device outputs (N,K,H,W), got {tuple(out.shape)} {out.dtype}")
+    N, K, H, W = out.shape
+    m = out.contiguous().view(N * K, H, W)
+    if out_hw is not None and (int(out_hw[0]) != H or int(out_hw[1]) != W):
+        m = zoom_nearest(m, out_hw)               # a gather (0 past the last sample): relu and the division commute with it
+    pred, _ = P.density_maps(m, scale)
+    return pred if K == 1 else pred.view(N, K, pred.shape[1], pred.shape[2])
+
+
+@torch.no_grad()
+def predict_density(model, x, out_hw=None, scale=200.0):
+    """Reference evaluation step of a regression (density-map) model (test_mc3serousv5.py:959-974): eval-mode forward, relu, the
+    order-0 zoom to `out_hw` = the image's own (height, width) when that differs from the network size, and the division by
+    `scale` (an IEEE division, umi_density_maps) -> fp32 (N,H,W) count map per head ((N,K,H,W) for a head with K > 1 channels).
+    A two-headed model gives a tuple in the model's own order; the reference reads it as (immune, other).  `model` may be any
+    callable returning fp32 device outputs (n,K,h,w), e.g. `lambda v: predict_logits_tiled(m, v, plan)[None]` or
+    `lambda v: predict_logits_tta(m, v, mode='relu')`.  Nothing returns to the host; a module's training flag is restored."""
+    is_module = isinstance(model, torch.nn.Module)
+    was_training = model.training if is_module else False
+    if is_module:
+        model.eval()
+    try:
+        out = model(x.to("cuda"))
+        if isinstance(out, tuple):
+            return tuple(_density_head(o, out_hw, scale) for o in out)
+        return _density_head(out, out_hw, scale)
+    finally:
+        if is_module:
+            model.train(was_training)
+
+
 class GraphedPredictor:
     """predict_mask (predict_binary_mask for a one-logit model) replayed from a HIP graph for inputs of one shape:
 
         predict = infer.GraphedPredictor(model, example_x)
         mask = predict(x)                         # uint8 [N,H,W], or a tuple of them for a two-headed model
 
+    With density=True it replays predict_density(model, x, out_hw, scale) instead and returns fp32 count maps.
+
     The constructor runs the eval-mode forward once eagerly and captures it, with the mask kernels behind it, in a
     umi.graphs.GraphedEval that holds the model's weight-pack cache: a call copies x into the static input, brings the weight
     copies up to date if a parameter changed since (optimizer step, load_state_dict), replays and returns CLONES of the static
     masks.  Inputs of another shape go through predict_mask / predict_binary_mask.  The model's training flag is left as it was."""
 
-    def __init__(self, model, example_x):
+    def __init__(self, model, example_x, density=False, out_hw=None, scale=200.0):
         from . import graph as G
         from .graphs import GraphedEval
         self.model = model
+        self.density, self.out_hw, self.scale = bool(density), out_hw, scale
         x = example_x.to("cuda")
         self.shape, self.dtype = tuple(x.shape), x.dtype
 
@@ -297,6 +341,8 @@ class GraphedPredictor:
             self._tuple = isinstance(out, tuple)
             outs = out if self._tuple else (out,)
             self.binary = outs[0].shape[1] == 1
+            if self.density:
+                return tuple(_density_head(o, out_hw, scale) for o in outs)
             return tuple((binary_mask if o.shape[1] == 1 else argmax_mask)(o) for o in outs)
 
         was_training = model.training
@@ -312,6 +358,8 @@ class GraphedPredictor:
     def __call__(self, x):
         x = x.to("cuda")
         if tuple(x.shape) != self.shape or x.dtype != self.dtype:
+            if self.density:
+                return predict_density(self.model, x, self.out_hw, self.scale)
             return (predict_binary_mask if self.binary else predict_mask)(self.model, x)
         masks = tuple(m.clone() for m in self._ge(x))
         return masks if self._tuple else masks[0]
@@ -885,3 +933,53 @@ def score_multiclass_masks(mask, gt_dots, n_classes, sigma_list, sigma_thresh_li
         host.append(back[at:at + t.numel()].reshape(t.shape))
         at += t.numel()
     return M.multiclass_scores(*host, K)
+
+
+# ---- density maps ----------------------------------------------------------------------------------------------------------------
+def score_density_maps(pred, gt_dots, sigma_list, sigma_thresh_list, size=512, min_distance=3, floor=1e-3):
+    """What the reference's regression evaluation (test_mc3serousv5.py `test_single_reg` :973-1024 and the localisation block
+    behind it, test_reg3serousv5mt.py `test_multiple_reg`) records for each image and head, computed on the device with ONE
+    device-to-host copy.  `pred` fp32 (N,H,W) count maps (predict_density's output), `gt_dots` uint8 / float32 (N,H,W) 0/1 dot
+    maps.  The fixed-order float64 sum of the map -> peak_lists (umi/peaks.py: the project's restatement of
+    skimage.feature.peak_local_max(pred, min_distance) after pred[pred < floor] = 0) -> Gaussian matching of the peaks against
+    the dot list (CrowdMatchingTest) -> the 8 x 8 grid sums of the dot map and of the count map (GMAE at levels 1-3 over `size`
+    pixels; CrowdMatching.game_from_cells truncates the cell sums with int() as the reference's GMAE does).
+
+    Returns a list of N dicts: 'GT' (dot count), 'Pred' (the float64 sum; the reference's np.sum of a float32 array is a float32
+    pairwise sum, a different rounding of the same number), 'AbsDiff', 'Accuracy', 'AccuracyRelative', 'AccuracyRelativePD'
+    (CrowdMatching.countAccuracyMetric), 'G1', 'G2', 'G3' (each [gmae, relative, relativePD]), 'peaks' (their number),
+    'arr_prec', 'arr_recall', 'arr_f1' ((S, T) float64).  For a pair of heads pass `pred` = (head 0, head 1) and `gt_dots` likewise:
+    every image then gives {0: ..., 1: ..., 'ratio': ...} with the reference's immune / (other + immune) block through
+    umi.matching.ratio_metrics, the heads read as (immune, other); still one copy.  Raises on either fault word (more than
+    umi.peaks.MAX_PEAKS peaks or umi.matching.MAX_DOTS dots in an image).  umi.peaks.score_density_numpy is the host statement."""
+    from . import matching as M
+    from . import peaks as P
+    pair = P._heads(pred, gt_dots)
+    if pair:
+        n_first = pred[0].shape[0]
+        pred, gt_dots = torch.cat([p.contiguous() for p in pred]), torch.cat([g.contiguous() for g in gt_dots])
+    if pred.dim() != 3 or gt_dots.shape != pred.shape or pred.dtype != torch.float32:
+        raise ValueError(f"score_density_maps expects fp32 (N,H,W) maps and dot maps of one shape, got {tuple(pred.shape)} "
+                         f"{pred.dtype} {tuple(gt_dots.shape)}")
+    ops._need_cuda(pred, gt_dots)
+    pred = pred.contiguous()
+    N = pred.shape[0]
+    counts, vmin = P.map_sums(pred)
+    peaks, p_count, peak_fault = P.peak_lists(pred, min_distance, floor, _fault=True, vmin=vmin)
+    dots, g_count, dot_fault = M.dot_lists(gt_dots, _fault=True)
+    crowd = M.crowd_match(dots, g_count, peaks, p_count, sigma_list, sigma_thresh_list)
+    cells_gt = M.grid_sums(gt_dots, size).to(torch.int64)           # sums of a 0/1 map: exact in either type
+    cells_pred = M.grid_sums(pred, size)
+    parts = (peak_fault, dot_fault, g_count, p_count, crowd, cells_gt, counts, cells_pred)
+    back = torch.cat([(t.view(torch.int64) if t.dtype == torch.float64 else t.to(torch.int64)).reshape(-1)
+                      for t in parts]).cpu().numpy()                  # float64 travels as its bits
+    P.raise_on_peak_fault(back[0])
+    M.raise_on_dot_overflow(back[1])
+    host, at = [], 2
+    for t in parts[2:]:
+        h = back[at:at + t.numel()]
+        host.append((h.view(np.float64) if t.dtype == torch.float64 else h).reshape(t.shape))
+        at += t.numel()
+    g_h, p_h, crowd_h, cg, cnt_h, cp = host
+    res = P.density_scores(g_h, cnt_h, p_h, crowd_h, cg, cp)
+    return P.pair_scores(res[:n_first], res[n_first:]) if pair else res

@@ -247,9 +247,11 @@ def ratio_metrics(cell_gt, immune_gt, cell_pred, immune_pred):
     immune / (cell + immune) of the ground truth and of the prediction and countAccuracyMetric of the two.  A prediction
     without a cell or immune object raises ZeroDivisionError as the reference does; a ground truth without either gives a
     ratio of nan (the reference's numpy.uint64 0 / 0), and the metrics derived from it are whatever the reference's
-    expressions make of nan."""
+    expressions make of nan.  Counts given as Python floats (the float64 sums of density maps, umi/peaks.py) stay floats, as in
+    the reference's regression scripts (test_mc3serousv5.py:1015-1017)."""
     import CrowdMatching as CM
-    cell_gt, immune_gt, cell_pred, immune_pred = int(cell_gt), int(immune_gt), int(cell_pred), int(immune_pred)
+    cell_gt, immune_gt, cell_pred, immune_pred = (v if isinstance(v, float) else int(v)
+                                                  for v in (cell_gt, immune_gt, cell_pred, immune_pred))
     ratio_gt = immune_gt / (cell_gt + immune_gt) if cell_gt + immune_gt else float("nan")
     ratio_pred = immune_pred / (cell_pred + immune_pred)
     abs_diff, acc, rel, rel_pd = CM.countAccuracyMetric(ratio_gt, ratio_pred)
