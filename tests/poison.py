@@ -32,8 +32,8 @@ def fill_bytes(t, byte, _empty=torch.empty):
 def poisoned(byte, cpu_too=False):
     """For the duration: every CUDA tensor returned by torch.empty / empty_like / empty_strided has all its bytes set to
     `byte`, and the buffer `umi.ops.workspace` returns is re-filled with `byte` on every call (each call site of the tapes
-    requests, fills and consumes the workspace within one Python call).  Not for use around `umi.infer`, whose `_fault_word`
-    reads the word a previous call left in the workspace.  cpu_too: also fill CPU tensors (the helper's own CPU test).
+    requests, fills and consumes the workspace within one Python call).  cpu_too: also fill CPU tensors (the helper's own CPU
+    test).
     The originals are restored on exit, also on error."""
     byte = int(byte)
     assert 0 <= byte <= 255

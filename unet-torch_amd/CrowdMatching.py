@@ -107,12 +107,12 @@ def CrowdMatchingTest(g_dot, estimation, sigma_list, sigma_thresh_list, inputTyp
     `estimation` = (x coordinates, y coordinates) to the dots of the 0/1 map `g_dot` (H, W)."""
     e_coord_x, e_coord_y = _coordinates(estimation, inputType)
     if _on_device(g_dot, e_coord_x, e_coord_y):
-        import torch
+        from umi import ops
         dots, g_count, fault, centers, c_count = _device_lists(g_dot, e_coord_x, e_coord_y)
         res = M.crowd_match(dots, g_count, centers, c_count, sigma_list, sigma_thresh_list)
-        back = torch.cat([fault, g_count, res.reshape(-1)]).cpu().numpy()
-        M.raise_on_dot_overflow(back[0])
-        return precision_recall_f1(back[2:].reshape(res.shape[1:]), int(back[1]), len(e_coord_x))
+        code, g_h, res_h = ops.read_back(fault, g_count, res)
+        M.raise_on_dot_overflow(code[0])
+        return precision_recall_f1(res_h[0], int(g_h[0]), len(e_coord_x))
     dots, g_count, centers, c_count = _host_lists(g_dot, e_coord_x, e_coord_y, inside=True)
     res = M.crowd_match_numpy(dots, g_count, centers, c_count, sigma_list, sigma_thresh_list)
     return precision_recall_f1(res[0], int(g_count[0]), int(c_count[0]))
@@ -125,16 +125,16 @@ def CrowdMatchingTestPeaks(g_dot, estimation, sigma_list, sigma_thresh_list, min
     tensors run the kernels (peak lists, dot lists, matching) and read the integers back once."""
     from umi import peaks as P
     if _on_device(g_dot, estimation):
-        import torch
+        from umi import ops
         if g_dot.dim() != 2 or estimation.shape != g_dot.shape:
             raise ValueError(f"expected an (H, W) dot map and density map, got {tuple(g_dot.shape)} {tuple(estimation.shape)}")
         peaks, p_count, peak_fault = P.peak_lists(estimation, min_distance, floor, _fault=True)
         dots, g_count, dot_fault = M.dot_lists(g_dot, _fault=True)
         res = M.crowd_match(dots, g_count, peaks, p_count, sigma_list, sigma_thresh_list)
-        back = torch.cat([peak_fault, dot_fault, g_count, p_count, res.reshape(-1)]).cpu().numpy()
-        P.raise_on_peak_fault(back[0])
-        M.raise_on_dot_overflow(back[1])
-        return precision_recall_f1(back[4:].reshape(res.shape[1:]), int(back[2]), int(back[3]))
+        peak_code, dot_code, g_h, p_h, res_h = ops.read_back(peak_fault, dot_fault, g_count, p_count, res)
+        P.raise_on_peak_fault(peak_code[0])
+        M.raise_on_dot_overflow(dot_code[0])
+        return precision_recall_f1(res_h[0], int(g_h[0]), int(p_h[0]))
     est = np.asarray(estimation.numpy() if hasattr(estimation, "numpy") else estimation)
     if est.ndim != 2:
         raise ValueError(f"expected an (H, W) density map, got {est.shape}")
@@ -158,12 +158,12 @@ def CrowdMatchingTest2(gt_dot, predLocalization, thresh):
     if len(e_coord_x) == 0:
         return 0, 0, 0
     if _on_device(gt_dot, e_coord_x, e_coord_y):
-        import torch
+        from umi import ops
         dots, g_count, fault, centers, c_count = _device_lists(gt_dot, e_coord_x, e_coord_y)
         res = M.distance_match(dots, g_count, centers, c_count, thresh)
-        back = torch.cat([fault, res.reshape(-1)]).cpu().tolist()
-        M.raise_on_dot_overflow(back[0])
-        return _prf_distance(back[1], back[2], back[3])
+        code, res_h = ops.read_back(fault, res)
+        M.raise_on_dot_overflow(code[0])
+        return _prf_distance(*res_h[0].tolist())
     g = np.asarray(gt_dot.numpy() if hasattr(gt_dot, "numpy") else gt_dot)
     dots, g_count, centers, c_count = _host_lists(g != 0, e_coord_x, e_coord_y, inside=False)
     tp, nc, ng = (int(v) for v in M.distance_match_numpy(dots, g_count, centers, c_count, thresh)[0])
@@ -196,8 +196,8 @@ def GMAE(L, gtImg, predImg, size=512):
     """Grid mean absolute error at level L (4^L cells of size // 2^L pixels over the top-left size x size pixels) of two count
     maps (H, W); L = 0..3.  Device tensors: uint8 or float32 maps, one read-back."""
     if _on_device(gtImg, predImg):
-        import torch
-        cells = torch.cat([M.grid_sums(gtImg, size).double(), M.grid_sums(predImg, size).double()]).cpu().numpy()
+        from umi import ops
+        cells = [c[0] for c in ops.read_back(M.grid_sums(gtImg, size), M.grid_sums(predImg, size))]
     else:
         cells = [M.grid_sums_numpy(np.asarray(m.numpy() if hasattr(m, "numpy") else m), size)[0] for m in (gtImg, predImg)]
     return game_from_cells(L, cells[0], cells[1])

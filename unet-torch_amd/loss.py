@@ -550,22 +550,20 @@ def MRAccuracy(pred, target):
     if batch_size == 0:
         raise ZeroDivisionError("MRAccuracy of an empty batch")
     if pred.is_cuda:
-        from umi import infer
+        from umi import infer, ops
         pred = pred[:batch_size]
         if pred.dtype == torch.float32:
             mask = infer.binary_mask(pred.unsqueeze(1))
         else:
             mask = (torch.sigmoid(pred) >= 0.5).to(torch.uint8).contiguous()
-        # the dot sums first: both calls use the shared workspace, and the labelling's fault word has to survive until the copy
         gts = infer.sum_trunc(target.detach().reshape(batch_size, -1).float()) if target.is_cuda else None
         counts, fault = infer.count_objects(mask, _fault=True)
         if gts is not None:
-            host = torch.cat([counts, gts, fault]).cpu().tolist()
-            n_pred, n_gt, code = host[:batch_size], host[batch_size:2 * batch_size], host[-1]
+            n_pred, n_gt, (code,) = (h.tolist() for h in ops.read_back(counts, gts, fault))
         else:
-            host = torch.cat([counts, fault]).cpu().tolist()
+            n_pred, (code,) = (h.tolist() for h in ops.read_back(counts, fault))
             tnp = target.detach().numpy()
-            n_pred, n_gt, code = host[:batch_size], [int(np.sum(tnp[b])) for b in range(batch_size)], host[-1]
+            n_gt = [int(np.sum(tnp[b])) for b in range(batch_size)]
         if code:
             raise RuntimeError(f"MRAccuracy: the component labelling reported fault {code}; the counts are invalid")
     else:

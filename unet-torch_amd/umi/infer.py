@@ -43,6 +43,7 @@ project's restatement of skimage.feature.peak_local_max, pinned to SciPy; agreem
 
 No CPU path: the arithmetic is libunetmi kernels (the resize restates SciPy's spline algorithm, oracle/ref_resize.py).
 """
+import contextlib
 import struct
 
 import numpy as np
@@ -50,6 +51,34 @@ import torch
 
 from . import lib as L
 from . import ops
+
+
+def _modules(models):
+    return [m for m in (models if isinstance(models, (list, tuple)) else [models]) if isinstance(m, torch.nn.Module)]
+
+
+@contextlib.contextmanager
+def _eval_mode(models):
+    """`models` (a module, a callable, or a list of either): the modules in eval mode for the duration, every training flag
+    restored on exit, also on error; anything that is no module is left alone."""
+    flags = [(m, m.training) for m in _modules(models)]
+    for m, _ in flags:
+        m.eval()
+    try:
+        yield
+    finally:
+        for m, was_training in flags:
+            m.train(was_training)
+
+
+def _capture(fn, example_inputs, models):
+    """`fn` run eagerly once (allocations, pack entries, the shared workspace) and then captured, both under no_grad with
+    `models` in eval mode: the umi.graphs.GraphedEval of `fn` that holds the modules' weight-pack caches."""
+    from . import graph as G
+    from .graphs import GraphedEval
+    with _eval_mode(models), torch.no_grad():
+        fn(*example_inputs)
+        return GraphedEval(fn, example_inputs, pack_cache=[G.pack_cache_of(m) for m in _modules(models)])
 
 
 def zoom_cubic(img, input_size):
@@ -131,15 +160,11 @@ def argmax_mask(logits):
 def predict_mask(model, x):
     """Reference evaluation step (test_mc3serousv5.py:879-885): eval-mode forward, softmax, argmax -> uint8 mask.  The
     model's kernel-layout weight copies are cached between calls (ops.PackCache), so a loop over images packs once."""
-    was_training = model.training
-    model.eval()
-    try:
+    with _eval_mode(model):
         out = model(x.to("cuda"))
         if isinstance(out, tuple):
             return tuple(argmax_mask(o) for o in out)
         return argmax_mask(out)
-    finally:
-        model.train(was_training)
 
 
 # fp32 sigmoid(x) >= 0.5 as torch evaluates it (1 / (1 + exp(-x))) holds exactly for x >= this value, not for x >= 0: 1 + exp(-x)
@@ -201,14 +226,14 @@ def _component_mask(mask):
     return m, N, H, W, nbytes
 
 
-def _raise_on_fault(ws, what):
-    code = int(ws[:4].view(torch.int32).item())
+def _raise_on_fault(code, what):
+    code = int(code)
     if code:
         raise RuntimeError(f"{what}: the union-find reported fault {code} (iteration cap reached or parent chain corrupted); "
                            "the results are invalid")
 
 
-def label_components(mask, check=False):
+def label_components(mask, check=False, _fault=False):
     """8-connected components (cv2.connectedComponents(connectivity=8), reference loss.py:432) of a uint8 (N,H,W) or (H,W)
     device mask, foreground = non-zero.  Returns, all on the device and without a host synchronisation:
       labels int32, the mask's shape: 0 = background, 1..n numbered in the raster order of each component's first pixel
@@ -227,9 +252,11 @@ def label_components(mask, check=False):
     ws = ops.workspace(nbytes, dev)
     L.call("umi_label_components", m.data_ptr(), labels.data_ptr(), counts.data_ptr(), area.data_ptr(), sum_y.data_ptr(),
            sum_x.data_ptr(), N, H, W, ws.data_ptr(), nbytes, ops._stream())
+    fault = ops.fault_word(ws) if check or _fault else None
     if check:
-        _raise_on_fault(ws, "label_components")
-    return (labels[0] if mask.dim() == 2 else labels), counts, area, sum_y, sum_x
+        _raise_on_fault(fault, "label_components")
+    outs = (labels[0] if mask.dim() == 2 else labels), counts, area, sum_y, sum_x
+    return outs + (fault,) if _fault else outs
 
 
 def count_objects(mask, check=False, _fault=False):
@@ -239,9 +266,10 @@ def count_objects(mask, check=False, _fault=False):
     counts = torch.empty(N, dtype=torch.int32, device=m.device)
     ws = ops.workspace(nbytes, m.device)
     L.call("umi_count_components", m.data_ptr(), counts.data_ptr(), N, H, W, ws.data_ptr(), nbytes, ops._stream())
+    fault = ops.fault_word(ws) if check or _fault else None
     if check:
-        _raise_on_fault(ws, "count_objects")
-    return (counts, ws[:4].view(torch.int32)) if _fault else counts
+        _raise_on_fault(fault, "count_objects")
+    return (counts, fault) if _fault else counts
 
 
 def sum_trunc(x):
@@ -270,15 +298,11 @@ def predict_binary_mask(model, x, out_hw=None):
     """Reference evaluation step of a one-logit model (test.py:391-404): eval-mode forward, sigmoid >= 0.5 -> uint8 [N,H,W]
     mask, and the nearest (order-0) resize to `out_hw` = the image's own (height, width) when that differs from the network
     size.  Two-headed models give a tuple of masks, as predict_mask does."""
-    was_training = model.training
-    model.eval()
-    try:
+    with _eval_mode(model):
         out = model(x.to("cuda"))
         if isinstance(out, tuple):
             return tuple(_binary_head(o, out_hw) for o in out)
         return _binary_head(out, out_hw)
-    finally:
-        model.train(was_training)
 
 
 def _density_head(out, out_hw, scale):
@@ -301,18 +325,11 @@ def predict_density(model, x, out_hw=None, scale=200.0):
     A two-headed model gives a tuple in the model's own order; the reference reads it as (immune, other).  `model` may be any
     callable returning fp32 device outputs (n,K,h,w), e.g. `lambda v: predict_logits_tiled(m, v, plan)[None]` or
     `lambda v: predict_logits_tta(m, v, mode='relu')`.  Nothing returns to the host; a module's training flag is restored."""
-    is_module = isinstance(model, torch.nn.Module)
-    was_training = model.training if is_module else False
-    if is_module:
-        model.eval()
-    try:
+    with _eval_mode(model):
         out = model(x.to("cuda"))
         if isinstance(out, tuple):
             return tuple(_density_head(o, out_hw, scale) for o in out)
         return _density_head(out, out_hw, scale)
-    finally:
-        if is_module:
-            model.train(was_training)
 
 
 class GraphedPredictor:
@@ -329,8 +346,6 @@ class GraphedPredictor:
     masks.  Inputs of another shape go through predict_mask / predict_binary_mask.  The model's training flag is left as it was."""
 
     def __init__(self, model, example_x, density=False, out_hw=None, scale=200.0):
-        from . import graph as G
-        from .graphs import GraphedEval
         self.model = model
         self.density, self.out_hw, self.scale = bool(density), out_hw, scale
         x = example_x.to("cuda")
@@ -345,14 +360,7 @@ class GraphedPredictor:
                 return tuple(_density_head(o, out_hw, scale) for o in outs)
             return tuple((binary_mask if o.shape[1] == 1 else argmax_mask)(o) for o in outs)
 
-        was_training = model.training
-        model.eval()
-        try:
-            with torch.no_grad():
-                fwd(x)                            # eager once: allocations, pack entries, the shared workspace
-            self._ge = GraphedEval(fwd, [x], pack_cache=G.pack_cache_of(model))
-        finally:
-            model.train(was_training)
+        self._ge = _capture(fwd, [x], model)
 
     @torch.no_grad()
     def __call__(self, x):
@@ -378,9 +386,7 @@ def predict_binary_mask_tiled(model, x, crop_size):
     if crop_size < 1 or Hp % crop_size or Wp % crop_size or Hp == 0 or Wp == 0:
         raise ValueError(f"the padded image {Hp}x{Wp} is not a whole number of {crop_size}-pixel tiles")
     x = x.to("cuda")
-    was_training = model.training
-    model.eval()
-    try:
+    with _eval_mode(model):
         pred = None
         for i in range(0, Hp, crop_size):
             for j in range(0, Wp, crop_size):
@@ -391,8 +397,6 @@ def predict_binary_mask_tiled(model, x, crop_size):
                 for p, o in zip(pred, outs):
                     p[i:i + crop_size, j:j + crop_size] = binary_mask(o)[0]
         return tuple(pred) if isinstance(out, tuple) else pred[0]
-    finally:
-        model.train(was_training)
 
 
 # ---- overlap-tile / sliding-window inference over an image larger than the network input (umi/tiles.py, csrc/tiles.hip) -------------
@@ -475,9 +479,7 @@ def _tiled_chunk(model, x3, plan, ids, canvases, tiles=None):
 def _predict_tiled(model, x, plan, batch, mask):
     x3 = _tiled_image(x, plan)
     ids = _chunk_ids(plan, batch, x3.device)
-    was_training = model.training
-    model.eval()
-    try:
+    with _eval_mode(model):
         canvases, two = [], False
         for c in range(ids.shape[0]):
             two = _tiled_chunk(model, x3, plan, ids[c], canvases)
@@ -485,8 +487,6 @@ def _predict_tiled(model, x, plan, batch, mask):
         if mask:
             res = tuple(m for _, m in res)
         return res if two else res[0]
-    finally:
-        model.train(was_training)
 
 
 def predict_logits_tiled(model, x, plan, batch=8):
@@ -519,8 +519,6 @@ class TiledPredictor:
     GraphedPredictor does.  The model's training flag is left as it was."""
 
     def __init__(self, model, plan, channels, batch=8):
-        from . import graph as G
-        from .graphs import GraphedEval
         self.model, self.plan = model, plan
         dev = torch.device("cuda", torch.cuda.current_device())
         self._ids = _chunk_ids(plan, batch, dev)
@@ -532,14 +530,7 @@ class TiledPredictor:
             self._tuple = _tiled_chunk(model, xs, plan, ids, self._canvases, self._tiles)
             return ()
 
-        was_training = model.training
-        model.eval()
-        try:
-            with torch.no_grad():
-                chunk(x3, self._ids[0])           # eager once: allocations, pack entries, the canvases
-            self._ge = GraphedEval(chunk, [x3, self._ids[0]], pack_cache=G.pack_cache_of(model))
-        finally:
-            model.train(was_training)
+        self._ge = _capture(chunk, [x3, self._ids[0]], model)
 
     @torch.no_grad()
     def _run(self, x, mask):
@@ -652,16 +643,10 @@ def _predict_tta(model, x, views, mode, batch, entropy, mask):
         raise ValueError(f"batch must be >= 1 or None, got {batch}")
     x = _tta_input(x)
     models = _tta_models(model)
-    flags = [(m, m.training) for m in models if isinstance(m, torch.nn.Module)]
-    for m, _ in flags:
-        m.eval()
-    try:
+    with _eval_mode(models):
         accs = []
         two = _tta_accumulate(models, x, elements, mode, batch, accs)
         return _tta_finish(accs, len(elements) * len(models), mode, mask, entropy, two)
-    finally:
-        for m, was_training in flags:
-            m.train(was_training)
 
 
 def predict_logits_tta(model, x, views="d4", mode="prob", batch=None, entropy=False):
@@ -700,9 +685,7 @@ class TTAPredictor:
     `model` may be a list of models (an ensemble)."""
 
     def __init__(self, model, example_x, views="d4", mode="prob", batch=None):
-        from . import graph as G
         from . import tta as T
-        from .graphs import GraphedEval
         self.model, self.views, self.mode, self.batch = model, T.view_set(views), mode, batch
         T.check_mode(mode)
         models = _tta_models(model)
@@ -717,17 +700,7 @@ class TTAPredictor:
             return ()
 
         self._count = len(self.views) * len(models)
-        flags = [(m, m.training) for m in models if isinstance(m, torch.nn.Module)]
-        for m, _ in flags:
-            m.eval()
-        try:
-            with torch.no_grad():
-                fwd(x)                            # eager once: allocations, pack entries, the sums
-            caches = [G.pack_cache_of(m) for m, _ in flags]
-            self._ge = GraphedEval(fwd, [x], pack_cache=caches)
-        finally:
-            for m, was_training in flags:
-                m.train(was_training)
+        self._ge = _capture(fwd, [x], models)
 
     @torch.no_grad()
     def _run(self, x, entropy, mask):
@@ -766,26 +739,18 @@ def score_binary_masks(mask, gt_dots, sigma_list, sigma_thresh_list, dist_thresh
                          f"{tuple(gt_dots.shape)}")
     ops._need_cuda(mask, gt_dots)
     N, H, W = mask.shape
-    _, counts, area, sum_y, sum_x = label_components(mask)
-    cc_fault = M._fault_word(ops.workspace(4, mask.device))
+    _, counts, area, sum_y, sum_x, cc_fault = label_components(mask, _fault=True)
     centers = M.component_centers(counts, area, sum_y, sum_x)
     dots, g_count, dot_fault = M.dot_lists(gt_dots, _fault=True)
     crowd = M.crowd_match(dots, g_count, centers, counts, sigma_list, sigma_thresh_list)
     dist = M.distance_match(dots, g_count, centers, counts, dist_thresh)
-    cells_gt = M.grid_sums(gt_dots, size)
+    cells_gt = M.grid_sums(gt_dots, size).to(torch.int64)           # sums of a 0/1 map: exact in either type
     cells_pred = M.grid_sums(M.scatter_centers(centers, counts, H, W), size)
-    back = torch.cat([t.reshape(-1).to(torch.int64) for t in (cc_fault, dot_fault, counts, g_count, crowd, dist, cells_gt,
-                                                              cells_pred)]).cpu().numpy()
-    if back[0]:
-        raise RuntimeError(f"score_binary_masks: the union-find reported fault {back[0]}; the results are invalid")
-    M.raise_on_dot_overflow(back[1])
-    parts, at = [], 2
-    for n_el in (N, N, crowd.numel(), dist.numel(), N * 64, N * 64):
-        parts.append(back[at:at + n_el])
-        at += n_el
-    counts_h, g_h = parts[0], parts[1]
-    crowd_h, dist_h = parts[2].reshape(crowd.shape), parts[3].reshape(N, 3)
-    cg, cp = parts[4].reshape(N, 8, 8), parts[5].reshape(N, 8, 8)
+    cc_code, dot_code, counts_h, g_h, crowd_h, dist_h, cg, cp = ops.read_back(cc_fault, dot_fault, counts, g_count, crowd, dist,
+                                                                              cells_gt, cells_pred)
+    if cc_code[0]:
+        raise RuntimeError(f"score_binary_masks: the union-find reported fault {cc_code[0]}; the results are invalid")
+    M.raise_on_dot_overflow(dot_code[0])
     out = []
     for n in range(N):
         gt, pred = int(g_h[n]), int(counts_h[n])
@@ -826,8 +791,8 @@ def _class_component_mask(mask, n_classes):
     return m, N, H, W, K, nbytes
 
 
-def _label_class_components(mask, n_classes, max_components):
-    """label_class_components' seven outputs and the int32 view of the kernels' fault word."""
+def _label_class_components(mask, n_classes, max_components, _fault=True):
+    """label_class_components' seven outputs and the kernels' fault word (ops.fault_word: a tensor of its own; None without _fault)."""
     from .components import class_components_cap
     m, N, H, W, K, nbytes = _class_component_mask(mask, n_classes)
     cap = class_components_cap(H, W, K) if max_components is None else int(max_components)
@@ -846,7 +811,7 @@ def _label_class_components(mask, n_classes, max_components):
            label_class.data_ptr(), area.data_ptr(), sum_y.data_ptr(), sum_x.data_ptr(), N, H, W, K,
            cap, ws.data_ptr(), nbytes, ops._stream())
     return ((labels[0] if mask.dim() == 2 else labels), counts, class_counts, label_class, area, sum_y, sum_x), \
-        ws[:4].view(torch.int32)
+        (ops.fault_word(ws) if _fault else None)
 
 
 def label_class_components(mask, n_classes, max_components=None, check=False):
@@ -864,13 +829,13 @@ def label_class_components(mask, n_classes, max_components=None, check=False):
     >= n_classes is taken as background and sets another (the first of the two stays; a union-find fault overrides both).  check=True reads the fault word back (one synchronisation) and
     raises on either, and on a union-find fault.  With n_classes = 2 and the default cap, labels, counts, area and the sums
     are label_components' bit for bit on a 0/1 mask."""
-    outs, fault = _label_class_components(mask, n_classes, max_components)
+    outs, fault = _label_class_components(mask, n_classes, max_components, _fault=check)
     if check:
-        _raise_on_class_fault(fault.item(), "label_class_components")
+        _raise_on_class_fault(fault, "label_class_components")
     return outs
 
 
-def count_class_objects(mask, n_classes, check=False):
+def count_class_objects(mask, n_classes, check=False, _fault=False):
     """Number of components per image and class, int32 (N, n_classes) on the device (column 0 is 0): label_class_components'
     `class_counts` without the flatten, rank, relabel and statistics passes."""
     m, N, H, W, K, nbytes = _class_component_mask(mask, n_classes)
@@ -878,9 +843,10 @@ def count_class_objects(mask, n_classes, check=False):
     ws = ops.workspace(nbytes, m.device)
     L.call("umi_count_class_components", m.data_ptr(), class_counts.data_ptr(), N, H, W, K, ws.data_ptr(), nbytes,
            ops._stream())
+    fault = ops.fault_word(ws) if check or _fault else None
     if check:
-        _raise_on_class_fault(ws[:4].view(torch.int32).item(), "count_class_objects")
-    return class_counts
+        _raise_on_class_fault(fault, "count_class_objects")
+    return (class_counts, fault) if _fault else class_counts
 
 
 def score_multiclass_masks(mask, gt_dots, n_classes, sigma_list, sigma_thresh_list, size=512, max_components=65536):
@@ -917,21 +883,15 @@ def score_multiclass_masks(mask, gt_dots, n_classes, sigma_list, sigma_thresh_li
     K = int(n_classes)
     cap = min(int(max_components), H * W)
     (_, counts, class_counts, label_class, area, sum_y, sum_x), cc_fault = _label_class_components(mask, K, cap)
-    cc_fault = cc_fault.clone()
     centers, c_count = M.class_center_lists(counts, label_class, area, sum_y, sum_x, K)
     planes = M.split_classes(gt_dots, K).view(N * (K - 1), H, W)
     dots, g_count, dot_fault = M.dot_lists(planes, _fault=True)
     crowd = M.crowd_match(dots, g_count, centers, c_count, sigma_list, sigma_thresh_list)
     cells_gt = M.grid_sums(planes, size)
     cells_pred = M.grid_sums(M.scatter_centers(centers, c_count, H, W), size)
-    parts = (cc_fault, dot_fault, class_counts, g_count, c_count, crowd, cells_gt, cells_pred)
-    back = torch.cat([t.reshape(-1).to(torch.int64) for t in parts]).cpu().numpy()
-    _raise_on_class_fault(back[0], "score_multiclass_masks")
-    M.raise_on_dot_overflow(back[1])
-    host, at = [], 2
-    for t in parts[2:]:
-        host.append(back[at:at + t.numel()].reshape(t.shape))
-        at += t.numel()
+    cc_code, dot_code, *host = ops.read_back(cc_fault, dot_fault, class_counts, g_count, c_count, crowd, cells_gt, cells_pred)
+    _raise_on_class_fault(cc_code[0], "score_multiclass_masks")
+    M.raise_on_dot_overflow(dot_code[0])
     return M.multiclass_scores(*host, K)
 
 
@@ -970,16 +930,9 @@ def score_density_maps(pred, gt_dots, sigma_list, sigma_thresh_list, size=512, m
     crowd = M.crowd_match(dots, g_count, peaks, p_count, sigma_list, sigma_thresh_list)
     cells_gt = M.grid_sums(gt_dots, size).to(torch.int64)           # sums of a 0/1 map: exact in either type
     cells_pred = M.grid_sums(pred, size)
-    parts = (peak_fault, dot_fault, g_count, p_count, crowd, cells_gt, counts, cells_pred)
-    back = torch.cat([(t.view(torch.int64) if t.dtype == torch.float64 else t.to(torch.int64)).reshape(-1)
-                      for t in parts]).cpu().numpy()                  # float64 travels as its bits
-    P.raise_on_peak_fault(back[0])
-    M.raise_on_dot_overflow(back[1])
-    host, at = [], 2
-    for t in parts[2:]:
-        h = back[at:at + t.numel()]
-        host.append((h.view(np.float64) if t.dtype == torch.float64 else h).reshape(t.shape))
-        at += t.numel()
-    g_h, p_h, crowd_h, cg, cnt_h, cp = host
+    peak_code, dot_code, g_h, p_h, crowd_h, cg, cnt_h, cp = ops.read_back(peak_fault, dot_fault, g_count, p_count, crowd, cells_gt,
+                                                                          counts, cells_pred)
+    P.raise_on_peak_fault(peak_code[0])
+    M.raise_on_dot_overflow(dot_code[0])
     res = P.density_scores(g_h, cnt_h, p_h, crowd_h, cg, cp)
     return P.pair_scores(res[:n_first], res[n_first:]) if pair else res

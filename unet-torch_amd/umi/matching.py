@@ -337,11 +337,6 @@ def _dev_modules():
     return lib, ops
 
 
-def _fault_word(ws):
-    import torch
-    return ws[:4].view(torch.int32).clone()
-
-
 def raise_on_dot_overflow(code, max_dots=MAX_DOTS):
     if int(code):
         raise RuntimeError(f"dot_lists: an image has more than max_dots = {max_dots} dots; its list was cut short")
@@ -370,9 +365,10 @@ def dot_lists(dot_map, max_dots=MAX_DOTS, check=False, _fault=False):
     ws = ops.workspace(nbytes, m.device)
     L.call("umi_dot_lists", m.data_ptr(), 0 if m.dtype == torch.uint8 else 1, dots.data_ptr(), g_count.data_ptr(), N, H, W,
            max_dots, ws.data_ptr(), nbytes, ops._stream())
+    fault = ops.fault_word(ws) if check or _fault else None
     if check:
-        raise_on_dot_overflow(ws[:4].view(torch.int32).item(), max_dots)
-    return (dots, g_count, _fault_word(ws)) if _fault else (dots, g_count)
+        raise_on_dot_overflow(fault, max_dots)
+    return (dots, g_count, fault) if _fault else (dots, g_count)
 
 
 def component_centers(counts, area, sum_y, sum_x):

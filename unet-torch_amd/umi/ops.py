@@ -551,6 +551,29 @@ def workspace(nbytes, device):
     return buf
 
 
+def fault_word(ws):
+    """The int32 status word a kernel left in the first 4 bytes of its workspace `ws`, as a tensor of its own.  The function that
+    launched the kernel calls this right after its own `L.call`: the workspace is shared, the next op may overwrite the word."""
+    return ws[:4].view(torch.int32).clone()
+
+
+_READ_BACK = {torch.int32: np.int32, torch.int64: np.int64, torch.uint8: np.uint8, torch.float64: np.float64}
+
+
+def read_back(*tensors):
+    """The int32 / int64 / uint8 / float64 tensors as NumPy arrays of their own shapes and dtypes, through ONE device-to-host
+    copy: they travel as their bytes in one concatenated buffer (so a float64 arrives with its bits), no cast is launched."""
+    for t in tensors:
+        if t.dtype not in _READ_BACK:
+            raise TypeError(f"read_back carries int32, int64, uint8 and float64 tensors, got {t.dtype}")
+    back = torch.cat([t.reshape(-1).view(torch.uint8) for t in tensors]).cpu().numpy()
+    out, at = [], 0
+    for t in tensors:
+        out.append(np.frombuffer(back, _READ_BACK[t.dtype], t.numel(), at).reshape(t.shape))
+        at += t.numel() * t.element_size()
+    return out
+
+
 def conv_dgrad_bnred(dy, wp8, da, ybn, txbn, rstd):
     """3x3 data gradient da <- conv(dy, rotated weights) that also emits stage 1 of the BatchNorm backward reduction of the
     layer whose raw output is `ybn` (the layer `da` belongs to).  Returns the partial-sum tensor, or None when the shape

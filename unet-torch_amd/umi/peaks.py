@@ -203,7 +203,7 @@ def peak_lists(maps, min_distance=3, floor=1e-3, max_peaks=MAX_PEAKS, check=Fals
     max_peaks and sets the kernels' fault word; check=True reads that word back (one synchronisation) and raises.  `vmin`:
     density_maps' per-image minimum of the same maps (saves the kernels' own pass over them).  NumPy input runs
     peak_lists_numpy (and raises on overflow when check=True)."""
-    from .matching import _dev_modules, _fault_word, _is_dev, _to_np
+    from .matching import _dev_modules, _is_dev, _to_np
     if not _is_dev(maps):
         peaks, p_count, fault = peak_lists_numpy(_to_np(maps), min_distance, floor, max_peaks)
         if check:
@@ -224,9 +224,10 @@ def peak_lists(maps, min_distance=3, floor=1e-3, max_peaks=MAX_PEAKS, check=Fals
     ws = ops.workspace(nbytes, m.device)
     L.call("umi_peak_lists", m.data_ptr(), None if vmin is None else vmin.data_ptr(), peaks.data_ptr(), p_count.data_ptr(),
            N, H, W, d, float(fl), max_peaks, ws.data_ptr(), nbytes, ops._stream())
+    fault = ops.fault_word(ws) if check or _fault else None
     if check:
-        raise_on_peak_fault(ws[:4].view(torch.int32).item(), max_peaks)
-    return (peaks, p_count, _fault_word(ws)) if _fault else (peaks, p_count)
+        raise_on_peak_fault(fault, max_peaks)
+    return (peaks, p_count, fault) if _fault else (peaks, p_count)
 
 
 def _density(x, scale, with_map):
