@@ -892,6 +892,42 @@ size_t umi_augment_znorm_ws_bytes(int N);
 int umi_augment_znorm(const void* src, int dtype, float* out_nchw, const int* params, const double* geom, int N, int H, int W, int C,
                       int reverse_channels, void* ws, size_t ws_bytes, umi_stream_t stream);
 
+/* Random-crop training batches and padded tile grids (csrc/crops.hip; statement: umi/augment.py crop_transform_numpy and
+ * grid_transform_numpy): the reference's DataRandomCrop, train and validation, cut out of images that stay on the device.
+ * A POOL is one device buffer of images of different sizes but one channel count and type (dtype 0 = uint8, 1 = float32, C <= 4):
+ * offsets[n_images] (int64) = the element offset of each image, sizes[n_images][2] (int32) = {H, W}, pool_elems = the buffer's
+ * length in elements.  Label and dot maps are pools of their own (C = 1).  All tables are on the device and read there; nothing
+ * synchronises with the host; no atomics: two runs give the same bits.
+ *   umi_crop_znorm: crops[N][3] = {index, r0, c0} (int32), params[N][4] and geom[N][6] as for umi_augment_* with H = W = crop
+ *     -> out[N][C][crop][crop] float32 = (augmented crop - mean) / std per (crop, channel) as umi_augment_znorm forms them.  The
+ *     geometry acts on the crop window: a rotation brings in 0, not the neighbouring image pixels.  N <= 65535.
+ *     ws: umi_crop_znorm_ws_bytes(N) bytes.
+ *   umi_crop_labels: the same gather for a map pool -> dst[N][crop][crop]; dst_dtype 0 = float32 ((float)v * scale), 1 = int64
+ *     (that product truncated), 2 = uint8 (the value as it is; uint8 pools only).
+ *   A crop row whose index is outside [0, n_images), whose window leaves its image, or whose image leaves the buffer, comes out
+ *   all 0 and reads nothing: no value of any table can form an address outside its image.
+ *   umi_grid_znorm: ONE image src[H][W][C], thought padded with the constant pad_value (0 .. 255) to [Hp][Wp] with the source at
+ *     (pad_top, pad_left); Hp % th == 0, Wp % tw == 0 -> out[T][C][th][tw] float32, the row-major th x tw tiles of
+ *     (padded - mean) / std, with the statistics of the WHOLE padded image: the source's sums plus the closed-form pad terms
+ *     (uint8: exact integers; float32: two float64 passes, the pad term added last).  The padded image is never written.
+ *     th = Hp, tw = Wp gives the padded image itself.  T <= 65535, Hp * Wp < 2^31.  ws: umi_grid_znorm_ws_bytes() bytes.
+ *   umi_grid_labels: the same tiles of a map src[H][W], padded with 0; dst_dtype as umi_crop_labels.
+ * Exactness bound of the uint8 statistics: std = sqrt(n * S2 - S1 * S1) / n in unsigned 64-bit integers is exact while
+ * (255 * n)^2 < 2^64, i.e. for n <= 16,843,009 pixels (n = crop * crop, or Hp * Wp; 4096 x 4096 fits).  Beyond it the uint8 forms
+ * return UMI_ERR_UNSUPPORTED and launch nothing. */
+size_t umi_crop_znorm_ws_bytes(int N);
+int umi_crop_znorm(const void* pool, int dtype, const long long* offsets, const int* sizes, int n_images, long long pool_elems, int C,
+                   const int* crops, const int* params, const double* geom, int N, int crop, float* out_nchw, int reverse_channels,
+                   void* ws, size_t ws_bytes, umi_stream_t stream);
+int umi_crop_labels(const void* pool, int src_dtype, const long long* offsets, const int* sizes, int n_images, long long pool_elems,
+                    const int* crops, const int* params, const double* geom, int N, int crop, void* dst, int dst_dtype, float scale,
+                    umi_stream_t stream);
+size_t umi_grid_znorm_ws_bytes(void);
+int umi_grid_znorm(const void* src, int dtype, int H, int W, int C, int pad_top, int pad_left, int pad_value, int Hp, int Wp, int th,
+                   int tw, float* out, int reverse_channels, void* ws, size_t ws_bytes, umi_stream_t stream);
+int umi_grid_labels(const void* src, int src_dtype, int H, int W, int pad_top, int pad_left, int Hp, int Wp, int th, int tw, void* dst,
+                    int dst_dtype, float scale, umi_stream_t stream);
+
 /* Hard-mask segmentation metrics (csrc/seg_metrics.hip; statement: umi/metrics.py): an exact integer confusion matrix per item
  * and Dice / IoU / pixel error from it.  `items` consecutive groups of n images; target [items*n][HW] with target_dtype as
  * umi_dice_ce_fwd (0 = int64, 1 = float32, 2 = uint8, 3 = int32).

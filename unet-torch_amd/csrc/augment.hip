@@ -18,53 +18,11 @@
 // All three are gathers: one thread per output pixel, 64 x 4 pixel tiles so that a wave stores one contiguous row segment and
 // the source pixels of a tile (a slanted strip for a rotation, a column strip for an odd k) stay close in L2.
 #include <type_traits>
-#include "common.h"
+#include "augment_gather.h"             // AgSample, ag_load, ag_src, ag_block_sum, the tile constants
 #include "zoom_nearest_rule.h"
 
 #pragma clang fp contract(off)
 namespace {
-
-constexpr int AG_MAXC = 4;
-constexpr int AG_TX = 64, AG_TY = 4;                     // workgroup = 64 x 4 output pixels
-constexpr int AG_STAT_BLOCKS = 64;                       // partial sums per sample
-
-struct AgSample {
-    int mode, k, axis;
-    double m00, m01, m10, m11, o0, o1;
-};
-
-__device__ inline AgSample ag_load(const int* __restrict__ params, const double* __restrict__ geom, int n) {
-    AgSample s;
-    s.mode = params[n * 4 + 0];
-    s.k = params[n * 4 + 1] & 3;
-    s.axis = params[n * 4 + 2] & 1;
-    const double* g = geom + (long)n * 6;
-    s.m00 = g[0]; s.m01 = g[1]; s.m10 = g[2]; s.m11 = g[3]; s.o0 = g[4]; s.o1 = g[5];
-    return s;
-}
-
-// pixel index y * W + x of the source of output pixel (r, q), 0 <= r < H, 0 <= q < W; -1 where the output is 0.  Every index
-// returned lies in [0, H * W): nothing read from `params` or `geom` can form an address outside the sample.
-__device__ inline int ag_src(const AgSample& s, int r, int q, int H, int W) {
-    if (s.mode == 1) {
-        if ((s.k & 1) && H != W) return -1;
-        const int i = s.axis == 0 ? H - 1 - r : r;       // undo the flip: (i, j) indexes rot90(x, k)
-        const int j = s.axis == 1 ? W - 1 - q : q;
-        switch (s.k) {                                   // rot90(x, 1)[i][j] = x[j][W - 1 - i], counter-clockwise
-            case 0: return i * W + j;
-            case 1: return j * W + (W - 1 - i);
-            case 2: return (H - 1 - i) * W + (W - 1 - j);
-            default: return (H - 1 - j) * W + i;
-        }
-    }
-    if (s.mode == 2) {
-        const double y = (s.o0 + (double)r * s.m00) + (double)q * s.m01;
-        const double x = (s.o1 + (double)r * s.m10) + (double)q * s.m11;
-        if (!(y >= 0.0 && y <= (double)(H - 1) && x >= 0.0 && x <= (double)(W - 1))) return -1;     // NaN: outside
-        return (int)floor(y + 0.5) * W + (int)floor(x + 0.5);
-    }
-    return r * W + q;
-}
 
 template <typename T>
 __global__ __launch_bounds__(AG_TX * AG_TY) void ag_geometry_kernel(const T* __restrict__ src, T* __restrict__ dst,
@@ -99,20 +57,8 @@ __global__ __launch_bounds__(AG_TX * AG_TY) void ag_labels_kernel(const T* __res
 //        (n * S2 and S1 * S1 stay below 2^63 for n <= 2^23 pixels).
 // float32: float64 sum -> mean, then the float64 sum of (v - mean)^2 (two passes, as numpy.std: survives |mean| >> std).
 // Partial sums: AG_STAT_BLOCKS slices per sample, threads striding a slice, wave shuffle then LDS in wave order; the finish
-// kernel adds the slices in index order.  ws: stats[N][2][AG_MAXC] float64 (mean, std), then part[N][AG_STAT_BLOCKS][2][AG_MAXC].
-template <typename V>
-__device__ inline V ag_block_sum(V v, V* sh) {
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    __syncthreads();
-    if (lane == 0) sh[w] = v;
-    __syncthreads();
-    V r = 0;
-    if (threadIdx.x == 0)
-        for (int i = 0; i < (int)(blockDim.x >> 6); ++i) r += sh[i];
-    return r;                                            // valid in thread 0
-}
-
+// kernel (ag_stats_finish_kernel, augment_gather.h) adds the slices in index order.
+// ws: stats[N][2][AG_MAXC] float64 (mean, std), then part[N][AG_STAT_BLOCKS][2][AG_MAXC].
 // PASS 0: uint8 -> S1, S2; float -> sum.  PASS 1 (float only): sum of squared deviations from stats' mean.
 template <typename T, int PASS>
 __global__ __launch_bounds__(256) void ag_stats_kernel(const T* __restrict__ src, const int* __restrict__ params,
@@ -153,30 +99,6 @@ __global__ __launch_bounds__(256) void ag_stats_kernel(const T* __restrict__ src
             if (threadIdx.x == 0) part[AG_MAXC + c] = t2;
         }
     }
-}
-
-// one thread per (sample, channel): the slices in index order
-template <typename T, int PASS>
-__global__ __launch_bounds__(64) void ag_stats_finish_kernel(const void* __restrict__ part_, int N, int HW, int C,
-                                                             double* __restrict__ stats) {
-    constexpr bool U8 = sizeof(T) == 1;
-    typedef typename std::conditional<U8, unsigned long long, double>::type V;
-    const int t = blockIdx.x * 64 + threadIdx.x;
-    if (t >= N * C) return;
-    const int n = t / C, c = t - n * C;
-    const V* part = (const V*)part_ + (long)n * AG_STAT_BLOCKS * 2 * AG_MAXC;
-    V s1 = 0, s2 = 0;
-    for (int b = 0; b < AG_STAT_BLOCKS; ++b) {
-        s1 += part[(long)b * 2 * AG_MAXC + c];
-        if (U8) s2 += part[(long)b * 2 * AG_MAXC + AG_MAXC + c];
-    }
-    double* st = stats + (long)n * 2 * AG_MAXC;
-    if (U8) {
-        const unsigned long long cnt = (unsigned long long)HW;
-        st[c] = (double)s1 / (double)HW;
-        st[AG_MAXC + c] = sqrt((double)(cnt * (unsigned long long)s2 - (unsigned long long)s1 * (unsigned long long)s1)) / (double)HW;
-    } else if (PASS == 0) st[c] = (double)s1 / (double)HW;
-    else st[AG_MAXC + c] = sqrt((double)s1 / (double)HW);
 }
 
 template <typename T>

@@ -144,6 +144,26 @@ def preprocess(img, reverse_channels=None, input_size=None):
     return out
 
 
+def preprocess_crop(img, crop_size):
+    """Reference `preprocessCrop` (test.py:91-128) for the image: HW / HWC (C <= 4) -> [1,C,Hp,Wp] fp32 with Hp, Wp the next
+    multiples of crop_size, the image centred (pad_top = padding_h // 2, pad_left = padding_w // 2) in a frame of 255,
+    z-normalised with the statistics of the whole padded image and channel-reversed like `preprocess`.  The padded image is
+    not materialised (umi.augment.grid_image); the result feeds predict_binary_mask_tiled / predict_logits_tiled."""
+    from . import augment
+    if isinstance(img, np.ndarray):
+        img = torch.from_numpy(np.ascontiguousarray(img))
+    if img.dtype not in (torch.uint8, torch.float32):
+        img = img.float()
+    img = img.to("cuda", non_blocking=True)
+    H, W = img.shape[:2]
+    crop_size = int(crop_size)
+    if crop_size < 1:
+        raise ValueError(f"crop_size {crop_size}")
+    Hp, Wp = H + (-H) % crop_size, W + (-W) % crop_size
+    top, left = augment.center_pad(H, W, crop_size)
+    return augment.grid_image(img, top, left, Hp, Wp, pad_value=255, padded=(Hp, Wp))
+
+
 def argmax_mask(logits):
     """[N,C,H,W] fp32 logits -> uint8 [N,H,W] class mask (== softmax(dim=1).argmax(dim=1), first maximum wins)."""
     ops._need_cuda(logits)
@@ -375,8 +395,8 @@ class GraphedPredictor:
 
 @torch.no_grad()
 def predict_binary_mask_tiled(model, x, crop_size):
-    """Reference test_single_crop (test.py:437-448): x (1,C,Hp,Wp) with Hp and Wp multiples of crop_size (padding the image
-    with 255 before `preprocess`, test.py:91-119, stays with the caller); every crop_size tile goes through the network on its
+    """Reference test_single_crop (test.py:437-448): x (1,C,Hp,Wp) with Hp and Wp multiples of crop_size (`preprocess_crop`
+    above pads the image with 255 and normalises it, test.py:91-119); every crop_size tile goes through the network on its
     own, one tile per forward as the reference does, and its thresholded mask is placed into a uint8 (Hp,Wp) mask on the
     device.  Two-headed models give a tuple of masks."""
     crop_size = int(crop_size)
