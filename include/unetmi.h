@@ -693,6 +693,22 @@ size_t umi_fingerprint_ws_bytes(int total_blocks);
 int umi_fingerprint_multi(const void* descs, int n_desc, int total_blocks, void* ws, size_t ws_bytes, unsigned long long* out,
                           umi_stream_t stream);
 
+/* State snapshot (checkpoints, best-model copies, in-place roll-back): every tensor of a umi_optim_desc table copied into one
+ * contiguous device arena in one pass, and back.  The fields mean: `p` the tensor (any alignment of 4 bytes), `s0` its slot in
+ * the arena (16-byte aligned), `n` its length in 32-bit words, `blk0` as for the optimizer; `g` and `s1` are not read.
+ *   umi_snapshot_multi  copies words p -> s0 and writes zeros into the words between n and 4 * ceil(n / 4), the length of a
+ *                       slot, so the arena's bytes are a function of the tensors alone; leaves in *out the word F that
+ *                       umi_fingerprint_multi gives on the same table, formed from the words as they are copied (the state is
+ *                       read once).  `ws`, `out` and their statuses as for umi_fingerprint_multi
+ *                       (umi_snapshot_ws_bytes(total_blocks) bytes).  Two launches: the copy with its block partials, the
+ *                       finalize pass.  No atomics.
+ *   umi_restore_multi   copies words s0 -> p, exactly n per tensor and nothing past them.  One launch; none when
+ *                       total_blocks == 0. */
+size_t umi_snapshot_ws_bytes(int total_blocks);
+int umi_snapshot_multi(const void* descs, int n_desc, int total_blocks, void* ws, size_t ws_bytes, unsigned long long* out,
+                       umi_stream_t stream);
+int umi_restore_multi(const void* descs, int n_desc, int total_blocks, umi_stream_t stream);
+
 /* umi_pack_kn / umi_pack_kn8 of many weight tensors in one launch (all the convolution weights of a model after an
  * optimizer step).  `descs`: DEVICE array sorted by blk0; an entry owns ceil(T*Kpad*Npad / umi_pack_block_elems()) blocks. */
 typedef struct umi_pack_desc {

@@ -93,6 +93,33 @@ synchronises: a group whose first, eager run took that route is never captured a
 (`_eval_host`, decided by `loss.surface_host_calls()`), with the same scores, at the host's speed.  As `loss_function` they raise
 ValueError.  With `val_confusion=True` the
 confusion matrices take their own pass next to it.
+`Trainer(..., async_checkpoints=True)` (keyword-only; singe_train / multi_task_train with the model on the device, otherwise
+ignored): `last_epoch.pt`, `epochN.pt` and `best.pt` come from a `umi.snapshot.Snapshot` of `model.state_dict()` -- the training
+stream pays one take() (umi_snapshot_multi: one copy pass into a contiguous arena) per epoch, the device-to-host copy runs on a
+side stream and one `umi.snapshot.CheckpointWriter` thread writes the files (`.tmp`, then `os.replace`) beside the next epoch.
+`best_model` becomes the views of a second arena (one launch instead of a deepcopy).  train() joins the writer before it
+returns, also when it raises, and a write that failed is raised there.  The files hold what the synchronous path writes: same
+keys, order, dtypes, shapes and values, every tensor in its own storage (CPU tensors; load with `map_location`).
+`Trainer(..., resume=True | path)` (keyword-only; True = `<output_save_dir>/run_state.pt`): after every epoch's validation phase
+rank 0 writes the RUN STATE atomically (through the writer when checkpoints are asynchronous): one dict that
+`torch.load(weights_only=True)` accepts, with a format number, the epoch just finished and whether the run is over (the last
+epoch, or an early stop), the model's state_dict, `optimizer.state_dict()` and the raw bytes of its device hyper blocks, the
+GradGuard block, the dropout bases and counters, `best_model`, and under 'host' iter_num, max_iterations, the best scores, the
+early-stop counter, every per-epoch list, `val_confusion_list`, `_guard_seen`, and the states of torch's CPU generator, the CUDA
+generator of the model's device, Python's `random`, NumPy's global generator and each `dataloaders[phase].generator`.  'word' is
+the fingerprint (umi.ddp) of all its state tensors in file order -- the word of the arena they were copied through --,
+'host_word' that of the host fields.  At train(), if the file exists, it is checked first -- state-dict keys, shapes and dtypes,
+optimizer class and group count, max_iterations, both words recomputed; ValueError or RuntimeError before anything is modified
+-- then everything is put back, the generator states last, and the loop continues at the next epoch, or goes straight to its end
+if the run was over; no file: a fresh run.  A run cut after any epoch and resumed with new objects, in a new process, gives the
+lists, files, weights and optimizer state of the run that was never cut, bit for bit (eager and graph=True, fp32 and fp16, SGD
+and Adam on the device poly rule, dropout, a moved dynamic loss scale, multi-task).  Refused with NotImplementedError before the
+first step: `resume` with 'multi_task_loss_ratio' (its alpha and gate bookkeeping is its own) and with `data_parallel` over more
+than one rank (per-rank generator states are not collected; a world of one works).  `snapshot_run_state()` /
+`restore_run_state()` do the same in memory and IN PLACE between steps of a live run (the roll-back after a diverged epoch):
+one Snapshot over parameters, buffers, optimizer state, hyper blocks, guard block and dropout counters, the host fields and
+generator states beside it; every tensor keeps its address, so under graph=True no graph is captured again, and the parameter
+versions are bumped, so the kernel-layout weight copies are re-packed.  With both arguments at their defaults none of this runs.
 `lr_scheduler=True` (what the reference's train.py passes) crashes the reference in its first validation after epoch 5
 (`True.step`); here train() raises NotImplementedError before the first step whenever the run would reach that point.
 The remaining epoch loops of the reference (uncertainty-weighted multi-task, CLTR, Topo losses) are out of scope and raise.
@@ -119,7 +146,8 @@ _OTHER = ('CLTR',)
 class Trainer():
     def __init__(self, model, model_type, dtype, device, output_save_dir, dataloaders, batch_size, optimizer,
                  patience, num_epochs, loss_function, accuracy_metric, lr_scheduler=None, start_epoch=1, *, graph=None,
-                 batch_transform=None, grad_guard=None, data_parallel=None, val_batch=None, val_confusion=False):
+                 batch_transform=None, grad_guard=None, data_parallel=None, val_batch=None, val_confusion=False,
+                 async_checkpoints=False, resume=None):
         self.model = model
         self.model_type = model_type
         self.dtype = dtype
@@ -177,6 +205,18 @@ class Trainer():
             raise ValueError(f"val_confusion covers the single-output model types {_SINGLE}, not {model_type!r}")
         self.val_confusion = bool(val_confusion)
         self.val_confusion_list, self.val_class_scores, self._val_conf = [], None, None
+
+        # snapshots (see the module docstring): checkpoints through a device arena and a writer thread; the run-state file; the
+        # in-memory roll-back.  All None / off by default: nothing below runs then.
+        self.async_checkpoints = bool(async_checkpoints)
+        if resume is None or resume is False:
+            self._resume_path = None
+        elif resume is True:
+            self._resume_path = os.path.join(self.output_save_dir, 'run_state.pt')
+        else:
+            self._resume_path = os.fspath(resume)
+        self._writer, self._ckpt_snap, self._best_snap, self._file_snap, self._run_snap = None, None, None, None, None
+        self._run_host, self._total_time, self._best_views, self._ckpt_event = None, 0.0, False, None
 
         self.save_dir_model = os.path.join(self.output_save_dir, 'models/')
         os.makedirs(self.save_dir_model, exist_ok=True)
@@ -314,8 +354,352 @@ class Trainer():
         dist.all_reduce(vec, op=dist.ReduceOp.SUM, group=self._dp.group)
         return vec.tolist()
 
+    # ---- snapshots: asynchronous checkpoints, the run-state file, in-place roll-back ------------------------------------------
+    _LISTS = ('train_loss_list', 'val_loss_list', 'val_score_list', 'train_loss_list_1', 'train_loss_list_2', 'val_loss_list_1',
+              'val_loss_list_2', 'alpha_list')
+    RUN_STATE_FORMAT = 1
+
+    def _resume_refusals(self):
+        """Before anything runs: what `resume` does not cover."""
+        if self._resume_path is None:
+            return
+        if self._ratio_loop():
+            raise NotImplementedError("resume with multi_task_loss_ratio: the loop's alpha and gate bookkeeping is its own and is "
+                                      "not part of the run state")
+        spec, world = self._dp_spec, 1
+        if spec is not None:
+            import torch.distributed as dist
+            if isinstance(spec, dict):
+                world = spec.get("world_size")
+            elif hasattr(spec, "world"):
+                world = spec.world
+            else:
+                world = None
+            if world is None:
+                world = dist.get_world_size() if dist.is_available() and dist.is_initialized() else 1
+        if world > 1:
+            raise NotImplementedError("resume with data_parallel over more than one rank: the per-rank random-generator states "
+                                      "are not collected (a world of one works)")
+
+    def _ckpt_async(self):
+        return self.async_checkpoints and self._dp_device().type == "cuda"
+
+    def _writer_get(self):
+        if self._writer is None:
+            from umi.snapshot import CheckpointWriter
+            self._writer = CheckpointWriter()
+        return self._writer
+
+    def _writer_close(self):
+        w, self._writer = self._writer, None
+        if w is not None:
+            w.close()
+
+    def _snap_for(self, slot, tensors):
+        """The Snapshot kept in attribute `slot` for exactly these live tensors (built again when one of them moved)."""
+        from umi.snapshot import Snapshot
+        key = tuple((k, v.data_ptr(), v.numel() * v.element_size()) for k, v in tensors.items())
+        have = getattr(self, slot)
+        if have is None or have[0] != key:
+            have = (key, Snapshot(tensors))
+            setattr(self, slot, have)
+        return have[1]
+
+    def _submit(self, snap, event, obj, path):
+        self._writer_get().submit(event, obj, path, snap.hold_host())
+
+    def _save_last(self, path):
+        """'last_epoch.pt' after a training phase: one take() on the training stream; the copy to the host and the write run
+        beside what follows."""
+        snap = self._snap_for('_ckpt_snap', self.model.state_dict())
+        snap.take()
+        self._ckpt_event = snap.to_host_async()
+        self._submit(snap, self._ckpt_event, snap.host_views(), path)
+
+    def _save_best(self, paths):
+        """A new best model: `best_model` becomes the views of a second arena (one launch instead of a deepcopy); the files come
+        from the host copy that 'last_epoch.pt' of this epoch was taken from (a validation phase changes no weight or buffer)."""
+        best = self._snap_for('_best_snap', self.model.state_dict())
+        best.take()
+        self.best_model, self._best_views = best.views(), True
+        snap = self._ckpt_snap[1] if self._ckpt_snap is not None else None
+        for path in paths:
+            self._submit(snap, self._ckpt_event, snap.host_views(), path)
+
+    def _state_tensors(self, best=True):
+        """name -> live tensor of everything a step reads or writes that lives in tensors: parameters and buffers, the optimizer's
+        momentum buffers or moments, its device hyper blocks, the guard block, the dropout counters, and (`best`) the best model."""
+        import collections
+        out = collections.OrderedDict()
+        for k, v in self.model.state_dict().items():
+            out['model.' + k] = v
+        idx = 0
+        for group in self.optimizer.param_groups:
+            for p in group['params']:
+                if p in self.optimizer.state:
+                    for k, v in self.optimizer.state[p].items():
+                        if torch.is_tensor(v) and k != 'step':         # Adam's step count is a host scalar (see _host_fields)
+                            out[f'optim.{idx}.{k}'] = v
+                idx += 1
+        for gi, (dev, _) in enumerate(getattr(self.optimizer, 'device_hyper', None) or []):
+            out[f'hyper.{gi}'] = dev
+        if self._guard is not None and self._guard.state is not None:
+            out['guard'] = self._guard.state
+        for name, m in self.model.named_modules():
+            if getattr(m, '_drop_step', None) is not None:
+                out['drop.' + name] = m._drop_step
+        if best and isinstance(self.best_model, dict):
+            for k, v in self.best_model.items():
+                out['best.' + k] = v
+        return out
+
+    def _rng_get(self):
+        import random
+        dev = self._dp_device()
+        kind, keys, pos, has_gauss, cached = np.random.get_state()
+        loaders = {ph: dl.generator.get_state() for ph, dl in self.dataloader.items()
+                   if isinstance(getattr(dl, 'generator', None), torch.Generator)}
+        return dict(torch_cpu=torch.get_rng_state(), torch_cuda=torch.cuda.get_rng_state(dev) if dev.type == 'cuda' else None,
+                    python=random.getstate(), loaders=loaders,
+                    numpy=(str(kind), torch.from_numpy(keys.astype(np.int64)), int(pos), int(has_gauss), float(cached)))
+
+    def _rng_set(self, rng):
+        import random
+        for ph, st in rng['loaders'].items():
+            gen = getattr(self.dataloader.get(ph), 'generator', None)
+            if isinstance(gen, torch.Generator):
+                gen.set_state(st)
+        kind, keys, pos, has_gauss, cached = rng['numpy']
+        np.random.set_state((kind, keys.numpy().astype(np.uint32), pos, has_gauss, cached))
+        version, words, gauss = rng['python']
+        random.setstate((version, tuple(words), gauss))
+        if rng['torch_cuda'] is not None:
+            torch.cuda.set_rng_state(rng['torch_cuda'], self._dp_device())
+        torch.set_rng_state(rng['torch_cpu'])
+
+    def _host_fields(self):
+        """Everything of the run that lives on the host, as values torch.load(weights_only=True) accepts."""
+        groups = [{k: v for k, v in g.items() if k != 'params'} for g in self.optimizer.param_groups]
+        steps, idx = {}, 0
+        for g in self.optimizer.param_groups:
+            for p in g['params']:
+                st = self.optimizer.state[p] if p in self.optimizer.state else {}
+                if 'step' in st:
+                    steps[idx] = float(st['step'])
+                idx += 1
+        scores = self.val_class_scores
+        return dict(iter_num=self.iter_num, max_iterations=self.max_iterations, base_lr=self.base_lr,
+                    best_val_score=self.best_val_score, best_loss=self.best_loss, early_stop_counter=self.early_stop_counter,
+                    lists={n: list(getattr(self, n)) for n in self._LISTS}, alpha=self.alpha,
+                    val_confusion_list=[torch.from_numpy(np.array(m, dtype=np.int64)) for m in self.val_confusion_list],
+                    val_class_scores=None if scores is None else {k: torch.from_numpy(np.array(v, dtype=np.float64))
+                                                                  for k, v in scores.items()},
+                    guard_seen=tuple(self._guard_seen), total_time=float(self._total_time), groups=copy.deepcopy(groups),
+                    adam_steps=steps, drop_base={name: int(m._drop_base) for name, m in self.model.named_modules()
+                                                 if getattr(m, '_drop_base', None) is not None},
+                    rng=self._rng_get())
+
+    def _put_host(self, host):
+        """The host fields back, except the generators' states (_rng_set, which goes last)."""
+        self.iter_num, self.base_lr = host['iter_num'], host['base_lr']
+        self.best_val_score, self.best_loss = host['best_val_score'], host['best_loss']
+        self.early_stop_counter, self.alpha = host['early_stop_counter'], host['alpha']
+        for n in self._LISTS:
+            setattr(self, n, list(host['lists'][n]))
+        self.val_confusion_list = [m.numpy().copy() for m in host['val_confusion_list']]
+        scores = host['val_class_scores']
+        self.val_class_scores = None if scores is None else {k: v.numpy().copy() for k, v in scores.items()}
+        self._guard_seen, self._total_time = tuple(host['guard_seen']), host['total_time']
+
+    # -- in memory, in place ---------------------------------------------------------------
+    def snapshot_run_state(self):
+        """Between two steps of a live run: the whole training state into one device arena (one launch) plus the host fields
+        and generator states beside it.  restore_run_state() puts it back IN PLACE: every tensor keeps its address, so graphs
+        captured before stay valid and none is captured again."""
+        # a deepcopy'd best model is never written to again: the reference is enough.  The views of the asynchronous path show
+        # an arena that the next best model overwrites, so that arena is part of the snapshot
+        views = self._best_views and isinstance(self.best_model, dict)
+        snap = self._snap_for('_run_snap', self._state_tensors(best=views))
+        snap.take()
+        self._run_host = (self._host_fields(), self.best_model, views)
+        return snap
+
+    def restore_run_state(self):
+        if self._run_snap is None or self._run_host is None:
+            raise RuntimeError("restore_run_state() without a snapshot_run_state() before it")
+        (key, snap), (host, best, views) = self._run_snap, self._run_host
+        live = self._state_tensors(best=False)
+        if views:
+            live.update(('best.' + k, v) for k, v in best.items())
+        if tuple((k, v.data_ptr(), v.numel() * v.element_size()) for k, v in live.items()) != key:
+            raise RuntimeError("restore_run_state(): the state's tensors changed since the snapshot (a tensor moved, or optimizer "
+                               "state appeared); take the snapshot after the first step")
+        snap.restore()                         # verifies the arena first; bumps the parameter versions (weight re-pack)
+        self.best_model = best
+        self._put_host(host)
+        for g, saved in zip(self.optimizer.param_groups, host['groups']):
+            g.update(copy.deepcopy(saved))
+        idx = 0
+        for g in self.optimizer.param_groups:
+            for p in g['params']:
+                if idx in host['adam_steps']:
+                    self.optimizer.state[p]['step'].fill_(host['adam_steps'][idx])
+                idx += 1
+        self._rng_set(host['rng'])
+
+    # -- the file --------------------------------------------------------------------------
+    @staticmethod
+    def _payload_tensors(pl):
+        """name -> tensor of a run-state payload, in the order of _state_tensors: what the fingerprint word is taken over."""
+        import collections
+        out = collections.OrderedDict(('model.' + k, v) for k, v in pl['model'].items())
+        for idx in sorted(pl['optimizer']['state']):
+            for k, v in pl['optimizer']['state'][idx].items():
+                if torch.is_tensor(v) and k != 'step':
+                    out[f'optim.{idx}.{k}'] = v
+        for gi, h in enumerate(pl['hyper'] or []):
+            out[f'hyper.{gi}'] = h
+        if pl['guard'] is not None:
+            out['guard'] = pl['guard']
+        for name, step in pl['drop_step'].items():
+            out['drop.' + name] = step
+        for k, v in (pl['best_model'] or {}).items():
+            out['best.' + k] = v
+        return out
+
+    @staticmethod
+    def _host_word(host):
+        """One fingerprint word over the host fields: the tensors among them (bytes, zero-padded to whole words) and the text of
+        everything else."""
+        from umi.ddp import fingerprint_numpy
+        arrays = []
+
+        def walk(o):
+            if torch.is_tensor(o):
+                raw = o.detach().cpu().contiguous().reshape(-1).view(torch.uint8).numpy()
+                arrays.append(np.concatenate([raw, np.zeros(-raw.size % 4, dtype=np.uint8)]))
+                return 'T%d' % (len(arrays) - 1)
+            if isinstance(o, dict):
+                return [(repr(k), walk(v)) for k, v in o.items()]
+            if isinstance(o, (list, tuple)):
+                return [walk(v) for v in o]
+            return repr(o)
+        text = np.frombuffer(repr(walk(host)).encode(), dtype=np.uint8)
+        arrays.append(np.concatenate([text, np.zeros(-text.size % 4, dtype=np.uint8)]))
+        return fingerprint_numpy(arrays)
+
+    def _write_run_state(self, epoch, over):
+        """The run state after `epoch`'s validation phase -> the file, atomically; through the writer when checkpoints are
+        asynchronous, otherwise before this returns."""
+        import collections
+        from umi.snapshot import _own, save_atomic
+        live = self._state_tensors()
+        snap = self._snap_for('_file_snap', live)
+        snap.take()
+        event = snap.to_host_async()
+        views = snap.host_views()
+        osd = self.optimizer.state_dict()
+        for idx, st in osd['state'].items():
+            osd['state'][idx] = {k: views.get(f'optim.{idx}.{k}', v.detach().cpu() if torch.is_tensor(v) else v)
+                                 for k, v in st.items()}
+        take = lambda prefix: collections.OrderedDict((k[len(prefix):], v) for k, v in views.items() if k.startswith(prefix))
+        model = take('model.')
+        meta = getattr(self.model.state_dict(), '_metadata', None)
+        if meta is not None:
+            model._metadata = meta
+        host = self._host_fields()
+        pl = dict(format=self.RUN_STATE_FORMAT, epoch=int(epoch), over=bool(over), model=model, optimizer=osd,
+                  optimizer_class=type(self.optimizer).__name__, hyper=list(take('hyper.').values()) or None,
+                  guard=views.get('guard'), drop_step=dict(take('drop.')), best_model=take('best.') or None, host=host,
+                  word=snap.word(), host_word=self._host_word(host))
+        assert list(self._payload_tensors(pl)) == list(live)
+        if self._ckpt_async():
+            self._submit(snap, event, pl, self._resume_path)
+        else:
+            event.synchronize()
+            save_atomic(_own(pl), self._resume_path)
+
+    def _resume_from_file(self):
+        """None when there is no file; else the file is checked against this Trainer -- nothing is modified before every check
+        has passed -- and put back.  Returns (epoch finished, run over)."""
+        path = self._resume_path
+        if not os.path.exists(path):
+            return None
+        from umi import ddp
+        if self._graphs or self._eval_graphs:
+            raise RuntimeError("resume: this Trainer has captured graphs, which hold the addresses of the optimizer state a file "
+                               "would replace; resume with a new Trainer, or roll back in place with restore_run_state()")
+        try:
+            pl = torch.load(path, map_location='cpu', weights_only=True)
+            ok = isinstance(pl, dict) and pl.get('format') == self.RUN_STATE_FORMAT
+            tensors = self._payload_tensors(pl) if ok else None
+        except Exception as e:
+            raise ValueError(f"resume: {path} cannot be read as a run state ({type(e).__name__}: {e})") from e
+        if not ok:
+            raise ValueError(f"resume: {path} is not a run state of format {self.RUN_STATE_FORMAT}")
+        sd = self.model.state_dict()
+        if list(pl['model']) != list(sd):
+            raise ValueError(f"resume: the model of {path} has other state-dict keys than this model")
+        for k, v in sd.items():
+            if pl['model'][k].shape != v.shape or pl['model'][k].dtype != v.dtype:
+                raise ValueError(f"resume: {k} is {tuple(pl['model'][k].shape)} {pl['model'][k].dtype} in {path}, "
+                                 f"{tuple(v.shape)} {v.dtype} in this model")
+        if pl['optimizer_class'] != type(self.optimizer).__name__ or \
+                len(pl['optimizer']['param_groups']) != len(self.optimizer.param_groups):
+            raise ValueError(f"resume: {path} was written with {pl['optimizer_class']} over "
+                             f"{len(pl['optimizer']['param_groups'])} param groups, not {type(self.optimizer).__name__} over "
+                             f"{len(self.optimizer.param_groups)}")
+        host = pl['host']
+        if host['max_iterations'] != self.max_iterations:
+            raise ValueError(f"resume: {path} belongs to a run of {host['max_iterations']} iterations, this one has "
+                             f"{self.max_iterations} (num_epochs or the training loader differ)")
+        if (pl['hyper'] or pl['guard'] is not None) and not hasattr(self.optimizer, 'device_schedule'):
+            raise ValueError(f"resume: {path} holds device optimizer blocks; this optimizer is not a umi.optim one")
+        if pl['guard'] is not None and self._guard is None:
+            raise ValueError(f"resume: {path} was written with a grad_guard, this Trainer has none")
+        dev = self._dp_device()
+        words = [t.to(dev) for t in tensors.values()]
+        for i, t in enumerate(words):
+            if (t.numel() * t.element_size()) % 4:
+                raise ValueError(f"resume: tensor {i} of {path} is not a whole number of 32-bit words")
+        if ddp.fingerprint(words) != pl['word'] or self._host_word(host) != pl['host_word']:
+            raise RuntimeError(f"resume: the contents of {path} do not match its fingerprint word; nothing was restored")
+        modules = dict(self.model.named_modules())
+        if any(name not in modules for name in list(pl['drop_step']) + list(host['drop_base'])):
+            raise ValueError(f"resume: {path} names dropout modules this model does not have")
+
+        # every check passed: put it back
+        self.model.load_state_dict(pl['model'])
+        self.optimizer.load_state_dict(pl['optimizer'])
+        self._put_host(host)
+        self.best_model, self._best_views = [], False
+        if pl['best_model'] is not None:
+            self.best_model = type(pl['best_model'])((k, v.to(dev)) for k, v in pl['best_model'].items())
+        if pl['hyper']:
+            self._device_schedule()
+            for (block, _), raw in zip(self.optimizer.device_hyper, pl['hyper']):
+                block.copy_(raw)
+        if pl['guard'] is not None:
+            self._attach_guard()
+            self._guard._device_state().copy_(pl['guard'])
+        for name, base in host['drop_base'].items():
+            modules[name]._drop_base = int(base)
+        for name, step in pl['drop_step'].items():
+            modules[name]._drop_step = step.to(dev)
+        self._rng_set(host['rng'])             # last: nothing above may consume a draw after this
+        return pl['epoch'], pl['over']
+
     # ------------------------------------------------------------------------------------
     def train(self):
+        if not self.async_checkpoints and self._resume_path is None:
+            return self._train_dp()
+        self._resume_refusals()
+        try:
+            return self._train_dp()
+        finally:
+            self._writer_close()              # every queued file is on disk, or its error is raised here
+
+    def _train_dp(self):
         if self._dp_spec is None:
             return self._train()
         try:
@@ -748,6 +1132,11 @@ class Trainer():
         multi = self.model_type in _MULTI
         os.makedirs(self.output_save_dir, exist_ok=True)
         main = self._main                     # data parallel: rank 0 alone writes files, prints and shows the progress bar
+        first_epoch, resumed = self.start_epoch, None
+        if self._resume_path is not None:
+            if self._dp is not None and self._dp.world > 1:
+                raise NotImplementedError("resume with data_parallel over more than one rank")
+            resumed = self._resume_from_file()          # raises before anything is modified; None: a fresh run
         log = open(os.path.join(self.output_save_dir, "logs.txt") if main else os.devnull, 'a')
 
         def say(msg, echo=True):
@@ -761,7 +1150,12 @@ class Trainer():
         use_cuda = torch.cuda.is_available()
         total_mem = f'{torch.cuda.get_device_properties(0).total_memory / 1E9 if use_cuda else 0:.3g}G'
         total_time = 0.0
-        for epoch in range(self.start_epoch, self.num_epochs + 1):
+        if resumed is not None:
+            say("Resumed after epoch %i from %s" % (resumed[0], self._resume_path))
+            if resumed[1]:                              # the run was over: only its end is left to do
+                return self._finish(log, say)
+            first_epoch, total_time = resumed[0] + 1, self._total_time
+        for epoch in range(first_epoch, self.num_epochs + 1):
             log.write('Epoch {}/{}\n'.format(epoch, self.num_epochs) + '-' * 10 + "\n")
             since = time.time()
             for phase in self.phases:
@@ -816,10 +1210,13 @@ class Trainer():
                     say("Train loss on epoch %i: %f" % (epoch, epoch_loss))
                     self._log_guard(say, epoch)
                     total_time += elapsed
+                    self._total_time = total_time
                     self.meanTimePerEpoch = total_time / epoch
                     say('Curent mean training time per epoch: {:.0f}m {:.0f}s\n'.format(
                         self.meanTimePerEpoch // 60, self.meanTimePerEpoch % 60))
-                    if main:
+                    if main and self._ckpt_async():
+                        self._save_last(os.path.join(self.save_dir_model, 'last_epoch.pt'))
+                    elif main:
                         torch.save(self.model.state_dict(), os.path.join(self.save_dir_model, 'last_epoch.pt'))
                     self._dp_verify()                       # the replicas still agree, bit for bit (one word per rank)
                     continue
@@ -840,13 +1237,21 @@ class Trainer():
                     self.best_val_score = selector
                     self.best_loss = epoch_loss
                     say("saving best model")
-                    self.best_model = copy.deepcopy(self.model.state_dict())      # on every rank: train() returns it everywhere
-                    if main:
+                    if self._ckpt_async():
+                        self._save_best([os.path.join(self.save_dir_model, n) for n in ('epoch{}.pt'.format(epoch), 'best.pt')]
+                                        if main else [])
+                    else:
+                        self.best_model = copy.deepcopy(self.model.state_dict())  # on every rank: train() returns it everywhere
+                        self._best_views = False
+                    if main and not self._ckpt_async():
                         torch.save(self.best_model, os.path.join(self.save_dir_model, 'epoch{}.pt'.format(epoch)))
                         torch.save(self.best_model, os.path.join(self.save_dir_model, 'best.pt'))
                 else:
                     self.early_stop_counter += 1
-                if self.early_stop_counter > self.patience:
+                stop = self.early_stop_counter > self.patience
+                if self._resume_path is not None and main:
+                    self._write_run_state(epoch, stop or epoch == self.num_epochs)
+                if stop:
                     say("Early stopping")
                     return self._finish(log, say)
 

@@ -670,9 +670,11 @@ def _eval_fold():
 
 def dropout_seeds(module, device, training):
     """(host seed, device step counter) for the dropout streams of `module`'s forward.  The host part is drawn ONCE per model
-    from torch's CPU generator (reproducible under torch.manual_seed, different between the seeds of a sweep and between a
-    run and its resumption); the device counter advances by a device op on every training forward, also under HIP-graph
-    replay, where anything computed on the host is frozen at capture time."""
+    from torch's CPU generator (reproducible under torch.manual_seed, different between the seeds of a sweep); the device
+    counter advances by a device op on every training forward, also under HIP-graph replay, where anything computed on the
+    host is frozen at capture time.  Both are part of the Trainer's run state (`Trainer(resume=...)`,
+    `snapshot_run_state()`): a resumed run sets `_drop_base` and `_drop_step` before its first forward, so nothing is drawn
+    here and the stream continues where the run was cut."""
     if not training or device.type != "cuda":
         return 0, None
     if getattr(module, "_drop_base", None) is None:
