@@ -709,6 +709,34 @@ int umi_snapshot_multi(const void* descs, int n_desc, int total_blocks, void* ws
                        umi_stream_t stream);
 int umi_restore_multi(const void* descs, int n_desc, int total_blocks, umi_stream_t stream);
 
+/* Exponential moving average of the weights (mean teacher, timm.ModelEmaV2, torch.optim.swa_utils.AveragedModel), updated on
+ * the device right after the optimizer step so that a captured HIP graph keeps averaging.  The state is a DEVICE array of
+ * UMI_EMA_LEN doubles (8-byte aligned), as the guard block is:
+ *   settings   DECAY (d, the ceiling), WARMUP (!= 0: d_t = min(d, (1 + t) / (10 + t)), else d_t = d)
+ *   state      UPDATES (t: updates applied so far)
+ *   last pass  LAST (the d_t of the last update), WEIGHT ((double)w_f, w_f = (float)(1.0 - d_t): the fp32 factor the multi pass
+ *              uses), ACTIVE (1: the multi pass stores; 0: it returns before any store)
+ * One update:  umi_ema_pre, then umi_ema_multi per descriptor table.
+ *   pre    `guard` (nullable) is a guard block (above).  guard != NULL and guard[UMI_GUARD_SKIP] != 0: ACTIVE = 0 and nothing
+ *          else changes (a skipped optimizer step does not move the average).  Otherwise, all in double with t = UPDATES:
+ *          d_t as above; LAST = d_t; WEIGHT = (double)(float)(1.0 - d_t); ACTIVE = 1; UPDATES = t + 1.  One small launch.
+ *   multi  over a umi_optim_desc table: `p` the live fp32 parameter (only read), `s0` its fp32 shadow, `n` and `blk0` as for
+ *          the optimizer; `g` and `s1` are not read.  ACTIVE set: every element e of s0 becomes
+ *              e + w_f * (p - e)      three separate fp32 roundings (subtract, multiply, add; never a fused multiply-add),
+ *          so the NumPy float32 statement e + w * (p - e) gives the same bits.  ACTIVE clear: returns before any store.
+ *          Any pointer alignment of 4 bytes: 16-byte accesses where p and s0 share their offset into a 16-byte line (at most
+ *          three leading and three trailing elements of a block go one by one), one element per lane where they do not.
+ *          Exactly n elements of s0 are written.  No atomics; every store is a vector store.
+ *   swap   exchanges the 32-bit words of p and s0, exactly n per row (validation on the averaged weights, in place); the same
+ *          alignment rule.  One launch; none when total_blocks == 0.  It does not read the state block.
+ * Null pointers (descs with n_desc > 0, state) and negative counts are UMI_ERR_BADARG before any launch; n_desc == 0
+ * succeeds and launches nothing. */
+enum { UMI_EMA_DECAY = 0, UMI_EMA_WARMUP = 1, UMI_EMA_UPDATES = 2, UMI_EMA_LAST = 3, UMI_EMA_WEIGHT = 4, UMI_EMA_ACTIVE = 5,
+       UMI_EMA_SPARE0 = 6, UMI_EMA_SPARE1 = 7, UMI_EMA_LEN = 8 };
+int umi_ema_pre(double* state, const double* guard, umi_stream_t stream);
+int umi_ema_multi(const void* descs, int n_desc, int total_blocks, const double* state, umi_stream_t stream);
+int umi_ema_swap_multi(const void* descs, int n_desc, int total_blocks, umi_stream_t stream);
+
 /* umi_pack_kn / umi_pack_kn8 of many weight tensors in one launch (all the convolution weights of a model after an
  * optimizer step).  `descs`: DEVICE array sorted by blk0; an entry owns ceil(T*Kpad*Npad / umi_pack_block_elems()) blocks. */
 typedef struct umi_pack_desc {

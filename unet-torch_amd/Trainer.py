@@ -120,6 +120,25 @@ than one rank (per-rank generator states are not collected; a world of one works
 one Snapshot over parameters, buffers, optimizer state, hyper blocks, guard block and dropout counters, the host fields and
 generator states beside it; every tensor keeps its address, so under graph=True no graph is captured again, and the parameter
 versions are bumped, so the kernel-layout weight copies are re-packed.  With both arguments at their defaults none of this runs.
+`Trainer(..., ema=...)` (keyword-only, after `resume`; singe_train / multi_task_train): None / False = nothing of this runs; True,
+a float (the decay), `dict(decay=0.999, warmup=True, validate=True)` or a ready `umi.ema.ModelEMA` = an exponential moving average
+of the parameters that require a gradient (buffers are not averaged: the averaged model is the averaged parameters plus the live
+BatchNorm running statistics, as `AveragedModel(use_buffers=False)`); anything else raises ValueError.  The shadows are copies of
+the parameters taken before the first step.  `ema.update()` (two launches, `umi_ema_pre` + `umi_ema_multi`) follows
+`optimizer.step()` inside the step body, so a captured step contains it; in the deferred data-parallel path it follows `flush()` +
+`optimizer.step()` after each replay.  The `grad_guard` block gates it on the device: a skipped step leaves the shadows' bits and
+the update count alone, eagerly and in a replay.  With `validate=True` (the default) the validation phase runs on the averaged
+weights IN PLACE: `ema.swap()` exchanges parameters and shadows after `_dp_phase`'s BatchNorm broadcast (one launch; the parameter
+versions are bumped, so `ops.PackCache` and the eval graphs re-pack), and swaps back after the best-model decision -- loss, score,
+`best_model`, `epochN.pt` and `best.pt` are those of the averaged weights (what is validated is what is saved, and what train()
+returns), `last_epoch.pt` keeps the live weights; under `async_checkpoints` the best files then come from a host copy of the
+best-model arena taken while the average is swapped in, not from the copy behind `last_epoch.pt`.  `validate=False` only maintains
+the average (`trainer.ema`: `averaged()`, `copy_to(model)`, `state_dict()`).  One line per epoch goes to `logs.txt` after the
+training phase, on rank 0: `EMA on epoch N: decay D, updates U` (D = the decay of the last update).  The shadows and the state
+block are part of `_state_tensors` (`ema.shadow.<name>`, `ema.state`): `resume` and `snapshot_run_state()` / `restore_run_state()`
+carry them, a resumed run stays bit-identical, a run-state file written with `ema` and read without it (or the reverse) raises
+before anything is modified, and the data-parallel replica check covers them.  With 'multi_task_loss_ratio' train() raises
+NotImplementedError before the first step.
 `lr_scheduler=True` (what the reference's train.py passes) crashes the reference in its first validation after epoch 5
 (`True.step`); here train() raises NotImplementedError before the first step whenever the run would reach that point.
 The remaining epoch loops of the reference (uncertainty-weighted multi-task, CLTR, Topo losses) are out of scope and raise.
@@ -147,7 +166,7 @@ class Trainer():
     def __init__(self, model, model_type, dtype, device, output_save_dir, dataloaders, batch_size, optimizer,
                  patience, num_epochs, loss_function, accuracy_metric, lr_scheduler=None, start_epoch=1, *, graph=None,
                  batch_transform=None, grad_guard=None, data_parallel=None, val_batch=None, val_confusion=False,
-                 async_checkpoints=False, resume=None):
+                 async_checkpoints=False, resume=None, ema=None):
         self.model = model
         self.model_type = model_type
         self.dtype = dtype
@@ -218,8 +237,67 @@ class Trainer():
         self._writer, self._ckpt_snap, self._best_snap, self._file_snap, self._run_snap = None, None, None, None, None
         self._run_host, self._total_time, self._best_views, self._ckpt_event = None, 0.0, False, None
 
+        # weight average (see the module docstring): the ModelEMA arguments (or a ready ModelEMA) until the first step, then the
+        # ModelEMA; whether the validation phase runs on the averaged weights
+        self._ema_spec, self._ema_validate = self._parse_ema(ema)
+        self._ema = None
+
         self.save_dir_model = os.path.join(self.output_save_dir, 'models/')
         os.makedirs(self.save_dir_model, exist_ok=True)
+
+    @staticmethod
+    def _parse_ema(spec):
+        """`ema` -> (None | dict of ModelEMA arguments | ModelEMA, validate).  ValueError on anything else."""
+        if spec is None or spec is False:
+            return None, False
+        if spec is True:
+            return {}, True
+        if isinstance(spec, float):
+            spec = dict(decay=spec)
+        if isinstance(spec, dict):
+            kw = dict(spec)
+            validate = kw.pop('validate', True)
+            if set(kw) - {'decay', 'warmup'} or not isinstance(validate, bool):
+                raise ValueError(f"ema takes dict(decay=0.999, warmup=True, validate=True), not {spec!r}")
+            if not 0.0 <= float(kw.get('decay', 0.999)) < 1.0:
+                raise ValueError(f"ema: decay must be in [0, 1), not {kw['decay']!r}")
+            return kw, validate
+        if type(spec).__name__ == 'ModelEMA' and hasattr(spec, 'swap'):
+            return spec, True
+        raise ValueError(f"ema takes None / False, True, a float (the decay), a dict(decay=, warmup=, validate=) or a "
+                         f"umi.ema.ModelEMA, not {spec!r}")
+
+    @property
+    def ema(self):
+        """The umi.ema.ModelEMA of this run (None: `ema` is off, or no step has run yet)."""
+        return self._ema
+
+    def _attach_ema(self):
+        """Before the first step (and before a run state is read): the shadows as copies of the parameters, which are where
+        they train by now; the guard gates the update on the device."""
+        if self._ema_spec is None or self._ema is not None:
+            return
+        if isinstance(self._ema_spec, dict):
+            from umi.ema import ModelEMA
+            self._attach_guard()
+            self._ema = ModelEMA(self.model, guard=self._guard, **self._ema_spec)
+        else:
+            self._ema = self._ema_spec
+            if self._ema.guard is None and self._guard is not None:
+                self._attach_guard()
+                self._ema.guard = self._guard
+
+    def _ema_tensors(self):
+        import collections
+        if self._ema is None:
+            return collections.OrderedDict()
+        return collections.OrderedDict(('ema.' + k, v) for k, v in self._ema.tensors().items())
+
+    def _log_ema(self, say, epoch):
+        if self._ema is None or not self._main:
+            return
+        r = self._ema.sync_host()
+        say("EMA on epoch %i: decay %g, updates %i" % (epoch, r["last"], r["updates"]))
 
     @staticmethod
     def _make_guard(spec):
@@ -313,7 +391,11 @@ class Trainer():
     def _dp_verify(self):
         if self._dp_check:
             from umi import ddp
-            ddp.check_replicas(self.model, self._dp.group, buffers=self._dp.batch_sync is not None)
+            if self._ema is None:
+                ddp.check_replicas(self.model, self._dp.group, buffers=self._dp.batch_sync is not None)
+            else:
+                ddp.check_replicas(self.model, self._dp.group, buffers=self._dp.batch_sync is not None,
+                                   extra=list(self._ema.tensors().values()))
 
     def _dp_end(self):
         """End of train(), also on an error: hand the model back as it came (a reducer built here is closed, so the
@@ -422,6 +504,13 @@ class Trainer():
         best = self._snap_for('_best_snap', self.model.state_dict())
         best.take()
         self.best_model, self._best_views = best.views(), True
+        if self._ema is not None and self._ema.swapped:
+            # the averaged weights are swapped in: this phase DID change the weights, so the files come from a host copy of the
+            # arena just taken, not from the one behind 'last_epoch.pt' (which keeps the live weights)
+            event = best.to_host_async()
+            for path in paths:
+                self._submit(best, event, best.host_views(), path)
+            return
         snap = self._ckpt_snap[1] if self._ckpt_snap is not None else None
         for path in paths:
             self._submit(snap, self._ckpt_event, snap.host_views(), path)
@@ -448,6 +537,7 @@ class Trainer():
         for name, m in self.model.named_modules():
             if getattr(m, '_drop_step', None) is not None:
                 out['drop.' + name] = m._drop_step
+        out.update(self._ema_tensors())
         if best and isinstance(self.best_model, dict):
             for k, v in self.best_model.items():
                 out['best.' + k] = v
@@ -563,6 +653,8 @@ class Trainer():
             out['guard'] = pl['guard']
         for name, step in pl['drop_step'].items():
             out['drop.' + name] = step
+        for k, v in (pl.get('ema') or {}).items():
+            out['ema.' + k] = v
         for k, v in (pl['best_model'] or {}).items():
             out['best.' + k] = v
         return out
@@ -611,6 +703,7 @@ class Trainer():
         pl = dict(format=self.RUN_STATE_FORMAT, epoch=int(epoch), over=bool(over), model=model, optimizer=osd,
                   optimizer_class=type(self.optimizer).__name__, hyper=list(take('hyper.').values()) or None,
                   guard=views.get('guard'), drop_step=dict(take('drop.')), best_model=take('best.') or None, host=host,
+                  ema=take('ema.') or None,
                   word=snap.word(), host_word=self._host_word(host))
         assert list(self._payload_tensors(pl)) == list(live)
         if self._ckpt_async():
@@ -657,6 +750,14 @@ class Trainer():
             raise ValueError(f"resume: {path} holds device optimizer blocks; this optimizer is not a umi.optim one")
         if pl['guard'] is not None and self._guard is None:
             raise ValueError(f"resume: {path} was written with a grad_guard, this Trainer has none")
+        mine, theirs = self._ema_tensors(), pl.get('ema') or {}
+        if ['ema.' + k for k in theirs] != list(mine):
+            raise ValueError(f"resume: {path} was written {'with' if theirs else 'without'} an `ema`, this Trainer runs "
+                             f"{'with another one' if mine and theirs else 'with one' if mine else 'without'}")
+        for k, v in theirs.items():
+            if v.shape != mine['ema.' + k].shape or v.dtype != mine['ema.' + k].dtype:
+                raise ValueError(f"resume: ema.{k} is {tuple(v.shape)} {v.dtype} in {path}, "
+                                 f"{tuple(mine['ema.' + k].shape)} {mine['ema.' + k].dtype} in this Trainer")
         dev = self._dp_device()
         words = [t.to(dev) for t in tensors.values()]
         for i, t in enumerate(words):
@@ -682,6 +783,9 @@ class Trainer():
         if pl['guard'] is not None:
             self._attach_guard()
             self._guard._device_state().copy_(pl['guard'])
+        with torch.no_grad():
+            for k, v in theirs.items():
+                mine['ema.' + k].copy_(v)
         for name, base in host['drop_base'].items():
             modules[name]._drop_base = int(base)
         for name, step in pl['drop_step'].items():
@@ -691,6 +795,8 @@ class Trainer():
 
     # ------------------------------------------------------------------------------------
     def train(self):
+        if self._ema_spec is not None and self._ratio_loop():
+            raise NotImplementedError("ema with multi_task_loss_ratio: the count-ratio loop is not covered")
         if not self.async_checkpoints and self._resume_path is None:
             return self._train_dp()
         self._resume_refusals()
@@ -773,6 +879,8 @@ class Trainer():
             if self.grad_sync is not None:
                 self.grad_sync()
             self.optimizer.step()
+            if self._ema is not None:         # inside the step: a captured step contains the update
+                self._ema.update()
         return loss
 
     def _graph_capable(self, inputs):
@@ -786,6 +894,7 @@ class Trainer():
         """One optimisation step (reference Trainer.py:700-726).  Returns the detached loss tensor."""
         inputs, labels = self._to_device(inputs, labels)
         self._attach_guard()
+        self._attach_ema()
         if self._graph_capable(inputs):
             return self._graphed_train_step(inputs, labels)
         guarded_adam = self._guard is not None and "betas" in self.optimizer.param_groups[0]
@@ -835,6 +944,8 @@ class Trainer():
             if deferred:
                 self._dp.flush()
                 self.optimizer.step()
+                if self._ema is not None:
+                    self._ema.update()
         else:
             # first step of a batch shape (allocations, weight-pack caches) or a ragged batch: eager, on the side stream; its
             # outputs are detached, so no autograd graph of it survives into a later capture (umi/graphs.py)
@@ -1136,6 +1247,7 @@ class Trainer():
         if self._resume_path is not None:
             if self._dp is not None and self._dp.world > 1:
                 raise NotImplementedError("resume with data_parallel over more than one rank")
+            self._attach_ema()                          # its tensors are part of the run state
             resumed = self._resume_from_file()          # raises before anything is modified; None: a fresh run
         log = open(os.path.join(self.output_save_dir, "logs.txt") if main else os.devnull, 'a')
 
@@ -1170,6 +1282,9 @@ class Trainer():
                     since = time.time()
                 self.model.train(train)
                 self._dp_phase(train)
+                averaged = not train and self._ema is not None and self._ema_validate
+                if averaged:                  # validate, select and save the averaged weights, in place (after the broadcast)
+                    self._ema.swap()
                 if not train and self._val_conf is not None:
                     self._val_conf.zero_()
 
@@ -1209,6 +1324,7 @@ class Trainer():
                         self.train_loss_list_2.append(float(task_sums[1]) / steps)
                     say("Train loss on epoch %i: %f" % (epoch, epoch_loss))
                     self._log_guard(say, epoch)
+                    self._log_ema(say, epoch)
                     total_time += elapsed
                     self._total_time = total_time
                     self.meanTimePerEpoch = total_time / epoch
@@ -1248,6 +1364,8 @@ class Trainer():
                         torch.save(self.best_model, os.path.join(self.save_dir_model, 'best.pt'))
                 else:
                     self.early_stop_counter += 1
+                if averaged:                  # the live weights back, bit for bit
+                    self._ema.swap()
                 stop = self.early_stop_counter > self.patience
                 if self._resume_path is not None and main:
                     self._write_run_state(epoch, stop or epoch == self.num_epochs)

@@ -358,10 +358,11 @@ def fingerprint(tensors):
     return FingerprintPlan(tensors).launch().word()
 
 
-def check_replicas(model, group=None, buffers=False):
-    """Every rank fingerprints its parameters (and buffers, when they are meant to be identical too: global_batch), the words
-    are all-gathered, and EVERY rank raises RuntimeError when they differ.  Returns this rank's word."""
-    tensors = list(model.parameters()) + (list(model.buffers()) if buffers else [])
+def check_replicas(model, group=None, buffers=False, extra=()):
+    """Every rank fingerprints its parameters (and buffers, when they are meant to be identical too: global_batch; and `extra`,
+    further tensors that must agree, such as the shadows of a weight average), the words are all-gathered, and EVERY rank raises
+    RuntimeError when they differ.  Returns this rank's word."""
+    tensors = list(model.parameters()) + (list(model.buffers()) if buffers else []) + list(extra)
     word = fingerprint(tensors)
     world = dist.get_world_size(group) if dist.is_available() and dist.is_initialized() else 1
     if world == 1:
