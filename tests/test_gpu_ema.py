@@ -271,7 +271,7 @@ def eager_items(tmp_path_factory):
 def test_trainer_validates_on_the_averaged_weights(tmp_path, eager_items, async_ckpt):
     _gpu()
     tr, m, swaps = _validating_run(tmp_path, graph=True, val_batch=2, async_checkpoints=async_ckpt)
-    assert len(tr._graphs) == 1 and len(tr._eval_graphs) == 1 and len(swaps) == 4 and not tr.ema.swapped
+    assert len(tr._graphs) == 1 and len(tr._validation().graphs) == 1 and len(swaps) == 4 and not tr.ema.swapped
     assert tr.val_loss_list == eager_items["val"] and tr.val_score_list == eager_items["score"]
     assert tr.train_loss_list == eager_items["train"] and len(tr.val_loss_list) == 2
     names = [n for n, _ in m.named_parameters()]
@@ -408,16 +408,16 @@ def _worker(rank, world, port, q, out_dir):
         out[name] = dict(shadows=[t.cpu().numpy() for t in tensors], val=tr.val_loss_list, replayed=bool(tr._graphs),
                          word=ddp.fingerprint(list(m.parameters()) + tensors), updates=tr.ema.sync_host()["updates"])
     # the replica word covers the shadows: one ulp in one shadow of rank 1 and the Trainer's check raises on both ranks
-    tr._dp, tr._dp_check = ddp.GradReducer(m, bucket_mb=0.05), True
-    tr._dp_verify()
+    tr._dp.reducer, tr._dp.check = ddp.GradReducer(m, bucket_mb=0.05), True
+    tr._dp.verify()
     if rank == 1:
         tr.ema.shadows[3].view(-1)[-1:].view(torch.int32).add_(1)
     try:
-        tr._dp_verify()
+        tr._dp.verify()
         out["differ"] = "no error"
     except RuntimeError as e:
         out["differ"] = str(e)
-    tr._dp.close()
+    tr._dp.reducer.close()
     q.put((rank, out))
     dist.barrier()
     dist.destroy_process_group()

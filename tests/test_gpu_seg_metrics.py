@@ -310,7 +310,7 @@ def test_trainer_paths_agree(tmp_path, family, mode):
     for name, kw in (("items", dict(val_batch=None, graph=False)), ("batched", dict(val_batch=4, graph=False)),
                      ("replayed", dict(val_batch=4, graph=True))):
         tr = _train(tmp_path / name, family, mode, **kw)
-        assert len(tr._eval_graphs) == (1 if name == "replayed" else 0)
+        assert len(tr._validation().graphs) == (1 if name == "replayed" else 0)
         runs[name] = _figures(tr, tmp_path / name)
     a = runs["items"]
     assert len(a["val"]) == len(a["score"]) == len(a["conf"]) == EPOCHS

@@ -318,4 +318,4 @@ def test_async_checkpoint_that_cannot_be_written_raises_from_train(tmp_path):
     (tmp_path / "models").write_text("not a directory")               # every file under models/ is unwritable now
     with pytest.raises((OSError, RuntimeError), match="models"):
         tr.train()
-    assert tr._writer is None                                          # joined and closed all the same
+    assert tr._run.writer is None                                          # joined and closed all the same

@@ -373,7 +373,7 @@ def test_nine_classes_stay_eager_under_graph(tmp_path, device_calls):
         with warnings.catch_warnings(record=True) as seen:
             warnings.simplefilter("always")
             for i in range(0, 9, 3):                                  # three full groups of one shape: eager, eager, eager
-                tr._run_val_group(items[i:i + 3])
+                tr._validation().run_group(items[i:i + 3])
             total = torch.zeros((), device=DEV)
             for xi, li in items:
                 total = total + tr.eval_step(xi, li)[1]
@@ -381,8 +381,8 @@ def test_nine_classes_stay_eager_under_graph(tmp_path, device_calls):
     finally:
         L.CLASS_NUMBER = 2
     assert any("host copies" in str(w.message) for w in seen)
-    assert len(tr._eval_graphs) == 0 and len(tr._eval_host) == 1 and len(tr._eval_seen) == 0
-    assert torch.isfinite(total) and float(tr._val_sums[1]) == float(total)
+    assert len(tr._validation().graphs) == 0 and len(tr._validation().host) == 1 and len(tr._validation().seen) == 0
+    assert torch.isfinite(total) and float(tr._validation().sums[1]) == float(total)
     assert device_calls["kernel"] == 0 and device_calls["composite"] == 3 + 9
 
 
@@ -394,7 +394,7 @@ def test_trainer_paths_agree(tmp_path, device_calls):
     for name, kw in (("items", dict(val_batch=None, graph=False)), ("batched", dict(val_batch=3, graph=False)),
                      ("replayed", dict(val_batch=3, graph=True)), ("confusion", dict(val_batch=3, graph=True, val_confusion=True))):
         tr = _train(tmp_path / name, **kw)
-        assert len(tr._eval_graphs) == (0 if name in ("items", "batched") else 1)
+        assert len(tr._validation().graphs) == (0 if name in ("items", "batched") else 1)
         runs[name] = dict(val=tr.val_loss_list, score=tr.val_score_list, best=tr.best_val_score)
     a = runs["items"]
     assert len(a["score"]) == EPOCHS and all(np.isfinite(s) and 0.0 <= s <= 31 * 2 ** 0.5 + 1e-6 for s in a["score"])

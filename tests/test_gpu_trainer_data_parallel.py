@@ -76,10 +76,11 @@ def test_a_second_train_call_replays_the_same_graphs_into_the_same_buckets(tmp_p
     for name, dp in (("plain", None), ("dp", dict(world_size=1))):
         tr, m = _trainer(tmp_path / name, list(range(6)), [6, 7], 2, 6, graph=True, data_parallel=dp)
         tr.lr_scheduler = None                                        # (the poly rule ends with the first call's last step)
+        built = lambda: None if tr._dp is None else tr._dp.built      # noqa: E731  (the plain Trainer has no data-parallel run)
         tr.train()
-        first = tr._dp_built
+        first = built()
         tr.train()
-        assert tr._dp_built is first and len(tr._graphs) == 1 and tr.iter_num == 6 * EPOCHS
+        assert built() is first and len(tr._graphs) == 1 and tr.iter_num == 6 * EPOCHS
         runs.append((tr.train_loss_list, _state(m)))
     assert runs[0][0] == runs[1][0] and len(runs[0][0]) == 2 * EPOCHS
     for k in runs[0][1]:

@@ -144,13 +144,13 @@ def _four_runs(tmp_path, family, mode, odd_at=None):
         calls = spy.n.get("umi_dice_ce_fwd_items", 0)
         assert len(tr._graphs) == (1 if kw["graph"] else 0)
         if kw["val_batch"] is None:
-            assert calls == 0 and tr._eval_graphs == {}
+            assert calls == 0 and tr._validation().graphs == {}
         elif not kw["graph"]:
-            assert tr._eval_graphs == {} and calls == (n_groups * EPOCHS if fused else 0)
+            assert tr._validation().graphs == {} and calls == (n_groups * EPOCHS if fused else 0)
         else:
             # the shape's 1st full group runs eagerly, its 2nd is captured (one call each, both in epoch 1), every later one is
             # a replay (no call); the ragged / odd-shaped group runs eagerly in every epoch
-            assert len(tr._eval_graphs) == 1 and calls == ((2 + EPOCHS) if fused else 0)
+            assert len(tr._validation().graphs) == 1 and calls == ((2 + EPOCHS) if fused else 0)
         out[name] = _figures(tr, tmp_path / name)
     return out
 
@@ -191,22 +191,22 @@ def test_replay_after_training_and_after_load_state_dict_reads_current_weights(t
     flat = [torch.cat([g[0] for g in group]), torch.cat([g[1] for g in group])]
 
     def grouped():                                  # through the Trainer's own path: eager, capture, replay
-        if tr._val_sums is not None:
-            tr._val_sums.zero_()
-        tr._run_val_group(group)
-        return tr._val_sums.clone()
+        if tr._validation().sums is not None:
+            tr._validation().sums.zero_()
+        tr._validation().run_group(group)
+        return tr._validation().sums.clone()
 
     def eager():                                    # the same function without a graph
-        tr._val_sums.zero_()
-        rows = tr._val_group_fn(K)(*flat)
-        return tr._val_sums.clone(), rows.clone()
+        tr._validation().sums.zero_()
+        rows = tr._validation().group_fn(K)(*flat)
+        return tr._validation().sums.clone(), rows.clone()
 
     m.eval()
     v1 = grouped()
-    assert tr._eval_graphs == {}
+    assert tr._validation().graphs == {}
     v2 = grouped()
-    assert len(tr._eval_graphs) == 1                # captured and replayed
-    ge = next(iter(tr._eval_graphs.values()))
+    assert len(tr._validation().graphs) == 1                # captured and replayed
+    ge = next(iter(tr._validation().graphs.values()))
     assert torch.equal(_bits(v1), _bits(v2))
     # a training phase: three steps (eager, captured, replayed), as the epoch between two validation phases
     m.train()
@@ -272,7 +272,7 @@ def test_world_of_one(tmp_path):
     for name, kw in (("items", dict(val_batch=None)), ("batched", dict(val_batch=K))):
         tr, m = _trainer(tmp_path / name, "unet", "fp16", graph=True, data_parallel=dict(world_size=1), **kw)
         tr.train()
-        assert bool(tr._eval_graphs) == (name == "batched") and len(tr._graphs) == 1
+        assert bool(tr._validation().graphs) == (name == "batched") and len(tr._graphs) == 1
         figs[name] = _figures(tr, tmp_path / name)
     _assert_same(figs["batched"], figs["items"])
 
@@ -288,7 +288,7 @@ def _worker(rank, world, port, q, out_dir):
                          data_parallel=dict(bucket_mb=0.05))
         tr.train()
         out[name] = dict(val=tr.val_loss_list, score=tr.val_score_list, train=tr.train_loss_list, best=tr.best_val_score,
-                         eval_graphs=len(tr._eval_graphs), graphs=len(tr._graphs))
+                         eval_graphs=len(tr._validation().graphs), graphs=len(tr._graphs))
     q.put((rank, out))
     dist.barrier()
     dist.destroy_process_group()

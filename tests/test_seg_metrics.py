@@ -342,7 +342,7 @@ def test_val_batch_gives_the_same_lists(tmp_path):
     assert sorted(os.listdir(tmp_path / "a" / "models")) == sorted(os.listdir(tmp_path / "b" / "models"))
     # the old names and the default are the old code: no matrix, no accumulator
     c = _run(tmp_path / "c", metric="dice_bce_mc", val_batch=3)
-    assert c.val_confusion_list == [] and c._val_conf is None and c.val_class_scores is None and c.val_score_list == c.val_loss_list
+    assert c.val_confusion_list == [] and c._validation().conf is None and c.val_class_scores is None and c.val_score_list == c.val_loss_list
     # val_confusion with an old metric name: the matrices of the same predictions
     d = _run(tmp_path / "d", metric="dice_bce_mc", val_batch=3, val_confusion=True)
     assert d.val_score_list == c.val_score_list

@@ -279,7 +279,7 @@ def test_resume_refusals_come_before_the_first_step(tmp_path):
                  resume=str(tmp_path / "elsewhere.pt"), data_parallel=dict(world_size=2))
     with pytest.raises(NotImplementedError, match="more than one rank"):
         tr.train()
-    assert tr._resume_path == str(tmp_path / "elsewhere.pt")
+    assert tr._run.resume_path == str(tmp_path / "elsewhere.pt")
 
 
 def test_roll_back_in_memory_on_the_cpu(tmp_path):
@@ -304,3 +304,47 @@ def test_roll_back_in_memory_on_the_cpu(tmp_path):
     b = more()
     assert a[0] == b[0] and a[3:] == b[3:]
     assert all(torch.equal(a[1][k], b[1][k]) for k in a[1]) and all(torch.equal(u, v) for u, v in zip(a[2], b[2]))
+
+
+# ---- the run-state file across changes of the Trainer -------------------------------------------------------------------------
+
+def _tensor_specs(obj, at=""):
+    """[(where, dtype, shape)] of every tensor in a nest of dicts, lists and tuples, in order."""
+    if torch.is_tensor(obj):
+        return [(at, obj.dtype, tuple(obj.shape))]
+    if isinstance(obj, dict):
+        return [s for k, v in obj.items() for s in _tensor_specs(v, f"{at}/{k}")]
+    if isinstance(obj, (list, tuple)):
+        return [s for i, v in enumerate(obj) for s in _tensor_specs(v, f"{at}/{i}")]
+    return []
+
+
+def test_a_run_state_file_of_format_1_still_resumes(tmp_path, golden_dir):
+    """tests/golden/run_state_v1.pt was written by tools/gen_golden_run_state.py (the setting of _cut_run at feat=2) before the
+    Trainer was split into umi/run_state.py, umi/val_batch.py and umi/dp_run.py.  No number of it is compared with a fresh run:
+    CPU arithmetic may differ between torch builds, and total_time is wall clock."""
+    import shutil
+    from umi import ddp, run_state as R
+    gold = torch.load(os.path.join(golden_dir, "run_state_v1.pt"), weights_only=True)
+    assert gold["format"] == 1 and gold["epoch"] == 2 and gold["over"] is False
+    # (a) both words, recomputed from the file's contents: the section order and host_word
+    assert ddp.fingerprint(list(R.payload_tensors(gold).values())) == gold["word"]
+    assert R.host_word(gold["host"]) == gold["host_word"]
+    # (b) a new Trainer resumes from a copy of it and trains to the end
+    path = str(tmp_path / "copy_of_v1.pt")
+    shutil.copyfile(os.path.join(golden_dir, "run_state_v1.pt"), path)
+    tr, m, opt = _trainer(tmp_path / "resumed", feat=2, resume=path)
+    tr.train()
+    assert tr.iter_num == 2 * EPOCHS and len(tr.train_loss_list) == len(tr.val_loss_list) == len(tr.val_score_list) == EPOCHS
+    for n in tr._LISTS:
+        was = gold["host"]["lists"][n]
+        assert len(getattr(tr, n)) == (EPOCHS if was else 0) and getattr(tr, n)[:2] == was, n
+    # (c) the file this code writes at the same cut has the fixture's layout
+    _seed_everything()
+    tr, m, opt = _trainer(tmp_path / "cut", cut_at=3, resume=True, feat=2)
+    with pytest.raises(Cut):
+        tr.train()
+    new = torch.load(str(tmp_path / "cut" / "run_state.pt"), weights_only=True)
+    assert list(new) == list(gold) and list(new["host"]) == list(gold["host"])
+    assert list(R.payload_tensors(new)) == list(R.payload_tensors(gold))
+    assert _tensor_specs(new) == _tensor_specs(gold) and len(_tensor_specs(R.payload_tensors(gold))) == len(R.payload_tensors(gold))

@@ -284,23 +284,23 @@ def test_groups_that_copy_to_the_host_are_never_captured(tmp_path):
                  "hd95_mc", graph=True, val_batch=3)
     rng = np.random.default_rng(8)
     key9, key3 = ((3, 9, 8, 8), (3, 8, 8)), ((3, 3, 8, 8), (3, 8, 8))
-    assert not tr._eval_capture_ok(key9)                                         # never seen: the first group runs eagerly
+    assert not tr._validation().capture_ok(key9)                                         # never seen: the first group runs eagerly
     before = L.surface_host_calls()
     x9, t9 = _inputs(rng, 3, 9, 8, 8)
     L.calc_loss_items(x9, t9, 3, loss_type="hd95_mc")                            # CPU tensors: the composite, like 9 channels on a device
     assert L.surface_host_calls() == before + 1
-    tr._eval_note_eager(key9, before)
-    assert key9 in tr._eval_host and key9 not in tr._eval_seen and not tr._eval_capture_ok(key9)
+    tr._validation().note_eager(key9, before)
+    assert key9 in tr._validation().host and key9 not in tr._validation().seen and not tr._validation().capture_ok(key9)
     now = L.surface_host_calls()
     L.calc_loss_items(x9, t9, 3, loss_type="dice_err_mc")                        # other metrics do not count
     assert L.surface_host_calls() == now
-    tr._eval_note_eager(key3, now)
-    assert key3 in tr._eval_seen and tr._eval_capture_ok(key3) and not tr._eval_capture_ok(key9)
+    tr._validation().note_eager(key3, now)
+    assert key3 in tr._validation().seen and tr._validation().capture_ok(key3) and not tr._validation().capture_ok(key9)
     try:
         L.METRICS_KERNEL = False                                                 # everything would go to the host: no capture
-        assert not tr._eval_capture_ok(key3)
+        assert not tr._validation().capture_ok(key3)
         tr.accuracy_metric = "dice_err_mc"                                       # (its composite captures)
-        assert tr._eval_capture_ok(key3)
+        assert tr._validation().capture_ok(key3)
     finally:
         L.METRICS_KERNEL = True
 

@@ -83,14 +83,14 @@ def _same_run(a, b, da, db, per_task=False):
 
 
 def _groups(monkeypatch):
-    """Spy on Trainer._run_val_group: the sizes of the groups the validation phases formed."""
-    from Trainer import Trainer
-    sizes, orig = [], Trainer._run_val_group
+    """Spy on Validation.run_group: the sizes of the groups the validation phases formed."""
+    from umi.val_batch import Validation
+    sizes, orig = [], Validation.run_group
 
     def spy(self, group):
         sizes.append(len(group))
         return orig(self, group)
-    monkeypatch.setattr(Trainer, "_run_val_group", spy)
+    monkeypatch.setattr(Validation, "run_group", spy)
     return sizes
 
 
@@ -101,7 +101,7 @@ def test_groups_of_3_3_1_match_the_item_loop(tmp_path, monkeypatch):
     b = _run(tmp_path / "b", _single_data(), None)
     assert sizes == [3, 3, 1] * 3                     # val_batch=None never comes here
     _same_run(a, b, tmp_path / "a", tmp_path / "b")
-    assert a._graphs == {} and a._eval_graphs == {}   # no device, no graphs
+    assert a._graphs == {} and a._validation().graphs == {}   # no device, no graphs
 
 
 def test_items_of_two_images(tmp_path, monkeypatch):

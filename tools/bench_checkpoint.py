@@ -111,11 +111,11 @@ def time_epoch(rounds, steps, epochs, parent):
         joins[name] = []
         if flags:                                                 # time the join at the end of train() on its own
 
-            def close(tr=tr, name=name, inner=tr._writer_close):
+            def close(name=name, inner=tr._run_state().close):
                 t0 = time.perf_counter()
                 inner()
                 joins[name].append((time.perf_counter() - t0) * 1e3)
-            tr._writer_close = close
+            tr._run_state().close = close
     turns = {k: [] for k in trainers}
     for r in range(rounds + 1):                                   # round 0 warms up: first steps, captures, first writes
         for k, tr in trainers.items():

@@ -65,7 +65,7 @@ def _phase(tr):
     tr.model.eval()
     with tqdm(tr.dataloader["val"], disable=True) as bar:
         if tr.val_batch is not None:
-            loss_sum, score_sum, steps, _ = tr._validate_batched(bar, 1, True, "")
+            loss_sum, score_sum, steps, _ = tr._validation().validate(bar, 1, True, "")
         else:
             loss_sum, score_sum, steps = None, None, 0
             for inputs, labels in bar:
@@ -100,7 +100,7 @@ def time_phase(rounds, items, k):
                 assert sums[v] == total, (v, sums[v], total)           # a replay gives what the first turn gave
                 if r:
                     turns[v].append(ms)
-        assert all(len(trainers[v]._eval_graphs) == 1 for v in ("batched_replay", "replay_slices"))
+        assert all(len(trainers[v]._validation().graphs) == 1 for v in ("batched_replay", "replay_slices"))
         med = {v: statistics.median(t) for v, t in turns.items()}
         spread = abs(med["items"] - med["items_again"])
         base = 0.5 * (med["items"] + med["items_again"])
@@ -160,7 +160,7 @@ def time_epoch(rounds, items, k, steps=30):
            "epoch_ms_turns": {v: [round(x, 2) for x in t] for v, t in turns.items()},
            "aa_spread_ms": round(abs(med["none_a"] - med["none_b"]), 2),
            "val_batch_minus_none_ms": round(med["val_batch"] - base, 2), "val_batch_over_none": round(med["val_batch"] / base, 4),
-           "eval_graphs": {v: len(tr._eval_graphs) for v, tr in trainers.items()},
+           "eval_graphs": {v: len(tr._validation().graphs) for v, tr in trainers.items()},
            "val_loss_equal": len({repr(tr.val_loss_list) for tr in trainers.values()}) == 1}
     print(json.dumps({"epoch": row}), flush=True)
     shutil.rmtree(tmp, ignore_errors=True)

@@ -10,6 +10,26 @@ weight w_f = (float)(1 - d_t) --, the second applies e <- e + w_f * (p - e) to e
 fp32 roundings.  `ema_state_update_numpy` and `ema_update_numpy` are the NumPy statements of the two; the device results equal
 them bit for bit.  A `umi.optim.GradGuard` gates the update on the device: a step the guard skipped leaves the shadows and the
 update count untouched, also inside a replayed graph.
+
+`Trainer(..., ema=...)` (keyword-only, after `resume`; singe_train / multi_task_train): None / False = nothing of this runs; True,
+a float (the decay), `dict(decay=0.999, warmup=True, validate=True)` or a ready `umi.ema.ModelEMA` = an exponential moving average
+of the parameters that require a gradient (buffers are not averaged: the averaged model is the averaged parameters plus the live
+BatchNorm running statistics, as `AveragedModel(use_buffers=False)`); anything else raises ValueError.  The shadows are copies of
+the parameters taken before the first step.  `ema.update()` (two launches, `umi_ema_pre` + `umi_ema_multi`) follows
+`optimizer.step()` inside the step body, so a captured step contains it; in the deferred data-parallel path it follows `flush()` +
+`optimizer.step()` after each replay.  The `grad_guard` block gates it on the device: a skipped step leaves the shadows' bits and
+the update count alone, eagerly and in a replay.  With `validate=True` (the default) the validation phase runs on the averaged
+weights IN PLACE: `ema.swap()` exchanges parameters and shadows after the data-parallel phase's BatchNorm broadcast (one launch;
+the parameter versions are bumped, so `ops.PackCache` and the eval graphs re-pack), and swaps back after the best-model decision
+-- loss, score, `best_model`, `epochN.pt` and `best.pt` are those of the averaged weights (what is validated is what is saved, and
+what train() returns), `last_epoch.pt` keeps the live weights; under `async_checkpoints` the best files then come from a host copy
+of the best-model arena taken while the average is swapped in, not from the copy behind `last_epoch.pt`.  `validate=False` only
+maintains the average (`trainer.ema`: `averaged()`, `copy_to(model)`, `state_dict()`).  One line per epoch goes to `logs.txt` after
+the training phase, on rank 0: `EMA on epoch N: decay D, updates U` (D = the decay of the last update).  The shadows and the state
+block are part of the run state (umi/run_state.py: `ema.shadow.<name>`, `ema.state`): `resume` and `snapshot_run_state()` /
+`restore_run_state()` carry them, a resumed run stays bit-identical, a run-state file written with `ema` and read without it (or
+the reverse) raises before anything is modified, and the data-parallel replica check covers them.  With 'multi_task_loss_ratio'
+train() raises NotImplementedError before the first step.
 """
 import collections
 
