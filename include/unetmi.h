@@ -141,8 +141,9 @@ int umi_conv_fwd_plan(int N, int H, int W, int Ci, int Co, int R, int S, int str
 
 /* BatchNorm2d training statistics -> consumer transform (reference Model.py:17,21 =
  * nn.BatchNorm2d: biased batch variance for normalisation, unbiased into running_var,
- * momentum 0.1).  tx_out[c] = {mean, gamma*rstd, beta - mean*gamma*rstd, 0}; running stats updated in place
- * when non-null. */
+ * momentum 0.1).  tx_out[c] = {mean, gamma*rstd, beta - mean*gamma*rstd, lo}, lo = 0 -- or NaN where scale or shift is not
+ * finite (a NaN / Inf in the channel): max(NaN, NaN) keeps such a channel NaN in every consumer.  Running stats updated in
+ * place when non-null. */
 int umi_bn_finalize(const float* stat_part, int rows, int C, double count,
                     const float* gamma, const float* beta, float eps, float momentum,
                     float* running_mean, float* running_var,

@@ -23,6 +23,19 @@ __device__ __forceinline__ float umi_tx_pre(float v, const float4 t) {
 __device__ __forceinline__ float umi_tx(float v, const float4 t) {
     return fmaxf(umi_tx_pre(v, t), t.w);
 }
+// Non-finite values: fmaxf (and the packed fp16 max of umi_tx8) returns its non-NaN operand, so the clamp alone would turn a
+// NaN into `lo`.  A channel whose batch statistics are not finite therefore carries lo = NaN (umi_tx_lo, stored by the
+// statistics finalize): max(NaN, NaN) is NaN, the whole channel reads as NaN in every consumer -- what torch's BatchNorm gives
+// for such a channel -- and no consumer pays an instruction for it.
+__device__ __forceinline__ float umi_tx_lo(float scale, float shift) {
+    return (isfinite(scale) && isfinite(shift)) ? 0.f : __builtin_nanf("");
+}
+// The ReLU mask of the backward pass: the gradient passes where z > lo -- and where z or lo is NaN, as torch's threshold_backward
+// lets it (result <= 0 ? 0 : grad).  A NaN activation must not turn its gradient into a finite zero: with `z > lo` the BatchNorm
+// bias gradient of a step whose loss is NaN came out as an exact 0.  Same cost: one compare (not-less-or-equal for greater).
+__device__ __forceinline__ bool umi_relu_open(float z, float lo) { return !(z <= lo); }
+// relu(v) that keeps a NaN (torch.relu): for the kernels that clamp a value of their own, not a stored activation.  -0 gives +0.
+__device__ __forceinline__ float umi_relu_keep_nan(float v) { return !(v <= 0.f) ? v : 0.f; }
 
 // Stage 3 of the BatchNorm(+ReLU) backward for one element: the gradient of the raw conv output from the gradient `g` of
 // the activated value, dz = gamma*rstd * (relu'(z)*g - c1 - xhat*c2), c1 = sum_dz/M, c2 = sum(dz*xhat)/M.  One definition
@@ -33,7 +46,7 @@ __device__ __forceinline__ float umi_tx(float v, const float4 t) {
 __device__ __forceinline__ float umi_bn_dz_inner(float y, float g, const float4 t, float rstd, float c1, float c2) {
 #pragma clang fp contract(off)
     const float z = umi_tx_pre(y, t);
-    const float dz = z > t.w ? g : 0.f;
+    const float dz = umi_relu_open(z, t.w) ? g : 0.f;
     const float xh = (y - t.x) * rstd;
     return fmaf(-xh, c2, dz - c1);
 }

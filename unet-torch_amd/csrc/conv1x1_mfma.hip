@@ -423,7 +423,7 @@ __global__ __launch_bounds__(256, (P == 128 && BN == 64) ? UMI_C1_OCC128 : 2) vo
 #pragma unroll
                 for (int jj = 0; jj < 8; ++jj) {
                     const float yy_ = (float)yv[jj];
-                    const float dz = umi_tx_pre(yy_, bt[jj]) > bt[jj].w ? (float)hv[jj] : 0.f;
+                    const float dz = umi_relu_open(umi_tx_pre(yy_, bt[jj]), bt[jj].w) ? (float)hv[jj] : 0.f;
                     bs[jj] += dz;
                     bq[jj] = fmaf(dz, (yy_ - bt[jj].x) * brs[jj], bq[jj]);
                 }

@@ -674,7 +674,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_mfma_kernel(
                     const half8 hv = __builtin_bit_cast(half8, v_);                                                   \
                     _Pragma("unroll") for (int jj = 0; jj < 8; ++jj) {                                                \
                         const float yy = (float)(yv_)[jj];                                                            \
-                        const float dz = umi_tx_pre(yy, t[jj]) > t[jj].w ? (float)hv[jj] : 0.f;                       \
+                        const float dz = umi_relu_open(umi_tx_pre(yy, t[jj]), t[jj].w) ? (float)hv[jj] : 0.f;       \
                         s[jj] += dz;                                                                                  \
                         s2[jj] = fmaf(dz, (yy - t[jj].x) * rs_[jj], s2[jj]);                                          \
                     }                                                                                                 \

@@ -41,7 +41,7 @@ __global__ __launch_bounds__(256) void bn_bwd_reduce1_v8(const half_t* __restric
     _Pragma("unroll") for (int j = 0; j < 8; ++j) {                    \
         float yy = (float)yv_[j];                                      \
         float z = umi_tx_pre(yy, t[j]);                                \
-        float dz = z > t[j].w ? (float)gv_[j] : 0.f;                   \
+        float dz = umi_relu_open(z, t[j].w) ? (float)gv_[j] : 0.f;     \
         s[j] += dz;                                                    \
         q[j] = fmaf(dz, (yy - t[j].x) * rs[j], q[j]);                  \
     }
@@ -273,7 +273,7 @@ __global__ __launch_bounds__(256) void pool2_fwd_v8(const half_t* __restrict__ x
             for (int d = 0; d < 4; ++d) {
                 float f = (float)v[d][j];
                 if (HAS_TX) f = umi_tx(f, t[j]);
-                m = f > m ? f : m;
+                m = (f > m || f != f) ? f : m;      // a NaN in the window is the result (F.max_pool2d)
             }
             o[j] = (half_t)m;
         }
@@ -340,7 +340,7 @@ __global__ __launch_bounds__(256) void pool2_bwd_v8(const half_t* __restrict__ d
                 o[d][j] = ACC ? (half_t)((float)o[d][j] + add) : (half_t)add;
                 if (RED) {                      // sums over the STORED (fp16) gradient, like the apply pass will read it
                     const float yy = (float)v[d][j];
-                    const float dz = umi_tx_pre(yy, t[j]) > t[j].w ? (float)o[d][j] : 0.f;
+                    const float dz = umi_relu_open(umi_tx_pre(yy, t[j]), t[j].w) ? (float)o[d][j] : 0.f;
                     s[j] += dz;
                     q[j] = fmaf(dz, (yy - t[j].x) * rs[j], q[j]);
                 }

@@ -235,8 +235,8 @@ __global__ __launch_bounds__(256) void pool3s2_fwd8_kernel(const half_t* __restr
         for (int d = 0; d < 9; ++d) {
             const half8 v = *reinterpret_cast<const half8*>(x + ((long)((long)n * H + 2 * ho + d / 3) * W + 2 * wo + d % 3) * ldx + c);
 #pragma unroll
-            for (int j = 0; j < 8; ++j)
-                if (d == 0 || (float)v[j] > m[j]) { m[j] = (float)v[j]; b[j] = (unsigned char)d; }
+            for (int j = 0; j < 8; ++j)       // (a NaN tap is the result and takes the gradient, as in F.max_pool2d; b stays in 0..8)
+                if (d == 0 || (float)v[j] > m[j] || v[j] != v[j]) { m[j] = (float)v[j]; b[j] = (unsigned char)d; }
         }
         half8 o;
 #pragma unroll

@@ -14,7 +14,6 @@
 
 namespace {
 
-__device__ inline float txf(float v, const float4 t) { return fmaxf(fmaf(v, t.y, t.z), t.w); }
 __device__ inline float sigmoidf_(float z) { return 1.f / (1.f + expf(-z)); }
 
 template <typename T>
@@ -26,9 +25,9 @@ __global__ __launch_bounds__(256) void add2_relu_fwd_kernel(const T* __restrict_
         const long m = i / C;
         const int c = (int)(i - m * C);
         float va = (float)a[m * lda + c], vb = (float)b[m * ldb + c];
-        if (txa) va = txf(va, txa[c]);
-        if (txb) vb = txf(vb, txb[c]);
-        y[m * ldy + c] = (T)fmaxf(va + vb, 0.f);
+        if (txa) va = umi_tx(va, txa[c]);
+        if (txb) vb = umi_tx(vb, txb[c]);
+        y[m * ldy + c] = (T)umi_relu_keep_nan(va + vb);
     }
 }
 
@@ -40,7 +39,7 @@ __global__ __launch_bounds__(256) void add2_relu_bwd_kernel(const T* __restrict_
     for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
         const long m = i / C;
         const int c = (int)(i - m * C);
-        const T g = (float)y[m * ldy + c] > 0.f ? dy[m * lddy + c] : (T)0.f;
+        const T g = umi_relu_open((float)y[m * ldy + c], 0.f) ? dy[m * lddy + c] : (T)0.f;
         da[m * ldda + c] = g;
         db[m * lddb + c] = g;
     }
@@ -54,10 +53,10 @@ __global__ __launch_bounds__(256) void gate_fwd_kernel(const T* __restrict__ x, 
     const long wave = ((long)blockIdx.x * 256 + threadIdx.x) >> 6, nwaves = ((long)gridDim.x * 256) >> 6;
     const float4 tp = txp ? txp[0] : make_float4(0.f, 1.f, 0.f, -INFINITY);
     for (long m = wave; m < M; m += nwaves) {
-        const float A = sigmoidf_(txf((float)p[m], tp));
+        const float A = sigmoidf_(umi_tx((float)p[m], tp));
         for (int c = lane; c < C; c += 64) {
             float v = (float)x[m * ldx + c];
-            if (txx) v = txf(v, txx[c]);
+            if (txx) v = umi_tx(v, txx[c]);
             y[m * ldy + c] = (T)(v * A);
         }
     }
@@ -72,12 +71,12 @@ __global__ __launch_bounds__(256) void gate_bwd_kernel(const T* __restrict__ dy,
     const long wave = ((long)blockIdx.x * 256 + threadIdx.x) >> 6, nwaves = ((long)gridDim.x * 256) >> 6;
     const float4 tp = txp ? txp[0] : make_float4(0.f, 1.f, 0.f, -INFINITY);
     for (long m = wave; m < M; m += nwaves) {
-        const float A = sigmoidf_(txf((float)p[m], tp));
+        const float A = sigmoidf_(umi_tx((float)p[m], tp));
         float acc = 0.f;
         for (int c = lane; c < C; c += 64) {
             const float g = (float)dy[m * lddy + c];
             float v = (float)x[m * ldx + c];
-            if (txx) v = txf(v, txx[c]);
+            if (txx) v = umi_tx(v, txx[c]);
             acc = fmaf(g, v, acc);
             dx[m * lddx + c] = (T)(g * A);
         }
@@ -104,13 +103,13 @@ __global__ __launch_bounds__(256) void gate_fwd_v8(const half_t* __restrict__ x,
         for (int j = 0; j < 8; ++j) t[j] = txx[cg * 8 + j];
     }
     for (long m = gt / G; m < M; m += stride) {
-        const float A = sigmoidf_(txf((float)p[m], tp));
+        const float A = sigmoidf_(umi_tx((float)p[m], tp));
         const half8g v = *reinterpret_cast<const half8g*>(x + m * ldx + cg * 8);
         half8g o;
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
             float f = (float)v[j];
-            if (HAS_TX) f = txf(f, t[j]);
+            if (HAS_TX) f = umi_tx(f, t[j]);
             o[j] = (half_t)(f * A);
         }
         *reinterpret_cast<half8g*>(y + m * ldy + cg * 8) = o;
@@ -134,7 +133,7 @@ __global__ __launch_bounds__(256) void gate_bwd_v8(const half_t* __restrict__ dy
     // every lane of a pixel's group runs the same number of trips (M and the stride are the same for all of them), so the
     // butterfly below always finds its partners
     for (long m = gt / G; m < M; m += stride) {
-        const float A = sigmoidf_(txf((float)p[m], tp));
+        const float A = sigmoidf_(umi_tx((float)p[m], tp));
         const half8g g = *reinterpret_cast<const half8g*>(dy + m * lddy + cg * 8);
         const half8g v = *reinterpret_cast<const half8g*>(x + m * ldx + cg * 8);
         half8g o;
@@ -142,7 +141,7 @@ __global__ __launch_bounds__(256) void gate_bwd_v8(const half_t* __restrict__ dy
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
             float f = (float)v[j];
-            if (HAS_TX) f = txf(f, t[j]);
+            if (HAS_TX) f = umi_tx(f, t[j]);
             acc = fmaf((float)g[j], f, acc);
             o[j] = (half_t)((float)g[j] * A);
         }
@@ -173,9 +172,9 @@ __global__ __launch_bounds__(256) void add2_relu_fwd_v8(const half_t* __restrict
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
             float fa = (float)va[j], fb = (float)vb[j];
-            if (txa) fa = txf(fa, ta[j]);
-            if (txb) fb = txf(fb, tb[j]);
-            o[j] = (half_t)fmaxf(fa + fb, 0.f);
+            if (txa) fa = umi_tx(fa, ta[j]);
+            if (txb) fb = umi_tx(fb, tb[j]);
+            o[j] = (half_t)umi_relu_keep_nan(fa + fb);
         }
         *reinterpret_cast<half8g*>(y + m * ldy + cg * 8) = o;
     }
@@ -192,7 +191,7 @@ __global__ __launch_bounds__(256) void add2_relu_bwd_v8(const half_t* __restrict
         const half8g v = *reinterpret_cast<const half8g*>(y + m * ldy + cg * 8);
         half8g o;
 #pragma unroll
-        for (int j = 0; j < 8; ++j) o[j] = (float)v[j] > 0.f ? g[j] : (half_t)0.f;
+        for (int j = 0; j < 8; ++j) o[j] = umi_relu_open((float)v[j], 0.f) ? g[j] : (half_t)0.f;
         *reinterpret_cast<half8g*>(da + m * ldda + cg * 8) = o;
         *reinterpret_cast<half8g*>(db + m * lddb + cg * 8) = o;
     }

@@ -352,7 +352,8 @@ __device__ __forceinline__ void bn_finalize_channel(int c, double sum, double su
     double rstd = 1.0 / sqrt(var + (double)eps);
     float g = gamma ? gamma[c] : 1.f, b = beta ? beta[c] : 0.f;
     const double scale = (double)g * rstd;
-    tx_out[c] = make_float4((float)mean, (float)scale, (float)((double)b - mean * scale), 0.f);
+    const float scf = (float)scale, shf = (float)((double)b - mean * scale);
+    tx_out[c] = make_float4((float)mean, scf, shf, umi_tx_lo(scf, shf));      // lo = NaN for non-finite statistics (common.h)
     if (rstd_out) rstd_out[c] = (float)rstd;
     if (rmean) rmean[c] = (1.f - momentum) * rmean[c] + momentum * (float)mean;
     if (rvar) {
@@ -511,7 +512,7 @@ __global__ void pool2_fwd_kernel(const T* __restrict__ x, int ldx, const float4*
                 int h = 2 * ho + (d >> 1), w = 2 * wo + (d & 1);
                 float v = (float)x[((long)((long)n * H + h) * W + w) * ldx + c];
                 if (tx) v = umi_tx(v, tx[c]);
-                m = (v > m) ? v : m;
+                m = (v > m || v != v) ? v : m;      // a NaN in the window is the result (F.max_pool2d); the last one stays
             }
             y[((long)((long)n * Ho + ho) * Wo + wo) * ldy + c] = (T)m;
         }
@@ -627,7 +628,7 @@ __global__ __launch_bounds__(256) void bn_bwd_reduce1_kernel(const T* __restrict
                 float yv = (float)y[r * ldy + c];
                 float g = (float)da[r * ldda + c];
                 float z = umi_tx_pre(yv, t);
-                float dz = z > t.w ? g : 0.f;
+                float dz = umi_relu_open(z, t.w) ? g : 0.f;
                 s += dz;
                 q = fmaf(dz, (yv - t.x) * rs, q);
             }

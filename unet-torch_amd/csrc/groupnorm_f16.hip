@@ -59,7 +59,7 @@ __global__ __launch_bounds__(256) void gn_rowsum_v8(const half_t* __restrict__ x
         if (MODE == 0) { float f = (float)xv_[j] - mu[j]; a[j] += f; b[j] = fmaf(f, f, b[j]); }                   \
         else {                                                                                                    \
             float dz = (float)gv_[j];                                                                             \
-            if (relu && !((float)yv_[j] > 0.f)) dz = 0.f;                                                         \
+            if (relu && !umi_relu_open((float)yv_[j], 0.f)) dz = 0.f;                                                \
             a[j] = fmaf(dz, ((float)xv_[j] - mu[j]) * rs[j], a[j]);                                               \
             b[j] += dz;                                                                                           \
         }                                                                                                         \
@@ -163,7 +163,7 @@ __global__ __launch_bounds__(256) void gn_apply_fin_kernel(const half_t* __restr
         _Pragma("unroll") for (int j = 0; j < 8; ++j) {                 /* gn_apply8_kernel's expression */        \
             float v = ((float)xv_[j] - m[j]) * rr[j] * gg[j] + bb[j];                                             \
             if (res) v += (float)rv_[j];                                                                          \
-            if (relu) v = fmaxf(v, 0.f);                                                                          \
+            if (relu) v = umi_relu_keep_nan(v);                                                                     \
             o[j] = (half_t)v;                                                                                     \
         }                                                                                                         \
         *reinterpret_cast<half8*>(y + (row_) * ldy + cg * 8) = o;                                                 \
@@ -238,7 +238,7 @@ __global__ __launch_bounds__(256) void gn_bwd_apply_fin_kernel(const half_t* __r
         half8 o, dz8;                                                                                             \
         _Pragma("unroll") for (int j = 0; j < 8; ++j) {                 /* gn_bwd_apply8_kernel's expression */    \
             float dz = (float)gv_[j];                                                                             \
-            if (relu && !((float)yv_[j] > 0.f)) dz = 0.f;                                                         \
+            if (relu && !umi_relu_open((float)yv_[j], 0.f)) dz = 0.f;                                                \
             const float xh = ((float)xv_[j] - m[j]) * rr[j];                                                      \
             o[j] = (half_t)(rr[j] * (dz * gg[j] - q1[j] - xh * q2[j]));                                           \
             dz8[j] = (half_t)dz;                                                                                  \

@@ -377,7 +377,7 @@ __global__ __launch_bounds__(256) void smallk1x1_bnred_kernel(const half_t* __re
             for (int k = 0; k < NC; ++k) a = fmaf(d[k], w[k][j], a);
             o[j] = (half_t)a;
             const float yy = (float)yv[j];
-            const float dz = umi_tx_pre(yy, t[j]) > t[j].w ? (float)o[j] : 0.f;
+            const float dz = umi_relu_open(umi_tx_pre(yy, t[j]), t[j].w) ? (float)o[j] : 0.f;
             s[j] += dz;
             q[j] = fmaf(dz, (yy - t[j].x) * rs[j], q[j]);
             if (wpart) {

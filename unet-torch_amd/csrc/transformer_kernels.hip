@@ -145,7 +145,7 @@ __global__ void gn_apply_kernel(const T* __restrict__ x, int ldx, const float* _
         int sg = n * G + c / Cg;
         float v = ((float)x[p * ldx + c] - mean[sg]) * rstd[sg] * gamma[c] + beta[c];
         if (res) v += (float)res[p * ldr + c];
-        if (relu) v = fmaxf(v, 0.f);
+        if (relu) v = umi_relu_keep_nan(v);
         y[p * ldy + c] = (T)v;
     }
 }
@@ -169,7 +169,7 @@ __global__ __launch_bounds__(256) void gn_bwd_reduce_kernel(const T* __restrict_
         for (long p = threadIdx.x; p < HW; p += 256) {
             long row = (long)n * HW + p;
             float dz = (float)dy[row * lddy + c];
-            if (relu && !((float)y[row * ldy + c] > 0.f)) dz = 0.f;
+            if (relu && !umi_relu_open((float)y[row * ldy + c], 0.f)) dz = 0.f;
             float xh = ((float)x[row * ldx + c] - m) * r;
             a = fmaf(dz, xh, a);
             b += dz;
@@ -198,7 +198,7 @@ __global__ void gn_bwd_apply_kernel(const T* __restrict__ dy, int lddy, const T*
         int n = (int)(p / HW);
         int sg = n * G + c / Cg;
         float dz = (float)dy[p * lddy + c];
-        if (relu && !((float)y[p * ldy + c] > 0.f)) dz = 0.f;
+        if (relu && !umi_relu_open((float)y[p * ldy + c], 0.f)) dz = 0.f;
         float xh = ((float)x[p * ldx + c] - mean[sg]) * rstd[sg];
         float v = rstd[sg] * (dz * gamma[c] - gsum[sg * 2 + 0] * invm - xh * gsum[sg * 2 + 1] * invm);
         dx[p * lddx + c] = (T)v;
@@ -221,7 +221,7 @@ __global__ void pool3s2_fwd_kernel(const T* __restrict__ x, int ldx, T* __restri
         float m = -INFINITY;
         for (int d = 0; d < 9; ++d) {
             float v = (float)x[((long)((long)n * H + 2 * ho + d / 3) * W + 2 * wo + d % 3) * ldx + c];
-            m = v > m ? v : m;
+            m = (v > m || v != v) ? v : m;          // a NaN in the window is the result (F.max_pool2d)
         }
         y[p * ldy + c] = (T)m;
     }
@@ -247,7 +247,7 @@ __global__ void pool3s2_bwd_kernel(const T* __restrict__ dy, int lddy, const T* 
                 int best = 0;
                 for (int d = 0; d < 9; ++d) {
                     float v = (float)x[((long)((long)n * H + 2 * ho + d / 3) * W + 2 * wo + d % 3) * ldx + c];
-                    if (d == 0 || v > m) { m = v; best = d; }
+                    if (d == 0 || v > m || v != v) { m = v; best = d; }       // (the forward's rule: a NaN tap wins)
                 }
                 if (2 * ho + best / 3 == h && 2 * wo + best % 3 == w)
                     acc += (float)dy[((long)((long)n * Ho + ho) * Wo + wo) * lddy + c];

@@ -42,10 +42,17 @@ def _fuse_bnapply(Ci):
     return mode != "0" and (Ci <= int(os.environ.get("UMI_BNAPPLY_MAXCI", "64")) or mode == "all")
 
 
+def _fill_cancelled(_, items, tape):
+    """The deferred kind "cancelled": items (gradient, dbeta) -> gradient = dbeta - dbeta, all of them in two launches."""
+    gs, ds = [g for g, _ in items], [d for _, d in items]
+    torch._foreach_copy_(gs, ds)
+    torch._foreach_sub_(gs, ds)
+
+
 class Act:
     """Lazily-activated NHWC tensor.  `raw` is an [N,H,W,C] view, `tx` the consumer transform
     (None = consume as stored).  `grad` = d loss / d activated value (same layout/dtype)."""
-    __slots__ = ("raw", "tx", "grad", "parts", "needs_grad", "bn_rstd", "bn_part", "bn_part_at", "gives")
+    __slots__ = ("raw", "tx", "grad", "parts", "needs_grad", "bn_rstd", "bn_part", "bn_part_at", "gives", "cancel_probe")
 
     def __init__(self, raw, tx=None, parts=None, needs_grad=True):
         self.raw, self.tx, self.grad, self.parts, self.needs_grad = raw, tx, None, parts, needs_grad
@@ -55,6 +62,7 @@ class Act:
                                   # conv_bn(..., input_exclusive=True), or the max-pool backward)
         self.gives = 0            # gradient contributions received so far; `bn_part` is valid iff bn_part_at == gives
         self.bn_part_at = -1
+        self.cancel_probe = None  # set by a consuming conv_bn's backward: its sum_dz, see conv_transpose2x2(bias_cancelled=True)
 
     @property
     def shape(self):
@@ -93,8 +101,7 @@ class Tape:
         d = self.deferred = Deferred(self)
         d.register("wgrad_reduce", lambda _, items, tape: ops.wgrad_reduce_flush(items),     # split-K reductions, 16 per launch
                    on=lambda tape: (tape.grad_sink is None or tape.deferred.marks) and _defer_wgrad_reduce())
-        d.register("zero", lambda _, items, tape: torch._foreach_zero_(items),               # conv bias under a BatchNorm
-                   on=lambda tape: tape.grad_sink is None)
+        d.register("cancelled", _fill_cancelled, on=lambda tape: tape.grad_sink is None)     # conv bias under a BatchNorm
         self._inputs = []
         self.conv3x3_flags = 0            # compute_dtype "fp32_mfma": lib.CONV_F32_MFMA, OR-ed into the 3x3 convolutions' calls
         self.conv1x1_flags = 0            # "fp32_mfma_gemm": lib.CONV_F32_MFMA_1X1, OR-ed into the pointwise convolutions' calls
@@ -246,7 +253,7 @@ class Tape:
             if bias is not None:
                 tx[:, 2] += tx[:, 1] * bias.detach().float()
             if not relu:
-                tx[:, 3] = ops.NEG_INF
+                tx[:, 3] += ops.NEG_INF               # 0 -> -inf; a NaN (non-finite statistics) stays
             if ops.conv3x3_fwd_act(a.raw, a.tx, self._pack("conv_fwd", weight, wf, True), tx, out):
                 return Act(out, None)
         # the pointwise matrix-core kernel has no statistics epilogue: a 1x1 conv that feeds a BatchNorm (attention gates) runs
@@ -289,7 +296,7 @@ class Tape:
             if bias is not None:
                 tx[:, 2] += tx[:, 1] * bias.detach().float()
         if not relu:
-            tx[:, 3] = ops.NEG_INF
+            tx[:, 3] += ops.NEG_INF                   # 0 -> -inf; a NaN (non-finite statistics) stays
         o = Act(out, tx)
         o.bn_rstd = rstd
         if self.record:
@@ -350,12 +357,15 @@ class Tape:
                 self._set_pgrad(weight, gw)
                 if bias is not None:
                     gb = self._new_pgrad(bias)
-                    # d/d bias of BatchNorm(conv + bias) vanishes identically: zero-filled with the other such gradients by ONE
-                    # multi-tensor launch at the end of the backward pass (18 fills per U-Net step otherwise); with a gradient
-                    # sink the slot must be final before it is handed over
-                    if not self.deferred.defer("zero", None, gb, fills=(gb,)):
-                        gb.zero_()
+                    # d/d bias of BatchNorm(conv + bias) vanishes identically: it is sum(dz) - M * mean(dz), written as
+                    # dbeta - dbeta -- +0 for every finite dbeta, NaN where dbeta is not finite (torch's gradient of a step whose
+                    # loss is NaN; a GradGuard must see it).  Filled with the other such gradients by two multi-tensor launches at
+                    # the end of the backward pass (18 fills per U-Net step otherwise); with a gradient sink the slot must be
+                    # final before it is handed over
+                    if not self.deferred.defer("cancelled", None, (gb, dbeta), fills=(gb,), reads=(dbeta,)):
+                        torch.sub(dbeta, dbeta, out=gb)
                     self._set_pgrad(bias, gb)
+                a.cancel_probe = dbeta
                 if _wants_grad(a):
                     if stride != 1:
                         raise NotImplementedError("dgrad for strided conv_bn")
@@ -466,7 +476,9 @@ class Tape:
         buffer, spatial size = the skip's), centred like F.pad in reference Model.py:69-73.
         bias_cancelled: the output feeds only an unpadded 1x1 conv followed by a training-mode BatchNorm (the attention gate's
         `up` -> `W_q`): the bias is a per-channel constant that the BatchNorm subtracts again, its gradient vanishes identically
-        and is written as zeros instead of a column sum over the upsampled gradient."""
+        and is written as zeros instead of a column sum over the upsampled gradient -- as s - s, s = the sum of the consuming
+        conv_bn's sum_dz (`cancel_probe`, which that conv_bn's backward leaves on THIS op's output Act), so that a non-finite
+        BatchNorm gradient leaves a NaN here as it does in torch; plain zeros if no conv_bn has consumed the output."""
         Cin, Cout = weight.shape[:2]
         N, h, w, Ca = a.shape
         assert Ca == Cin
@@ -500,7 +512,13 @@ class Tape:
                 if bias is not None:
                     gb = self._new_pgrad(bias)
                     if bias_cancelled and self.training and not (dY or dX):
-                        gb.zero_()
+                        # zeros -- or NaN when the BatchNorm that cancels the bias saw a non-finite gradient (its sum_dz, left on
+                        # `o` by that conv_bn's backward, which has run by now): s - s is +0 for a finite s
+                        if o.cancel_probe is None:
+                            gb.zero_()
+                        else:
+                            s = o.cancel_probe.sum()
+                            gb.copy_(s - s)
                     elif os.environ.get("UMI_NO_CONVT_BIAS_FUSION") != "1" and ops.convT_wgrad_bias(g, a.raw, a.tx, gw, gb, inv,
                                                                                                     defer=dlist):
                         fused = True                     # the bias gradient rode on the weight gradient's pass over g

@@ -80,8 +80,11 @@ def eval_bn_tx(weight, bias, running_mean, running_var, eps):
     """Consumer transform for BatchNorm in eval mode (running statistics) + ReLU."""
     rstd = torch.rsqrt(running_var.float() + eps)
     scale = weight.float() * rstd
-    return torch.stack([running_mean.float(), scale, bias.float() - running_mean.float() * scale,
-                        torch.zeros_like(rstd)], dim=1).contiguous(), rstd
+    shift = bias.float() - running_mean.float() * scale
+    # lo = 0, or NaN where scale or shift is not finite (x * 0 is NaN for x = +-Inf / NaN): the rule of the device finalize,
+    # umi_tx_lo in csrc/common.h -- max(NaN, NaN) keeps such a channel NaN in every consumer
+    lo = torch.abs(scale * 0.0 + shift * 0.0)
+    return torch.stack([running_mean.float(), scale, shift, lo], dim=1).contiguous(), rstd
 
 
 # ------------------------------------------------------------------------------------------
