@@ -593,7 +593,8 @@ int umi_mt_ratio_bwd(const float* o1, const float* o2, const float* l1, const fl
  *   SGD:  g += wd*p; m = first_step ? g : momentum*m + (1-dampening)*g; g = nesterov ? g + momentum*m : m; p -= lr*g
  *         (s0 = momentum buffer, NULL when momentum == 0; s1 unused)
  *   Adam: g += wd*p; m += (1-beta1)*(g-m); v = beta2*v + (1-beta2)*g*g; p -= step_size * m / (sqrt(v)/bc2_sqrt + eps)
- *         (s0 = exp_avg, s1 = exp_avg_sq; step_size = lr / (1-beta1^t), bc2_sqrt = sqrt(1-beta2^t), computed by the host) */
+ *         (s0 = exp_avg, s1 = exp_avg_sq; step_size = lr / (1-beta1^t), bc2_sqrt = sqrt(1-beta2^t), computed by the host)
+ *   AdamW (umi_optim_adamw_multi*, below): p *= (float)(1 - lr*wd), then Adam with wd = 0 */
 typedef struct umi_optim_desc {
     float* p;            /* parameter (fp32 master), updated in place */
     const float* g;      /* gradient */
@@ -624,16 +625,39 @@ int umi_optim_adam_multi(const void* descs, int n_desc, int total_blocks, double
  * The host fills the block once (umi_table_upload) and reads it back when it wants param_group['lr'] / state['step']. */
 typedef struct umi_optim_hyper {
     double lr, base_lr, iter, max_iter, power, adam_t, beta1, beta2;
-    float lr_f, step_size_f, bc2_sqrt_f, pad_;
-    double pad2_[2];
+    float lr_f, step_size_f, bc2_sqrt_f;
+    int kind;                              /* UMI_SCHED_*; read by umi_optim_hyper_schedule only */
+    double warmup, final_ratio;            /* (kind, warmup, final_ratio all zero: a block as it was before the schedule rule) */
 } umi_optim_hyper;                         /* 96 bytes */
 size_t umi_optim_hyper_bytes(void);
 int umi_optim_hyper_pre(void* hyper, int adam, umi_stream_t stream);
 int umi_optim_hyper_poly(void* hyper, umi_stream_t stream);
+/* Warm-up + decay schedule, run after the update of a group where umi_optim_hyper_poly would run (one thread, all in double):
+ *     iter += 1;  lr = base_lr * factor(iter)
+ *     factor(k) = w(k) * (final_ratio + (1 - final_ratio) * s(k))
+ *     w(k) = warmup > 0 ? min(1, (k + 1) / warmup) : 1
+ *     x    = min(k, max_iter) / max_iter
+ *     s(k) = UMI_SCHED_POLY: (1 - x)^power   UMI_SCHED_COSINE: 0.5 * (1 + cos(pi * x))   UMI_SCHED_CONSTANT (and NONE): 1
+ * Step k, counted from 0, uses base_lr * factor(k): unlike the poly rule above this one has no lag, so whoever fills the block
+ * writes lr = base_lr * factor(iter) into it.  `iter` counts attempted steps: a step the guard skips advances it too. */
+enum { UMI_SCHED_NONE = 0, UMI_SCHED_POLY = 1, UMI_SCHED_COSINE = 2, UMI_SCHED_CONSTANT = 3 };
+int umi_optim_hyper_schedule(void* hyper, umi_stream_t stream);
 int umi_optim_sgd_multi_dev(const void* descs, int n_desc, int total_blocks, const void* hyper, double momentum,
                             double dampening, double weight_decay, int nesterov, int first_step, umi_stream_t stream);
 int umi_optim_adam_multi_dev(const void* descs, int n_desc, int total_blocks, const void* hyper, double beta1, double beta2,
                              double eps, double weight_decay, umi_stream_t stream);
+/* AdamW (torch.optim.AdamW = Adam with decoupled_weight_decay): the Adam entry points with the weight decay taken out of the
+ * gradient.  Per element, in torch's order:
+ *     weight_decay != 0:  p = p * (float)(1 - lr * weight_decay)     (param.mul_(1 - lr * wd): lr and wd doubles, the factor
+ *                                                                     formed in double, ONE rounding to fp32, one fp32 multiply)
+ *     then the Adam update above with wd = 0.
+ * `lr` is the learning rate of THIS step: the block's double `lr` when `hyper` is given (_dev; _guarded with hyper != NULL), the
+ * `lr` argument otherwise (step_size = lr / (1 - beta1^t) does not determine it).  Descriptor table, blocks, 16-byte path and
+ * status codes as for umi_optim_adam_multi*; the guarded form stores nothing on a skipped step, so it applies no decay either. */
+int umi_optim_adamw_multi(const void* descs, int n_desc, int total_blocks, double lr, double step_size, double beta1,
+                          double beta2, double bc2_sqrt, double eps, double weight_decay, umi_stream_t stream);
+int umi_optim_adamw_multi_dev(const void* descs, int n_desc, int total_blocks, const void* hyper, double beta1, double beta2,
+                              double eps, double weight_decay, umi_stream_t stream);
 
 /* Guarded optimizer step: non-finite check, global gradient-norm clipping and a dynamic loss scale, all on the device so that a
  * captured HIP graph keeps deciding per step.  The state is a DEVICE array of UMI_GUARD_LEN doubles (8-byte aligned; the
@@ -679,6 +703,9 @@ int umi_optim_sgd_multi_guarded(const void* descs, int n_desc, int total_blocks,
 int umi_optim_adam_multi_guarded(const void* descs, int n_desc, int total_blocks, const void* hyper, double step_size,
                                  double beta1, double beta2, double bc2_sqrt, double eps, double weight_decay,
                                  const double* guard, umi_stream_t stream);
+int umi_optim_adamw_multi_guarded(const void* descs, int n_desc, int total_blocks, const void* hyper, double lr, double step_size,
+                                  double beta1, double beta2, double bc2_sqrt, double eps, double weight_decay,
+                                  const double* guard, umi_stream_t stream);
 
 /* Replica fingerprint (data parallel: every rank must hold bit-identical parameters).  One 64-bit word over the tensors of a
  * umi_optim_desc table; only `p`, `n` and `blk0` are read (blocks of umi_optim_block_elems() words, as for the optimizer), the

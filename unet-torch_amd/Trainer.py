@@ -50,6 +50,12 @@ from it, bit for bit; `snapshot_run_state()` / `restore_run_state()` roll a live
 `Trainer(..., ema=...)` (keyword-only; None / False, True, a float, `dict(decay=0.999, warmup=True, validate=True)` or a
 `umi.ema.ModelEMA`): an exponential moving average of the weights, updated inside the step and, with `validate`, validated and
 saved in place of the live weights.  See umi/ema.py.
+`Trainer(..., lr_schedule=dict(kind='cosine' | 'poly' | 'constant', warmup=0, power=0.9, final_ratio=0.0, max_iterations=None))`
+(keyword-only; not together with a truthy `lr_scheduler`): linear warm-up and decay per step, `umi.optim.schedule_lr`, with each
+param group's own `lr` as its base and `iter_num` counted across epochs (and carried by `resume`).  `max_iterations` defaults to
+num_epochs * len(train loader).  With a `umi.optim` optimizer the rule always lives in the device block
+(`optimizer.device_schedule(schedule=...)`), eager or replayed; with a torch optimizer the Trainer writes
+`param_groups[i]['lr']` on the host before each step.
 `lr_scheduler=True` (what the reference's train.py passes) crashes the reference in its first validation after epoch 5
 (`True.step`); here train() raises NotImplementedError before the first step whenever the run would reach that point.
 The remaining epoch loops of the reference (uncertainty-weighted multi-task, CLTR, Topo losses) are out of scope and raise.
@@ -76,7 +82,7 @@ class Trainer():
     def __init__(self, model, model_type, dtype, device, output_save_dir, dataloaders, batch_size, optimizer,
                  patience, num_epochs, loss_function, accuracy_metric, lr_scheduler=None, start_epoch=1, *, graph=None,
                  batch_transform=None, grad_guard=None, data_parallel=None, val_batch=None, val_confusion=False,
-                 async_checkpoints=False, resume=None, ema=None):
+                 async_checkpoints=False, resume=None, ema=None, lr_schedule=None):
         self.model = model
         self.model_type = model_type
         self.dtype = dtype
@@ -106,6 +112,16 @@ class Trainer():
         self.graph = (os.environ.get("UMI_TRAINER_GRAPH") == "1") if graph is None else bool(graph)
         self._graphs, self._seen_shapes, self._dev_sched, self._side = {}, set(), False, None
         self.batch_transform = batch_transform
+        # warm-up + decay rule: the checked dict (None: off) and each param group's base LR
+        self._lr_schedule, self._sched_base = None, [g['lr'] for g in self.optimizer.param_groups]
+        if lr_schedule is not None:
+            if lr_scheduler:
+                raise ValueError("lr_schedule and lr_scheduler are two learning-rate rules: pass one of them")
+            from umi.optim import check_schedule
+            if isinstance(lr_schedule, dict) and 'iter_num' in lr_schedule:
+                raise ValueError("lr_schedule: iter_num is the Trainer's own count (Trainer.iter_num), not a setting")
+            self._lr_schedule = check_schedule(lr_schedule, "Trainer(lr_schedule=...)", max_iterations=self.max_iterations)
+            del self._lr_schedule['iter_num']
         self._guard, self._guard_seen = self._make_guard(grad_guard), (0, 0)
         # multi_task_trainRatio: epoch > 5 (host, and in graph mode a device flag), ratioAccuracy of the last step
         self._ratio_gate, self._gate_dev, self._ratio = False, None, None
@@ -232,10 +248,23 @@ class Trainer():
         self._guard.attach(self.model)
 
     def _device_schedule(self):
+        if not self._dev_sched and self._lr_schedule is not None:
+            self.optimizer.device_schedule(schedule=dict(self._lr_schedule, iter_num=self.iter_num))
+            self._dev_sched = True
         if not self._dev_sched:
             poly = dict(base_lr=self.base_lr, max_iterations=self.max_iterations, power=0.9, iter_num=self.iter_num)
             self.optimizer.device_schedule(poly=poly if self.lr_scheduler else None)
             self._dev_sched = True
+
+    def _schedule_on_device(self, on_device):
+        """lr_schedule with a umi.optim optimizer: the rule lives in the device block, in the eager step too."""
+        return self._lr_schedule is not None and on_device and hasattr(self.optimizer, "device_schedule")
+
+    def _host_schedule(self):
+        """lr_schedule with a torch optimizer: the LR of step `iter_num` into every param group, before the step."""
+        from umi.optim import schedule_lr
+        for group, base in zip(self.optimizer.param_groups, self._sched_base):
+            group['lr'] = schedule_lr(self.iter_num, base, **self._lr_schedule)
 
     def _log_guard(self, say, epoch):
         if self._guard is None:
@@ -369,8 +398,10 @@ class Trainer():
         if self._graph_capable(inputs):
             return self._graphed_train_step(inputs, labels)
         guarded_adam = self._guard is not None and "betas" in self.optimizer.param_groups[0]
-        if guarded_adam:
-            self._device_schedule()           # the step count advances on the device, and the poly rule with it
+        if guarded_adam or self._schedule_on_device(inputs.is_cuda):
+            self._device_schedule()           # the step count advances on the device, and the LR rule with it
+        elif self._lr_schedule is not None:
+            self._host_schedule()
         loss = self._step_body(inputs, labels)
         if self.lr_scheduler and not guarded_adam:
             lr_ = self.base_lr * (1.0 - self.iter_num / self.max_iterations) ** 0.9
@@ -479,6 +510,10 @@ class Trainer():
         return log, say
 
     def _print_lr(self, log):
+        if self._schedule_on_device(self._model_device().type == "cuda"):
+            self._device_schedule()           # the LR of the next step is the rule's, before the first step too
+        elif self._lr_schedule is not None and not self._dev_sched:
+            self._host_schedule()
         if self._dev_sched:
             self.optimizer.sync_host()        # the LR lives on the device in graph mode
         for group in self.optimizer.param_groups:

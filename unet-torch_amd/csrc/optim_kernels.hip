@@ -31,8 +31,9 @@ __device__ inline int find_desc(const D* d, int n, int blk) {
 // with the roundings torch applies to its Python doubles.
 struct Hyper {
     double lr, base_lr, iter, max_iter, power, adam_t, beta1, beta2;
-    float lr_f, step_size_f, bc2_sqrt_f, pad_;
-    double pad2_[2];
+    float lr_f, step_size_f, bc2_sqrt_f;
+    int kind;                            // UMI_SCHED_*: what hyper_schedule_kernel applies (0: none installed)
+    double warmup, final_ratio;
 };
 static_assert(sizeof(Hyper) == 96, "umi_optim_hyper is 96 bytes");
 
@@ -53,7 +54,19 @@ __device__ inline void sgd_one(float& p, float g, float& m, const SgdArgs a) {
 
 struct AdamArgs { float step_size, omb1, beta2, omb2, bc2_sqrt, eps, wd; const Hyper* hp; };   // omb = 1 - beta, rounded from double
 
-__device__ inline void adam_one(float& p, float g, float& m, float& v, const AdamArgs a) {
+// AdamW (decoupled weight decay): the Adam arguments with wd = 0, plus what the decay factor is formed from, in double.  `lr` is
+// this step's learning rate when there is no hyper block (step_size = lr / bc1 does not determine it).
+struct AdamWArgs { float step_size, omb1, beta2, omb2, bc2_sqrt, eps, wd; const Hyper* hp; double lr, wd_d; };
+
+// (float)(1 - lr * wd) with the two roundings of the Python doubles torch forms it from: no fused multiply-add
+__device__ inline float adamw_decay(double lr, double wd) {
+#pragma clang fp contract(off)
+    const double prod = lr * wd;
+    return (float)(1.0 - prod);
+}
+
+template <typename A>
+__device__ inline void adam_one(float& p, float g, float& m, float& v, const A a) {
     if (a.wd != 0.f) g = fmaf(a.wd, p, g);                            // grad.add(param, alpha=wd)  (L2, not AdamW)
     m = fmaf(a.omb1, g - m, m);                                        // exp_avg.lerp_(grad, 1-beta1)
     v = fmaf(a.omb2 * g, g, __fmul_rn(v, a.beta2));                   // exp_avg_sq.mul_(beta2).addcmul_(g, g, 1-beta2)
@@ -64,7 +77,10 @@ __device__ inline void adam_one(float& p, float g, float& m, float& v, const Ada
 // GUARD: the step is conditional on the device guard block (umi_grad_guard_finalize): nothing is stored on a skipped step, and
 // every gradient is multiplied by (float)COEF -- one fp32 rounding, as a torch multiply of the gradient would make -- before the
 // unchanged sgd_one / adam_one.  Without GUARD the body is the one the unguarded entry points have always run.
-template <bool ADAM, bool GUARD, typename A>
+// DECOUPLED (AdamW, A = AdamWArgs): param.mul_(1 - lr * weight_decay) first -- the factor formed in double from THIS step's
+// learning rate (the block's `lr` when there is one) and rounded once -- then adam_one with wd = 0.  A skipped step returns
+// before it: no decay either.
+template <bool ADAM, bool GUARD, typename A, bool DECOUPLED = false>
 __device__ __forceinline__ void optim_multi_body(const umi_optim_desc* __restrict__ descs, int n_desc, A a,
                                                  const double* __restrict__ guard) {
     bool skip = false;
@@ -78,6 +94,13 @@ __device__ __forceinline__ void optim_multi_body(const umi_optim_desc* __restric
         if constexpr (ADAM) { a.step_size = a.hp->step_size_f; a.bc2_sqrt = a.hp->bc2_sqrt_f; }
         else a.lr = a.hp->lr_f;
     }
+    float decay = 1.f;
+    bool decays = false;
+    if constexpr (DECOUPLED) {
+        decays = a.wd_d != 0.0;
+        if (decays) decay = adamw_decay(a.hp ? a.hp->lr : a.lr, a.wd_d);
+    }
+    const auto dk = [decay, decays](float p) { return (DECOUPLED && decays) ? __fmul_rn(p, decay) : p; };
     const int blk = blockIdx.x;
     const umi_optim_desc d = descs[find_desc(descs, n_desc, blk)];
     const long base = (long)(blk - d.blk0) * OPT_BLOCK;
@@ -105,6 +128,7 @@ __device__ __forceinline__ void optim_multi_body(const umi_optim_desc* __restric
             float4 mv = s0 ? *reinterpret_cast<float4*>(s0 + i) : make_float4(0.f, 0.f, 0.f, 0.f);
             float4 vv = (ADAM && s1) ? *reinterpret_cast<float4*>(s1 + i) : make_float4(0.f, 0.f, 0.f, 0.f);
             if constexpr (ADAM) {
+                if constexpr (DECOUPLED) pv = make_float4(dk(pv.x), dk(pv.y), dk(pv.z), dk(pv.w));
                 adam_one(pv.x, gv.x, mv.x, vv.x, a); adam_one(pv.y, gv.y, mv.y, vv.y, a);
                 adam_one(pv.z, gv.z, mv.z, vv.z, a); adam_one(pv.w, gv.w, mv.w, vv.w, a);
                 *reinterpret_cast<float4*>(s1 + i) = vv;
@@ -119,7 +143,7 @@ __device__ __forceinline__ void optim_multi_body(const umi_optim_desc* __restric
         const int i = tail0 + threadIdx.x;
         if (i < cnt) {
             float pv = p[i], mv = s0 ? s0[i] : 0.f;
-            if constexpr (ADAM) { float vv = s1[i]; adam_one(pv, gs(g[i]), mv, vv, a); s1[i] = vv; }
+            if constexpr (ADAM) { float vv = s1[i]; pv = dk(pv); adam_one(pv, gs(g[i]), mv, vv, a); s1[i] = vv; }
             else sgd_one(pv, gs(g[i]), mv, a);
             p[i] = pv;
             if (s0) s0[i] = mv;
@@ -127,7 +151,7 @@ __device__ __forceinline__ void optim_multi_body(const umi_optim_desc* __restric
     } else {
         for (int i = threadIdx.x; i < cnt; i += 256) {
             float pv = p[i], mv = s0 ? s0[i] : 0.f;
-            if constexpr (ADAM) { float vv = s1[i]; adam_one(pv, gs(g[i]), mv, vv, a); s1[i] = vv; }
+            if constexpr (ADAM) { float vv = s1[i]; pv = dk(pv); adam_one(pv, gs(g[i]), mv, vv, a); s1[i] = vv; }
             else sgd_one(pv, gs(g[i]), mv, a);
             p[i] = pv;
             if (s0) s0[i] = mv;
@@ -135,15 +159,15 @@ __device__ __forceinline__ void optim_multi_body(const umi_optim_desc* __restric
     }
 }
 
-template <bool ADAM, typename A>
+template <bool ADAM, typename A, bool DECOUPLED = false>
 __global__ __launch_bounds__(256) void optim_multi_kernel(const umi_optim_desc* __restrict__ descs, int n_desc, A a) {
-    optim_multi_body<ADAM, false, A>(descs, n_desc, a, nullptr);
+    optim_multi_body<ADAM, false, A, DECOUPLED>(descs, n_desc, a, nullptr);
 }
 
-template <bool ADAM, typename A>
+template <bool ADAM, typename A, bool DECOUPLED = false>
 __global__ __launch_bounds__(256) void optim_multi_guarded_kernel(const umi_optim_desc* __restrict__ descs, int n_desc, A a,
                                                                   const double* __restrict__ guard) {
-    optim_multi_body<ADAM, true, A>(descs, n_desc, a, guard);
+    optim_multi_body<ADAM, true, A, DECOUPLED>(descs, n_desc, a, guard);
 }
 
 // ---- gradient guard: per-block sum of squares and non-finite count, then one workgroup that decides the step ----------------
@@ -446,6 +470,19 @@ __global__ void hyper_poly_kernel(Hyper* h) {
     h->iter += 1.0;
 }
 
+// The schedule rule of include/unetmi.h, after the update: iter += 1; lr = base_lr * factor(iter).  No lag: step k (from 0) runs
+// on base_lr * factor(k), which device_schedule wrote for k = iter_num and this kernel writes for every later k.
+__global__ void hyper_schedule_kernel(Hyper* h) {
+    const double k = h->iter + 1.0;
+    h->iter = k;
+    const double w = h->warmup > 0.0 ? fmin(1.0, (k + 1.0) / h->warmup) : 1.0;
+    const double x = fmin(k, h->max_iter) / h->max_iter;
+    double s = 1.0;
+    if (h->kind == UMI_SCHED_POLY) s = pow(1.0 - x, h->power);
+    else if (h->kind == UMI_SCHED_COSINE) s = 0.5 * (1.0 + cos(3.141592653589793 * x));
+    h->lr = h->base_lr * (w * (h->final_ratio + (1.0 - h->final_ratio) * s));
+}
+
 extern "C" size_t umi_optim_hyper_bytes(void) { return sizeof(Hyper); }
 
 extern "C" int umi_optim_hyper_pre(void* hyper, int adam, umi_stream_t stream) {
@@ -458,6 +495,13 @@ extern "C" int umi_optim_hyper_pre(void* hyper, int adam, umi_stream_t stream) {
 extern "C" int umi_optim_hyper_poly(void* hyper, umi_stream_t stream) {
     if (!hyper || ((uintptr_t)hyper & 7)) return UMI_ERR_BADARG;
     hipLaunchKernelGGL(hyper_poly_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, (Hyper*)hyper);
+    UMI_LAUNCH_CHECK();
+    return UMI_OK;
+}
+
+extern "C" int umi_optim_hyper_schedule(void* hyper, umi_stream_t stream) {
+    if (!hyper || ((uintptr_t)hyper & 7)) return UMI_ERR_BADARG;
+    hipLaunchKernelGGL(hyper_schedule_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, (Hyper*)hyper);
     UMI_LAUNCH_CHECK();
     return UMI_OK;
 }
@@ -533,6 +577,41 @@ extern "C" int umi_optim_adam_multi_guarded(const void* descs, int n_desc, int t
     AdamArgs a{(float)step_size, (float)(1.0 - beta1), (float)beta2, (float)(1.0 - beta2), (float)bc2_sqrt, (float)eps,
                (float)weight_decay, (const Hyper*)hyper};
     hipLaunchKernelGGL((optim_multi_guarded_kernel<true, AdamArgs>), dim3(total_blocks), dim3(256), 0, (hipStream_t)stream,
+                       (const umi_optim_desc*)descs, n_desc, a, guard);
+    UMI_LAUNCH_CHECK();
+    return UMI_OK;
+}
+
+// ---- AdamW: the Adam entry points with decoupled weight decay (include/unetmi.h) ---------------------------------------------
+extern "C" int umi_optim_adamw_multi(const void* descs, int n_desc, int total_blocks, double lr, double step_size, double beta1,
+                                     double beta2, double bc2_sqrt, double eps, double weight_decay, umi_stream_t stream) {
+    if (!descs || n_desc <= 0 || total_blocks <= 0) return UMI_ERR_BADARG;
+    AdamWArgs a{(float)step_size, (float)(1.0 - beta1), (float)beta2, (float)(1.0 - beta2), (float)bc2_sqrt, (float)eps, 0.f,
+                nullptr, lr, weight_decay};
+    hipLaunchKernelGGL((optim_multi_kernel<true, AdamWArgs, true>), dim3(total_blocks), dim3(256), 0, (hipStream_t)stream,
+                       (const umi_optim_desc*)descs, n_desc, a);
+    UMI_LAUNCH_CHECK();
+    return UMI_OK;
+}
+
+extern "C" int umi_optim_adamw_multi_dev(const void* descs, int n_desc, int total_blocks, const void* hyper, double beta1,
+                                         double beta2, double eps, double weight_decay, umi_stream_t stream) {
+    if (!descs || !hyper || n_desc <= 0 || total_blocks <= 0) return UMI_ERR_BADARG;
+    AdamWArgs a{0.f, (float)(1.0 - beta1), (float)beta2, (float)(1.0 - beta2), 1.f, (float)eps, 0.f, (const Hyper*)hyper, 0.0,
+                weight_decay};
+    hipLaunchKernelGGL((optim_multi_kernel<true, AdamWArgs, true>), dim3(total_blocks), dim3(256), 0, (hipStream_t)stream,
+                       (const umi_optim_desc*)descs, n_desc, a);
+    UMI_LAUNCH_CHECK();
+    return UMI_OK;
+}
+
+extern "C" int umi_optim_adamw_multi_guarded(const void* descs, int n_desc, int total_blocks, const void* hyper, double lr,
+                                             double step_size, double beta1, double beta2, double bc2_sqrt, double eps,
+                                             double weight_decay, const double* guard, umi_stream_t stream) {
+    if (!descs || !guard || ((uintptr_t)guard & 7) || n_desc <= 0 || total_blocks <= 0) return UMI_ERR_BADARG;
+    AdamWArgs a{(float)step_size, (float)(1.0 - beta1), (float)beta2, (float)(1.0 - beta2), (float)bc2_sqrt, (float)eps, 0.f,
+                (const Hyper*)hyper, lr, weight_decay};
+    hipLaunchKernelGGL((optim_multi_guarded_kernel<true, AdamWArgs, true>), dim3(total_blocks), dim3(256), 0, (hipStream_t)stream,
                        (const umi_optim_desc*)descs, n_desc, a, guard);
     UMI_LAUNCH_CHECK();
     return UMI_OK;

@@ -7,6 +7,11 @@ schedule) work unchanged.  `step()` updates every parameter of a group with ONE 
 (umi_optim_sgd_multi / umi_optim_adam_multi) that follows torch's operation order, instead of torch's 4-10 foreach
 launches per group.
 
+`AdamW` subclasses `torch.optim.AdamW` the same way and shares `Adam.step`: decoupled weight decay (umi_optim_adamw_multi*), also
+what `Adam(..., decoupled_weight_decay=True)` runs.  `device_schedule(schedule=...)` puts a linear warm-up + cosine / poly /
+constant decay into the device block (`schedule_lr` is the rule on the host); `decay_groups` splits a model's parameters into the
+decayed and the not decayed group.
+
 `GradGuard` + `optimizer.grad_guard(guard)`: a non-finite check that skips the step, global gradient-norm clipping and a
 dynamic loss scale, decided on the device inside the step (so a captured HIP graph keeps deciding).
 
@@ -267,8 +272,77 @@ class _Guarded:
                 L.call("umi_optim_hyper_pre_guarded", hyper[gi][0].data_ptr(), int("betas" in self.param_groups[gi]), st, stream)
             for table in tables:
                 launch(table, st)
-            if hyper is not None and self._umi_poly:
-                L.call("umi_optim_hyper_poly", hyper[gi][0].data_ptr(), stream)
+            if hyper is not None:
+                self._advance_schedule(gi)
+
+
+SCHEDULE_KINDS = {k[len("UMI_SCHED_"):].lower(): v for k, v in L.ENUMS.items() if k.startswith("UMI_SCHED_") and v != 0}
+
+
+def check_schedule(spec, what="schedule", max_iterations=None):
+    """A schedule dict -> dict(kind, max_iterations, warmup, power, final_ratio, iter_num), all checked; ValueError otherwise.
+    `max_iterations`: the default for a dict that leaves it out or gives None (Trainer: num_epochs * len(train loader))."""
+    if not isinstance(spec, dict):
+        raise ValueError(f"{what} takes a dict(kind=, max_iterations=, warmup=0, power=0.9, final_ratio=0.0, iter_num=0), "
+                         f"not {spec!r}")
+    extra = set(spec) - {"kind", "max_iterations", "warmup", "power", "final_ratio", "iter_num"}
+    if extra:
+        raise ValueError(f"{what}: unknown keys {sorted(extra)}")
+    kind = spec.get("kind")
+    if kind not in SCHEDULE_KINDS:
+        raise ValueError(f"{what}: kind must be one of {sorted(SCHEDULE_KINDS)}, not {kind!r}")
+    mx = spec.get("max_iterations")
+    mx = max_iterations if mx is None else mx
+    out = dict(kind=kind, max_iterations=mx, warmup=spec.get("warmup", 0), power=spec.get("power", 0.9),
+               final_ratio=spec.get("final_ratio", 0.0), iter_num=spec.get("iter_num", 0))
+    for k, v in out.items():
+        if k != "kind" and (isinstance(v, bool) or not isinstance(v, (int, float)) or not math.isfinite(v)):
+            raise ValueError(f"{what}: {k} must be a finite number, not {v!r}")
+    if not out["max_iterations"] > 0:
+        raise ValueError(f"{what}: max_iterations must be positive, not {out['max_iterations']!r}")
+    if out["warmup"] < 0:
+        raise ValueError(f"{what}: warmup must not be negative, not {out['warmup']!r}")
+    if not 0.0 <= out["final_ratio"] <= 1.0:
+        raise ValueError(f"{what}: final_ratio must be in [0, 1], not {out['final_ratio']!r}")
+    if not out["power"] > 0:
+        raise ValueError(f"{what}: power must be positive, not {out['power']!r}")
+    if out["iter_num"] < 0:
+        raise ValueError(f"{what}: iter_num must not be negative, not {out['iter_num']!r}")
+    return out
+
+
+def schedule_lr(k, base_lr, kind, max_iterations, warmup=0, power=0.9, final_ratio=0.0):
+    """The learning rate of step k (counted from 0) under the warm-up + decay rule of include/unetmi.h
+    (umi_optim_hyper_schedule), in Python doubles and in the kernel's operation order:
+
+        lr(k) = base_lr * (w(k) * (final_ratio + (1 - final_ratio) * s(k)))
+        w(k)  = min(1, (k + 1) / warmup) if warmup > 0 else 1
+        x     = min(k, max_iterations) / max_iterations
+        s(k)  = poly: (1 - x) ** power    cosine: 0.5 * (1 + cos(pi * x))    constant: 1"""
+    w = min(1.0, (k + 1) / warmup) if warmup > 0 else 1.0
+    x = min(k, max_iterations) / max_iterations
+    if kind == "poly":
+        s = (1.0 - x) ** power
+    elif kind == "cosine":
+        s = 0.5 * (1.0 + math.cos(math.pi * x))
+    elif kind == "constant":
+        s = 1.0
+    else:
+        raise ValueError(f"schedule_lr: kind must be one of {sorted(SCHEDULE_KINDS)}, not {kind!r}")
+    return base_lr * (w * (final_ratio + (1.0 - final_ratio) * s))
+
+
+def decay_groups(model, weight_decay, no_decay_names=("position_embeddings",)):
+    """Two param groups over the trainable parameters of `model`, each parameter exactly once: [decayed, not decayed].
+    Not decayed (weight_decay=0): parameters with ndim <= 1 (biases; BatchNorm / GroupNorm / LayerNorm scales and shifts) and
+    parameters whose name ends in one of `no_decay_names`; every other one gets `weight_decay`."""
+    decay, rest, seen = [], [], set()
+    for name, p in model.named_parameters():
+        if not p.requires_grad or id(p) in seen:
+            continue
+        seen.add(id(p))
+        (rest if p.ndim <= 1 or name.endswith(tuple(no_decay_names)) else decay).append(p)
+    return [dict(params=decay, weight_decay=weight_decay), dict(params=rest, weight_decay=0.0)]
 
 
 class _DeviceHyper:
@@ -279,21 +353,40 @@ class _DeviceHyper:
         opt.device_schedule()                                          constant LR (Adam: the step count advances on device)
         opt.device_schedule(poly=dict(base_lr=.., max_iterations=.., power=0.9, iter_num=0))
                                                                        + the reference's poly rule, applied by step() itself
+        opt.device_schedule(schedule=dict(kind='cosine' | 'poly' | 'constant', max_iterations=.., warmup=0, power=0.9,
+                                          final_ratio=0.0, iter_num=0))
+                                                                       + linear warm-up and decay (`schedule_lr`), applied by
+                                                                       step() itself; each param group's base LR is its own
+                                                                       `lr` at this call, and step k runs on rule(k): no lag
 
     From then on `step()` reads the LR from the device block and ignores later edits of `param_groups[i]['lr']`;
     `sync_host()` copies lr / iteration / Adam step back into `param_groups` and `state` (it synchronises; `state_dict()`
     calls it).  Eager and graph-replayed steps are interchangeable in this mode: nothing step-dependent is a kernel argument."""
 
-    def device_schedule(self, poly=None):
+    def device_schedule(self, poly=None, schedule=None):
+        if poly is not None and schedule is not None:
+            raise ValueError("umi.optim: device_schedule() takes poly= or schedule=, not both")
+        if schedule is not None:
+            schedule = check_schedule(schedule, "device_schedule(schedule=...)")
+        return self._build_hyper(poly, schedule, [float(group["lr"]) for group in self.param_groups])
+
+    def _build_hyper(self, poly, schedule, base_lrs):
+        """The blocks of device_schedule(); `base_lrs`: the schedule's base LR per param group."""
         if torch.cuda.is_current_stream_capturing():
             raise RuntimeError("umi.optim: call device_schedule() before the HIP-graph capture")
         blocks = []
-        for group in self.param_groups:
+        for group, base in zip(self.param_groups, base_lrs):
             h = np.zeros(1, dtype=_HYPER)
             h["lr"] = float(group["lr"])
             if poly is not None:
                 h["base_lr"], h["max_iter"] = float(poly["base_lr"]), float(poly["max_iterations"])
                 h["power"], h["iter"] = float(poly.get("power", 0.9)), float(poly.get("iter_num", 0))
+            if schedule is not None:
+                rule = {k: schedule[k] for k in ("kind", "max_iterations", "warmup", "power", "final_ratio")}
+                h["base_lr"], h["max_iter"], h["power"] = base, float(rule["max_iterations"]), float(rule["power"])
+                h["iter"], h["kind"] = float(schedule["iter_num"]), SCHEDULE_KINDS[rule["kind"]]
+                h["warmup"], h["final_ratio"] = float(rule["warmup"]), float(rule["final_ratio"])
+                h["lr"] = schedule_lr(float(schedule["iter_num"]), base, **rule)
             if "betas" in group:
                 h["beta1"], h["beta2"] = (float(b) for b in group["betas"])
                 steps = {float(self.state[p]["step"]) for p in group["params"] if len(self.state.get(p, {}))}
@@ -306,12 +399,19 @@ class _DeviceHyper:
             L.call("umi_table_upload", host.data_ptr(), dev.data_ptr(), _HYPER.itemsize, ops._stream())
             blocks.append((dev, host))
         torch.cuda.current_stream().synchronize()
-        self._umi_hyper, self._umi_poly = blocks, poly is not None
+        self._umi_hyper, self._umi_poly, self._umi_sched = blocks, poly is not None, schedule
         return self
 
     @property
     def device_hyper(self):
         return self.__dict__.get("_umi_hyper")
+
+    def _advance_schedule(self, gi):
+        """After the update of group `gi` (device block present): the installed learning-rate rule, if any."""
+        if self._umi_poly:
+            L.call("umi_optim_hyper_poly", self._umi_hyper[gi][0].data_ptr(), ops._stream())
+        elif self._umi_sched is not None:
+            L.call("umi_optim_hyper_schedule", self._umi_hyper[gi][0].data_ptr(), ops._stream())
 
     def sync_host(self):
         """Device block -> param_groups[i]['lr'] (and Adam state['step']); returns the list of blocks as numpy records."""
@@ -347,10 +447,16 @@ class _DeviceHyper:
     def load_state_dict(self, state_dict):
         """Loading a state dict rewrites param_groups[i]['lr'] and Adam's step counts on the host; with a device schedule active
         the device block is what step() reads, so it is rebuilt from the loaded values (the poly rule keeps its base_lr /
-        max_iterations / power and the ITERATION COUNT of the block: pass iter_num to device_schedule() to resume elsewhere)."""
+        max_iterations / power and the ITERATION COUNT of the block: pass iter_num to device_schedule() to resume elsewhere).
+        A schedule= rule keeps its settings, each group's base LR and the iteration count of the block likewise, and the
+        block's LR is the rule's at that count, not the loaded one: the rule owns the LR."""
         blocks = self.sync_host() if self.device_hyper is not None else []
         super().load_state_dict(state_dict)
         if self.device_hyper is not None:
+            if self._umi_sched is not None and len(blocks) == len(self.param_groups):
+                self._build_hyper(None, dict(self._umi_sched, iter_num=float(blocks[0]["iter"])),
+                                  [float(h["base_lr"]) for h in blocks])
+                return
             poly = None
             if self._umi_poly and blocks:
                 h = blocks[0]
@@ -428,8 +534,8 @@ class SGD(_DeviceHyper, _Guarded, torch.optim.SGD):
                     L.call("umi_optim_sgd_multi", ptr, n, blocks, float(group["lr"]), mom, float(group["dampening"]),
                            float(group["weight_decay"]), int(bool(group["nesterov"])), int(first),
                            ops._stream())
-            if hyper is not None and self._umi_poly:
-                L.call("umi_optim_hyper_poly", hyper[gi][0].data_ptr(), ops._stream())
+            if hyper is not None:
+                self._advance_schedule(gi)
             for p, _ in touched:
                 _bump(p)
         if guarded:
@@ -438,10 +544,12 @@ class SGD(_DeviceHyper, _Guarded, torch.optim.SGD):
 
 
 class Adam(_DeviceHyper, _Guarded, torch.optim.Adam):
-    """torch.optim.Adam(lr, betas, eps, weight_decay) (L2 weight decay, no amsgrad) with a single-launch step."""
+    """torch.optim.Adam(lr, betas, eps, weight_decay) (no amsgrad) with a single-launch step: L2 weight decay, or with
+    `decoupled_weight_decay=True` torch's AdamW rule (the umi_optim_adamw_* entry points)."""
 
     @torch.no_grad()
     def step(self, closure=None):
+        me = "umi.optim." + type(self).__name__
         loss = None
         if closure is not None:
             with torch.enable_grad():
@@ -449,20 +557,23 @@ class Adam(_DeviceHyper, _Guarded, torch.optim.Adam):
         guarded = [] if self.guard is not None else None
         if guarded is not None and self.device_hyper is None:
             # the host cannot know whether a step was skipped: Adam's step count has to advance on the device
-            raise RuntimeError("umi.optim.Adam: a guarded step needs the device-side step count; call "
+            raise RuntimeError(f"{me}: a guarded step needs the device-side step count; call "
                                "optimizer.device_schedule() first (umi.graphs.GraphedStep(optimizers=[...]) does)")
         for gi, group in enumerate(self.param_groups):
             if group.get("amsgrad") or group.get("maximize") or group.get("differentiable") or group.get("capturable"):
-                raise NotImplementedError("umi.optim.Adam: amsgrad / maximize / differentiable / capturable are not supported")
+                raise NotImplementedError(f"{me}: amsgrad / maximize / differentiable / capturable are not supported")
             if isinstance(group["lr"], torch.Tensor):
-                raise NotImplementedError("umi.optim.Adam: tensor learning rates are not supported")
+                raise NotImplementedError(f"{me}: tensor learning rates are not supported")
             b1, b2 = (float(b) for b in group["betas"])
+            # decoupled: p *= 1 - lr * wd before the update instead of g += wd * p inside it (torch.optim.AdamW)
+            decoupled = bool(group.get("decoupled_weight_decay"))
+            fam = "umi_optim_adamw_multi" if decoupled else "umi_optim_adam_multi"
             hyper = self.device_hyper
             cap = torch.cuda.is_current_stream_capturing()
             if cap and hyper is None:
                 # torch.optim.Adam refuses capture unless capturable=True; here the host-side `step += 1` and the bias
                 # corrections baked into kernel arguments would silently repeat step t on every replay
-                raise RuntimeError("umi.optim.Adam: a captured step needs the device-side step count; call "
+                raise RuntimeError(f"{me}: a captured step needs the device-side step count; call "
                                    "optimizer.device_schedule() before capturing (umi.graphs.GraphedStep(optimizers=[...]) does)")
             by_step = {}
             touched = []
@@ -474,7 +585,7 @@ class Adam(_DeviceHyper, _Guarded, torch.optim.Adam):
                 st = self.state[p]
                 if len(st) == 0:
                     if cap:
-                        raise RuntimeError("umi.optim.Adam: first step inside a HIP-graph capture; run a warm-up step first")
+                        raise RuntimeError(f"{me}: first step inside a HIP-graph capture; run a warm-up step first")
                     st["step"] = torch.tensor(0.0, dtype=torch.float32)            # host scalar, as torch keeps it
                     st["exp_avg"] = torch.zeros_like(p, memory_format=torch.contiguous_format)
                     st["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.contiguous_format)
@@ -487,13 +598,14 @@ class Adam(_DeviceHyper, _Guarded, torch.optim.Adam):
                                                   st["exp_avg_sq"].data_ptr(), p.numel()))
                 touched.append((p, g))
             tabs = self.__dict__.setdefault("_umi_tables", {})
+            eps, wd = float(group["eps"]), float(group["weight_decay"])
             if guarded is not None:
                 tables = [_table(tabs, (gi, slot), cap, rr) + (slot,) for slot, (t, rr) in enumerate(sorted(by_step.items()))]
 
-                def launch(table, st, group=group, b1=b1, b2=b2, hp=hyper[gi][0].data_ptr()):
+                def launch(table, st, fam=fam, decoupled=decoupled, b1=b1, b2=b2, eps=eps, wd=wd, hp=hyper[gi][0].data_ptr()):
                     ptr, n, blocks, _ = table
-                    L.call("umi_optim_adam_multi_guarded", ptr, n, blocks, hp, 0.0, b1, b2, 1.0, float(group["eps"]),
-                           float(group["weight_decay"]), st, ops._stream())
+                    host = (0.0, 0.0) if decoupled else (0.0,)         # (lr,) step_size: the block's are used
+                    L.call(fam + "_guarded", ptr, n, blocks, hp, *host, b1, b2, 1.0, eps, wd, st, ops._stream())
                 guarded.append((gi, tables, launch))
                 for p, _ in touched:
                     _bump(p)
@@ -503,17 +615,24 @@ class Adam(_DeviceHyper, _Guarded, torch.optim.Adam):
             for slot, (t, rr) in enumerate(sorted(by_step.items())):
                 ptr, n, blocks = _table(tabs, (gi, slot), cap, rr)
                 if hyper is not None:
-                    L.call("umi_optim_adam_multi_dev", ptr, n, blocks, hyper[gi][0].data_ptr(), b1, b2, float(group["eps"]),
-                           float(group["weight_decay"]), ops._stream())
+                    L.call(fam + "_dev", ptr, n, blocks, hyper[gi][0].data_ptr(), b1, b2, eps, wd, ops._stream())
                     continue
                 bc1 = 1.0 - b1 ** t
                 bc2 = 1.0 - b2 ** t
-                L.call("umi_optim_adam_multi", ptr, n, blocks, float(group["lr"]) / bc1, b1, b2, math.sqrt(bc2),
-                       float(group["eps"]), float(group["weight_decay"]), ops._stream())
-            if hyper is not None and self._umi_poly and touched:
-                L.call("umi_optim_hyper_poly", hyper[gi][0].data_ptr(), ops._stream())
+                lr = float(group["lr"])
+                L.call(fam, ptr, n, blocks, *((lr,) if decoupled else ()), lr / bc1, b1, b2, math.sqrt(bc2), eps, wd,
+                       ops._stream())
+            if hyper is not None and touched:
+                self._advance_schedule(gi)
             for p, _ in touched:
                 _bump(p)
         if guarded:
             self._guarded_step(guarded)
         return loss
+
+
+class AdamW(_DeviceHyper, _Guarded, torch.optim.AdamW):
+    """torch.optim.AdamW(lr, betas, eps, weight_decay) (decoupled weight decay, no amsgrad) with a single-launch step: the step
+    of `Adam` on the umi_optim_adamw_* entry points.  Same `state_dict()` layout as torch's."""
+
+    step = Adam.step
