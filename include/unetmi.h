@@ -765,6 +765,35 @@ int umi_ema_pre(double* state, const double* guard, umi_stream_t stream);
 int umi_ema_multi(const void* descs, int n_desc, int total_blocks, const double* state, umi_stream_t stream);
 int umi_ema_swap_multi(const void* descs, int n_desc, int total_blocks, umi_stream_t stream);
 
+/* Gradient accumulation: one optimizer step over the mean gradient of a WINDOW of micro-batches, summed on the device in one
+ * launch per micro-batch, so that a captured HIP graph keeps accumulating.  The state is a DEVICE array of UMI_ACCUM_LEN doubles
+ * (8-byte aligned), as the guard and EMA blocks are:
+ *   state      COUNT (micro-batches in the open window; 0: closed)
+ *   this call  FIRST, LAST, SCALE (written by pre, read by multi)
+ *   totals     WINDOWS (windows closed so far), MICRO (calls so far)
+ * One call per micro-batch, after its backward pass:  umi_grad_accum_pre, then umi_grad_accum_multi per descriptor table.
+ *   pre    one thread, all in double, with J = COUNT:  FIRST = (J == 0); LAST = (last != 0);
+ *          SCALE = (double)(float)(1.0 / (J + 1)); COUNT = last ? 0 : J + 1; MICRO += 1; WINDOWS += (last != 0).
+ *          "First" lives in the block and not in an argument: one captured micro-step serves every non-final position.
+ *   multi  over a umi_optim_desc table: `g` the fp32 gradient, `s0` its fp32 accumulator, `n` and `blk0` as for the optimizer;
+ *          `p` and `s1` are not read.  With s = (float)SCALE, per element:
+ *              LAST 0, FIRST 1   s0 = g              words are moved; s0 is NOT read: nobody ever zeroes the accumulator
+ *              LAST 0, FIRST 0   s0 = s0 + g         one fp32 rounding; g is not written
+ *              LAST 1, FIRST 1   (a window of one)   returns before any access: g keeps its bits, NaN payloads included
+ *              LAST 1, FIRST 0   g = (s0 + g) * s    two fp32 roundings (never a fused multiply-add); s0 is not written
+ *          so the gradient of a window of r micro-batches is float32(1 / r) * (((g1 + g2) + g3) + ... + gr) in fp32, in arrival
+ *          order, and it lands in the gradient itself.  NOTE: the desc declares `g` as `const float*`; the LAST-and-not-FIRST
+ *          pass WRITES through it (the table is the optimizer's, its gradients are the destination here).
+ *          Any pointer alignment of 4 bytes: 16-byte accesses where g and s0 share their offset into a 16-byte line (at most
+ *          three leading and three trailing elements of a block go one by one), one element per lane where they do not.
+ *          Exactly n elements are written per tensor.  No atomics; every store is a vector store.
+ * A null or misaligned state, null descs with n_desc > 0 and negative counts are UMI_ERR_BADARG before any launch; n_desc == 0
+ * succeeds and launches nothing; UMI_ERR_UNSUPPORTED if umi_optim_block_elems() is not this file's block. */
+enum { UMI_ACCUM_COUNT = 0, UMI_ACCUM_FIRST = 1, UMI_ACCUM_LAST = 2, UMI_ACCUM_SCALE = 3, UMI_ACCUM_WINDOWS = 4,
+       UMI_ACCUM_MICRO = 5, UMI_ACCUM_SPARE0 = 6, UMI_ACCUM_SPARE1 = 7, UMI_ACCUM_LEN = 8 };
+int umi_grad_accum_pre(double* state, int last, umi_stream_t stream);
+int umi_grad_accum_multi(const void* descs, int n_desc, int total_blocks, const double* state, umi_stream_t stream);
+
 /* umi_pack_kn / umi_pack_kn8 of many weight tensors in one launch (all the convolution weights of a model after an
  * optimizer step).  `descs`: DEVICE array sorted by blk0; an entry owns ceil(T*Kpad*Npad / umi_pack_block_elems()) blocks. */
 typedef struct umi_pack_desc {

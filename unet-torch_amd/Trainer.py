@@ -56,6 +56,13 @@ param group's own `lr` as its base and `iter_num` counted across epochs (and car
 num_epochs * len(train loader).  With a `umi.optim` optimizer the rule always lives in the device block
 (`optimizer.device_schedule(schedule=...)`), eager or replayed; with a torch optimizer the Trainer writes
 `param_groups[i]['lr']` on the host before each step.
+`Trainer(..., accumulate=k)` (keyword-only; None or 1: off, nothing of it is built; an int >= 2): one optimizer step over the mean
+gradient of a window of k consecutive training batches of an epoch (the last window of an epoch may be shorter), summed on the
+device by `umi.accum.GradAccumulator` in one launch per micro-batch; `train_step(inputs, labels, last=None)` steps on the last
+micro-batch of a window.  `iter_num`, both learning-rate rules, Adam's step count, the guard's `steps` and the EMA's updates count
+optimizer steps, `max_iterations` defaults to num_epochs * ceil(len(train loader) / k), epoch losses stay means over batches;
+BatchNorm statistics are per micro-batch.  One line in `logs.txt` per run: `Gradient accumulation: K micro-batches per optimizer
+step, S optimizer steps per epoch`.  See umi/accum.py.
 `lr_scheduler=True` (what the reference's train.py passes) crashes the reference in its first validation after epoch 5
 (`True.step`); here train() raises NotImplementedError before the first step whenever the run would reach that point.
 The remaining epoch loops of the reference (uncertainty-weighted multi-task, CLTR, Topo losses) are out of scope and raise.
@@ -82,7 +89,7 @@ class Trainer():
     def __init__(self, model, model_type, dtype, device, output_save_dir, dataloaders, batch_size, optimizer,
                  patience, num_epochs, loss_function, accuracy_metric, lr_scheduler=None, start_epoch=1, *, graph=None,
                  batch_transform=None, grad_guard=None, data_parallel=None, val_batch=None, val_confusion=False,
-                 async_checkpoints=False, resume=None, ema=None, lr_schedule=None):
+                 async_checkpoints=False, resume=None, ema=None, lr_schedule=None, accumulate=None):
         self.model = model
         self.model_type = model_type
         self.dtype = dtype
@@ -102,6 +109,11 @@ class Trainer():
         self.iter_num = 0
         self.base_lr = self.optimizer.param_groups[-1]['lr']
         self.max_iterations = self.num_epochs * len(self.dataloader['train'])
+        # gradient accumulation: micro-batches per optimizer step (0: off), the umi.accum.GradAccumulator (built by the first
+        # step, and only when on) and the host count of the open window.  Every count below is in OPTIMIZER steps
+        self._accum_k, self._accum, self._window = self._parse_accumulate(accumulate), None, 0
+        if self._accum_k:
+            self.max_iterations = self.num_epochs * -(-len(self.dataloader['train']) // self._accum_k)
         self.best_loss = 1e15
         self.best_val_score = 0 if accuracy_metric in ('dice_score', 'dice_score_mc') else 1e15
         self.best_model = []
@@ -175,11 +187,18 @@ class Trainer():
 
     def snapshot_run_state(self):
         """The whole training state into one device arena, between two steps of a live run (umi/run_state.py)."""
+        if self._window:
+            raise RuntimeError(f"snapshot_run_state() inside an open accumulation window ({self._window} of {self._accum_k} "
+                               "micro-batches): the accumulators are not part of the run state; close the window first")
         return self._run_state().snapshot()
 
     def restore_run_state(self):
         """The state of the last snapshot_run_state() back, in place."""
         self._run_state().restore()
+        if self._accum_k:                     # an open window is dropped: the snapshot was taken with the window closed
+            self._window = 0
+            if self._accum is not None:
+                self._accum.reset()
 
     @staticmethod
     def _parse_ema(spec):
@@ -202,6 +221,41 @@ class Trainer():
             return spec, True
         raise ValueError(f"ema takes None / False, True, a float (the decay), a dict(decay=, warmup=, validate=) or a "
                          f"umi.ema.ModelEMA, not {spec!r}")
+
+    @staticmethod
+    def _parse_accumulate(k):
+        """`accumulate` -> micro-batches per optimizer step, 0 for off (None or 1).  ValueError on anything else."""
+        if k is None:
+            return 0
+        if isinstance(k, bool) or not isinstance(k, int) or k < 1:
+            raise ValueError(f"accumulate takes None or an int >= 1 (1 = off), not {k!r}")
+        return 0 if k == 1 else k
+
+    @property
+    def accumulator(self):
+        """The umi.accum.GradAccumulator of this run (None: `accumulate` is off, or no step has run yet)."""
+        return self._accum
+
+    def _attach_accum(self):
+        """Before the first step of a run with `accumulate`: the accumulator over the model's parameters."""
+        if self._accum_k and self._accum is None:
+            from umi.accum import GradAccumulator
+            self._accum = GradAccumulator(self.model, self._accum_k)
+
+    def _accum_refusals(self):
+        if not self._accum_k:
+            return
+        if self._ratio_loop():
+            raise NotImplementedError("accumulate with multi_task_loss_ratio: the count-ratio loop is not covered")
+        spec = None if self._dp is None else self._dp.spec
+        if (isinstance(spec, dict) and spec.get("global_batch")) or getattr(spec, "batch_sync", None) is not None:
+            raise NotImplementedError("accumulate with data_parallel global_batch=True: the statistics collectives of every "
+                                      "micro-batch are not covered")
+
+    def _log_accum(self, say):
+        if self._accum_k:
+            say("Gradient accumulation: %i micro-batches per optimizer step, %i optimizer steps per epoch"
+                % (self._accum_k, -(-len(self.dataloader['train']) // self._accum_k)))
 
     @property
     def ema(self):
@@ -290,6 +344,7 @@ class Trainer():
     def train(self):
         if self._ema_spec is not None and self._ratio_loop():
             raise NotImplementedError("ema with multi_task_loss_ratio: the count-ratio loop is not covered")
+        self._accum_refusals()
         if not self.async_checkpoints and self._run is None:
             return self._train_dp()
         run = self._run_state()
@@ -368,7 +423,41 @@ class Trainer():
             return out, self._task_losses[0] + self._task_losses[1]
         return out, calc_loss(out, labels, loss_type=self.loss_function)
 
-    def _step_body(self, inputs, labels, deferred=False):
+    def _accum_step_body(self, inputs, labels, deferred, last):
+        """A step of a run with `accumulate`: the micro-step (forward, loss, zero_grad, backward, add) and, on the `last`
+        micro-batch of a window, the tail of _step_body on the window's mean gradient.  Under a reducer every backward pass runs
+        in its deferred mode, so a window costs one set of collectives."""
+        reducer = None if self._dp is None else self._dp.reducer
+        with torch.set_grad_enabled(True):
+            _, loss = self._forward_loss(inputs, labels)
+            self.optimizer.zero_grad()
+            if reducer is not None:
+                reducer.deferred = True       # the tape fills the buckets and launches nothing
+            try:
+                loss.backward()
+            finally:
+                if reducer is not None:
+                    reducer.deferred = False
+            filled = reducer is not None and reducer._marked
+            self._accum.add(last=last)        # on the bucket views where the tape filled them, else on .grad
+            if not last:
+                if filled:
+                    reducer.reset()
+                return loss
+            if deferred:                      # captured data-parallel step: flush() and optimizer.step() follow each replay
+                return loss
+            if filled:
+                reducer.flush()               # the window's collectives; .grad -> the bucket slots
+            elif self.grad_sync is not None:
+                self.grad_sync()
+            self.optimizer.step()
+            if self._ema is not None:
+                self._ema.update()
+        return loss
+
+    def _step_body(self, inputs, labels, deferred=False, last=True):
+        if self._accum is not None:
+            return self._accum_step_body(inputs, labels, deferred, last)
         with torch.set_grad_enabled(True):
             _, loss = self._forward_loss(inputs, labels)
             self.optimizer.zero_grad()
@@ -390,11 +479,16 @@ class Trainer():
             return reducer.world == 1 or reducer.batch_sync is None
         return self.grad_sync is None
 
-    def train_step(self, inputs, labels):
-        """One optimisation step (reference Trainer.py:700-726).  Returns the detached loss tensor."""
+    def train_step(self, inputs, labels, *, last=None):
+        """One optimisation step (reference Trainer.py:700-726).  Returns the detached loss tensor.
+        With `accumulate`: one micro-batch; the optimizer steps when it is the `last` of its window (None: the Trainer's own
+        count, every `accumulate`-th call; True closes the window now).  Without it `last` is not looked at."""
         inputs, labels = self._to_device(inputs, labels)
         self._attach_guard()
         self._attach_ema()
+        if self._accum_k:
+            self._attach_accum()
+            return self._accum_train_step(inputs, labels, self._window + 1 >= self._accum_k if last is None else bool(last))
         if self._graph_capable(inputs):
             return self._graphed_train_step(inputs, labels)
         guarded_adam = self._guard is not None and "betas" in self.optimizer.param_groups[0]
@@ -410,7 +504,29 @@ class Trainer():
         self.iter_num += 1
         return loss.detach()
 
-    def _graphed_train_step(self, inputs, labels):
+    def _accum_train_step(self, inputs, labels, last):
+        """train_step of a run with `accumulate`: iter_num and the learning-rate rules move with the optimizer step."""
+        if self._graph_capable(inputs):
+            loss = self._graphed_train_step(inputs, labels, last)
+            self._window = 0 if last else self._window + 1
+            self._accum.position = self._window               # (a replay does not pass through add())
+            return loss
+        guarded_adam = self._guard is not None and "betas" in self.optimizer.param_groups[0]
+        if guarded_adam or self._schedule_on_device(inputs.is_cuda):
+            self._device_schedule()
+        elif self._lr_schedule is not None:
+            self._host_schedule()
+        loss = self._step_body(inputs, labels, last=last)
+        self._window = 0 if last else self._window + 1
+        if last:
+            if self.lr_scheduler and not guarded_adam:
+                lr_ = self.base_lr * (1.0 - self.iter_num / self.max_iterations) ** 0.9
+                for group in self.optimizer.param_groups:
+                    group['lr'] = lr_
+            self.iter_num += 1
+        return loss.detach()
+
+    def _graphed_train_step(self, inputs, labels, last=True):
         from umi.graphs import GraphedStep
         self._device_schedule()
         if self._side is None:
@@ -419,6 +535,8 @@ class Trainer():
         multi = isinstance(labels, (list, tuple))
         ratio = self._ratio_loop()
         key = tuple(tuple(t.shape) for t in flat)
+        if self._accum is not None:           # two graphs per batch shape: the micro-step and the final step
+            key += (("final",) if last else ("micro",),)
         if ratio and self._gate_dev is None:       # the gate as a device flag: a captured kernel argument would freeze it
             self._gate_dev = torch.full((), float(self._ratio_gate), dtype=torch.float32, device=inputs.device)
 
@@ -428,7 +546,7 @@ class Trainer():
         deferred = reducer is not None and reducer.world > 1
 
         def body(x, *ys, deferred=False):
-            loss = self._step_body(x, tuple(ys) if multi else ys[0], deferred)
+            loss = self._step_body(x, tuple(ys) if multi else ys[0], deferred, last)
             extra = (self._task_losses if multi else []) + ([self._ratio] if ratio else [])
             return (loss.detach(),) + tuple(t.detach() for t in extra)
 
@@ -444,7 +562,7 @@ class Trainer():
                     reducer.deferred = False                        # first steps of other shapes and ragged batches stay eager
         if gs is not None:
             outs = gs(*flat)
-            if deferred:
+            if deferred and last:
                 reducer.flush()
                 self.optimizer.step()
                 if self._ema is not None:
@@ -461,7 +579,8 @@ class Trainer():
             self._task_losses = [o.clone() for o in outs[1:3]]
         if ratio:
             self._ratio = outs[3].clone()
-        self.iter_num += 1
+        if last:
+            self.iter_num += 1
         return outs[0].clone()            # the static output buffer is overwritten by the next replay
 
     def eval_step(self, inputs, labels):
@@ -622,6 +741,7 @@ class Trainer():
         log, say = self._open_log()
         if dp is not None and dp.note:
             say(dp.note)
+        self._log_accum(say)
 
         use_cuda = torch.cuda.is_available()
         total_mem = f'{torch.cuda.get_device_properties(0).total_memory / 1E9 if use_cuda else 0:.3g}G'
@@ -657,7 +777,9 @@ class Trainer():
                     for inputs, labels in bar:
                         bar.set_description(f"Epoch {epoch}")
                         steps += 1
-                        if train:
+                        if train and self._accum_k:          # a window never spans two epochs
+                            loss = self.train_step(inputs, labels, last=True if steps == len(self.dataloader[phase]) else None)
+                        elif train:
                             loss = self.train_step(inputs, labels)
                         else:
                             loss, score = self.eval_step(inputs, labels)
